@@ -1,6 +1,7 @@
 """Benchmark of the CDDMSL training step on MI355X (BASELINE.json metric: images/sec of the train step).
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched under torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed, DIR/<name>.npy)
 
 Workload (config.workload): configs[1] of BASELINE.json -- VOC(labeled)+Clipart(unlabeled) CLIP RN50-C4 Faster R-CNN +
 caption consistency, 16 images/GPU of 800x1333, bf16 MFMA, iteration > 10000 so all three branches of
@@ -24,6 +25,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")   # (see cddmsl_amd/__init__.py; set before anything can initialise the HIP runtime)
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -84,6 +86,48 @@ def cpu_baseline(height, width, threads, batch=2, timed=3, budget_s=150.0):
             "sample": f"B={batch} images {height}x{width}, full step (3 branches, backward, clip+SGD), oracle fp32 on "
                       f"{threads} threads of {cpu_model_name()}; 1 warm-up ({warm:.1f} s) then median of {len(times)} "
                       f"timed steps ({', '.join('%.1f' % t for t in times)} s)"}
+
+
+def step_outputs(losses, params, sample=4 << 20, seed=0):
+    """What the last timed step hands its caller, as host arrays for ``--dump-outputs``: every loss (float64, shape [1]) and the
+    trainable parameters after the step's SGD update with the step's gradients (float32).  Parameters and gradients are flattened
+    in optimizer order, each tensor in its logical row-major order, and read at one fixed, seeded sample of positions (the full
+    48.4 M values would be 194 MB per array); ``sample`` draws keep the two arrays near 16 MB each."""
+    out = {k: np.array([float(v.detach())], dtype=np.float64) for k, v in losses.items()}
+    total = sum(p.numel() for p in params)
+    idx = np.arange(total) if total <= sample else np.unique(np.random.default_rng(seed).integers(0, total, size=sample))
+    idx = torch.from_numpy(idx).to(params[0].device)
+    out["params_sample"] = torch.cat([p.detach().reshape(-1).float() for p in params])[idx].cpu().numpy()
+    out["grads_sample"] = torch.cat([p.grad.detach().reshape(-1).float() for p in params])[idx].cpu().numpy()
+    return out
+
+
+class StartState:
+    """The trainer's state before its first step: trainable weights, the step / optimizer counters, the samplers' generators and the
+    loader's position.  ``restore()`` puts it back, so that the step after it computes from the same inputs on every run -- the
+    steps before it update the weights with gradient sums some kernels add with f32 atomics, whose last bits vary from run to run
+    and which later steps carry into which proposals they sample.  (``--dtype fp8``: the delayed scales the earlier steps recorded
+    stay; they belong to the quantisers, which calibrate once per tensor.)"""
+
+    def __init__(self, tr):
+        from cddmsl_amd import layers
+        self.tr, self.layers = tr, layers
+        self.params = [p.detach().clone() for p in tr.optimizer.params]
+        self.iter, self.steps_done = tr.iter, tr.optimizer.steps_done
+        m = tr.model
+        self.gens = [(g, g.get_state()) for g in (m.proposal_generator.sample_generator, m.roi_heads.sample_generator, m.region_generator)]
+        self.loader_i = tr.data_loader.i
+
+    def restore(self):
+        tr, layers = self.tr, self.layers
+        with torch.no_grad():
+            for p, v in zip(tr.optimizer.params, self.params):
+                p.copy_(v)
+        layers.bump_weight_version()                     # prepared (cast / transposed / e4m3) weight copies are stale now
+        tr.iter, tr.optimizer.steps_done = self.iter, self.steps_done   # steps_done 0: the SGD step starts its momentum afresh
+        for g, st in self.gens:
+            g.set_state(st)
+        tr.data_loader.i = self.loader_i
 
 
 def visible_gpu_count(env=os.environ):
@@ -152,7 +196,12 @@ def main():
     ap.add_argument("--cpu-baseline-steps", type=int, default=3, help="timed oracle steps (median reported), after one warm-up")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal: start the ranks, form the process group (gloo when "
                     "no GPU is visible), barrier, print the rank layout; no model, no timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(rank 0): its losses, and a fixed, seeded sample of the updated parameters and of their gradients; the last "
+                    "timed step starts from the seeded state, so the arrays depend on the arguments alone")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # one process per GPU: with --gpus N > 1 and no launcher around us, start N ranks as children (before any GPU call)
     mode, cmd = launch_plan(args.gpus, sys.argv[1:], os.environ, visible_gpu_count() if args.gpus > 1 and "RANK" not in os.environ else 1)
@@ -190,6 +239,7 @@ def main():
     tr.clipcap_model.load_state_dict(synthetic.make_mapper_state_dict(1))
     tr.iter = 20000          # past burn-in (train_loop.py:334): every branch is computed AND contributes gradients
     tr.metrics_period = 0    # no per-step host sync inside the timed region (losses stay on device)
+    start = StartState(tr)   # the last timed step starts again from here: its inputs are the same on every run (--dump-outputs)
 
     def barrier():
         if world > 1:
@@ -218,17 +268,33 @@ def main():
             dom_name = max(rows, key=lambda k: full[k]["ms"])
     barrier()
     t0 = time.perf_counter()
-    for i in range(args.steps):
-        if i == args.steps - 1:                        # the dominant kernel's launches of the LAST timed step carry the events
-            hip.PROFILE.enable(only={dom_name})
-        last = tr.run_step()
+    for i in range(args.steps - 1):
+        ld_ = tr.run_step()
         if step0 is None:
-            step0 = last
+            step0 = ld_
     barrier()
     dt = time.perf_counter() - t0
+    # the LAST timed step: from the state before the first step (put back outside the timing), so that what it computes -- the
+    # --dump-outputs arrays -- depends on the arguments alone; its kernels and shapes are those of every other step.  The dominant
+    # kernel's launches of this step carry the events.
+    start.restore()
+    barrier()
+    t0 = time.perf_counter()
+    hip.PROFILE.enable(only={dom_name})
+    last = tr.run_step()
+    if step0 is None:
+        step0 = last
+    barrier()
+    dt += time.perf_counter() - t0
     dom_shapes = hip.PROFILE.by_shape()
     prof = hip.PROFILE.collect()
     prof_steps = 1
+    dumped = None
+    if args.dump_outputs and rank == 0:                # read before any later step or forward can touch the model
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = step_outputs(last, tr.buckets.params)
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     if full is None:                                   # --warmup 0: the instrumented step runs after the timed region
         hip.PROFILE.enable()
         tr.run_step()
@@ -328,6 +394,8 @@ def main():
             "losses": losses,
             "losses_gate": gate,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": sorted(k + ".npy" for k in dumped)}
         if fwd_ms is not None:
             ftf = 1.878 * args.batch
             out["forward_roofline"] = {"what": "supervised RN50-C4 forward only (autograd recording on), algorithmic 1.878 TFLOP/image",

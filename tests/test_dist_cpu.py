@@ -4,6 +4,7 @@ intends, and match the oracle's simulated two-rank computation."""
 import os
 import socket
 
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
@@ -89,6 +90,62 @@ def test_bench_launch_plan():
     with pytest.raises(SystemExit) as e:
         b.launch_plan(2, [], {}, 1)
     assert "needs 2 visible GPUs" in str(e.value)
+
+
+def test_bench_step_outputs_sample_is_fixed():
+    """bench.py --dump-outputs: losses as float64, parameters and gradients (logical row-major order, channels_last included) as
+    float32 at the same seeded positions on every call; a parameter set no larger than the sample is written whole."""
+    b = _bench()
+    rng = np.random.default_rng(0)
+    w, w_grad = rng.standard_normal((8, 3, 3, 3), dtype=np.float32), rng.standard_normal((8, 3, 3, 3), dtype=np.float32)
+    v, v_grad = rng.standard_normal(5, dtype=np.float32), rng.standard_normal(5, dtype=np.float32)
+    params = [torch.from_numpy(w).to(memory_format=torch.channels_last), torch.from_numpy(v)]
+    params[0].grad = torch.from_numpy(w_grad).to(memory_format=torch.channels_last)
+    params[1].grad = torch.from_numpy(v_grad)
+    assert not params[0].is_contiguous() and not params[0].grad.is_contiguous()      # NHWC storage: logical order != memory order
+    flat_p, flat_g = np.concatenate([w.reshape(-1), v]), np.concatenate([w_grad.reshape(-1), v_grad])   # numpy C order = logical
+    losses = {"loss_cls": torch.tensor(1.5), "cont_loss": torch.tensor(0.25)}
+    whole = b.step_outputs(losses, params)
+    assert sorted(whole) == ["cont_loss", "grads_sample", "loss_cls", "params_sample"]
+    assert whole["loss_cls"].dtype == np.float64 and whole["loss_cls"].tolist() == [1.5]
+    assert whole["params_sample"].dtype == np.float32 and np.array_equal(whole["params_sample"], flat_p)
+    assert np.array_equal(whole["grads_sample"], flat_g)
+    s1, s2 = b.step_outputs(losses, params, sample=50), b.step_outputs(losses, params, sample=50)
+    assert 0 < len(s1["params_sample"]) <= 50 and np.array_equal(s1["params_sample"], s2["params_sample"])
+    pos = [int(np.flatnonzero(flat_p == x)[0]) for x in s1["params_sample"]]      # (randn values: distinct)
+    assert pos == sorted(set(pos)) and np.array_equal(s1["grads_sample"], flat_g[pos])
+
+
+def test_bench_start_state_restores_the_inputs_of_a_step():
+    """bench.py's StartState: after steps have changed the weights, the counters, the samplers and the loader position, restore()
+    puts back exactly what the first step saw (the last timed step's inputs are then the same on every run)."""
+    from types import SimpleNamespace
+
+    from cddmsl_amd import layers
+    b = _bench()
+    gens = [torch.Generator().manual_seed(s) for s in (1, 2, 3)]
+    w = torch.nn.Parameter(torch.randn(4, 3, generator=gens[0]))
+    tr = SimpleNamespace(optimizer=SimpleNamespace(params=[w], steps_done=0), iter=20000, data_loader=SimpleNamespace(i=0),
+                         model=SimpleNamespace(proposal_generator=SimpleNamespace(sample_generator=gens[0]),
+                                               roi_heads=SimpleNamespace(sample_generator=gens[1]), region_generator=gens[2]))
+    w0 = w.detach().clone()
+    want = []                                             # each sampler's next draws as the first step would see them
+    for g in gens:
+        h = torch.Generator()
+        h.set_state(g.get_state())
+        want.append(torch.randint(0, 1 << 30, (3,), generator=h))
+    start = b.StartState(tr)
+    version = layers._STEP[0]
+    with torch.no_grad():                                 # what steps do to the state
+        w.add_(1.0)
+    tr.iter, tr.optimizer.steps_done, tr.data_loader.i = 20005, 5, 5
+    for g in gens:
+        torch.randint(0, 10, (7,), generator=g)
+    start.restore()
+    assert torch.equal(w.detach(), w0) and w.requires_grad
+    assert (tr.iter, tr.optimizer.steps_done, tr.data_loader.i) == (20000, 0, 0)
+    assert all(torch.equal(torch.randint(0, 1 << 30, (3,), generator=g), x) for g, x in zip(gens, want))
+    assert layers._STEP[0] != version                     # cached copies of the weights are refreshed
 
 
 def test_bench_gpus2_without_devices_exits_nonzero():
