@@ -114,6 +114,7 @@ class DatasetMapper:
         anns = d.pop("annotations", None)
         if not self.is_train or anns is None:
             return d
+        anns = [a for a in anns if not a.get("iscrowd", 0)]                                        # dataset_mapper.py:203
         boxes = np.asarray([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
         boxes = boxes * np.array([neww / w, newh / h, neww / w, newh / h])            # ResizeTransform.apply_coords
         if do_flip:

@@ -177,3 +177,195 @@ def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False):
     if rank == 0:
         print({k: round(v, 4) for k, v in res["bbox"].items()})
     return res if return_results else 0
+
+
+# ------------------------------------------------------------------------------------------------ COCO-style box AP
+COCO_IOU_THRS = np.linspace(0.5, 0.95, 10)
+COCO_REC_THRS = np.linspace(0.0, 1.0, 101)
+COCO_AREA_RNGS = ((0.0, 1e5 ** 2), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))    # all, small, medium, large
+COCO_MAX_DETS = 100
+
+
+def coco_box_iou(dt, gt, iscrowd):
+    """pycocotools ``maskUtils.iou`` on XYWH boxes: [D,G] IoU; against a crowd GT the union is the detection's own area"""
+    if len(dt) == 0 or len(gt) == 0:
+        return np.zeros((len(dt), len(gt)))
+    iw = np.minimum(dt[:, None, 0] + dt[:, None, 2], gt[None, :, 0] + gt[None, :, 2]) - np.maximum(dt[:, None, 0], gt[None, :, 0])
+    ih = np.minimum(dt[:, None, 1] + dt[:, None, 3], gt[None, :, 1] + gt[None, :, 3]) - np.maximum(dt[:, None, 1], gt[None, :, 1])
+    inter = np.maximum(iw, 0.0) * np.maximum(ih, 0.0)
+    da, ga = dt[:, 2] * dt[:, 3], gt[:, 2] * gt[:, 3]
+    union = np.where(np.asarray(iscrowd, dtype=bool)[None, :], da[:, None], da[:, None] + ga[None, :] - inter)
+    return inter / union
+
+
+def _coco_match(dt_boxes, dt_scores, gt_boxes, gt_area, gt_crowd, area_rng):
+    """``COCOeval.evaluateImg`` for one (image, class, area range): -> (scores, matched [T,D] bool, ignored [T,D] bool, n non-ignored gt)"""
+    gt_ig = gt_crowd | (gt_area < area_rng[0]) | (gt_area > area_rng[1])
+    gorder = np.argsort(gt_ig, kind="mergesort")                # non-ignored GT first
+    gb, gig, gcrowd = gt_boxes[gorder], gt_ig[gorder], gt_crowd[gorder]
+    dorder = np.argsort(-dt_scores, kind="mergesort")[:COCO_MAX_DETS]
+    db, ds = dt_boxes[dorder], dt_scores[dorder]
+    ious = coco_box_iou(db, gb, gcrowd)
+    T, D, G = len(COCO_IOU_THRS), len(db), len(gb)
+    gtm = np.zeros((T, G), dtype=bool)
+    dtm = np.zeros((T, D), dtype=bool)
+    dtig = np.zeros((T, D), dtype=bool)
+    for ti, t in enumerate(COCO_IOU_THRS):
+        for d in range(D):
+            iou, m = min(t, 1 - 1e-10), -1
+            for g in range(G):
+                if gtm[ti, g] and not gcrowd[g]:
+                    continue
+                if m > -1 and not gig[m] and gig[g]:         # already matched a real GT: stop at the ignored ones
+                    break
+                if ious[d, g] < iou:
+                    continue
+                iou, m = ious[d, g], g
+            if m == -1:
+                continue
+            dtig[ti, d], dtm[ti, d], gtm[ti, m] = gig[m], True, True
+    darea = db[:, 2] * db[:, 3]
+    out_rng = (darea < area_rng[0]) | (darea > area_rng[1])
+    dtig |= ~dtm & out_rng[None, :]
+    return ds, dtm, dtig, int((~gig).sum())
+
+
+def coco_precision(gt_by_image, dt_by_image, num_classes):
+    """``COCOeval.evaluate`` + ``accumulate`` (bbox, maxDets 100): precision [T, R=101, K, A=4], -1 where a class has no non-ignored GT.
+    ``gt_by_image[img] = (xywh [G,4], area [G], crowd [G] bool, class [G])``, ``dt_by_image[img] = (xywh [D,4], score [D], class [D])``."""
+    T, R, A = len(COCO_IOU_THRS), len(COCO_REC_THRS), len(COCO_AREA_RNGS)
+    prec = -np.ones((T, R, num_classes, A))
+    imgs = list(gt_by_image)
+    for k in range(num_classes):
+        for a, rng in enumerate(COCO_AREA_RNGS):
+            scores, dtm, dtig, npig = [], [], [], 0
+            for img in imgs:
+                gb, garea, gcrowd, gcls = gt_by_image[img]
+                g = gcls == k
+                db, dsc, dcls = dt_by_image.get(img, (np.zeros((0, 4)), np.zeros(0), np.zeros(0, dtype=np.int64)))
+                d = dcls == k
+                if not g.any() and not d.any():
+                    continue
+                s, m, ig, n = _coco_match(db[d], dsc[d], gb[g], garea[g], gcrowd[g], rng)
+                scores.append(s); dtm.append(m); dtig.append(ig); npig += n
+            if npig == 0:
+                continue
+            s = np.concatenate(scores) if scores else np.zeros(0)
+            order = np.argsort(-s, kind="mergesort")
+            m = np.concatenate(dtm, axis=1)[:, order] if dtm else np.zeros((T, 0), dtype=bool)
+            ig = np.concatenate(dtig, axis=1)[:, order] if dtig else np.zeros((T, 0), dtype=bool)
+            tps = np.cumsum(m & ~ig, axis=1, dtype=np.float64)
+            fps = np.cumsum(~m & ~ig, axis=1, dtype=np.float64)
+            for t in range(T):
+                tp, fp = tps[t], fps[t]
+                rc = tp / npig
+                pr = (tp / (fp + tp + np.spacing(1))).tolist()
+                for i in range(len(pr) - 1, 0, -1):           # precision envelope, from the right
+                    if pr[i] > pr[i - 1]:
+                        pr[i - 1] = pr[i]
+                q = np.zeros(R)
+                inds = np.searchsorted(rc, COCO_REC_THRS, side="left")
+                for ri, pi in enumerate(inds):
+                    if pi < len(pr):
+                        q[ri] = pr[pi]
+                prec[t, :, k, a] = q
+    return prec
+
+
+class COCODetectionEvaluator:
+    """COCO-style box AP (evaluation/coco_evaluation.py:292-360 over pycocotools ``COCOeval``, iouType "bbox") in numpy, with the
+    same ``reset / process / evaluate`` protocol and rank-0 gather as ``PascalVOCDetectionEvaluator``.  pycocotools is not a
+    dependency: parity unpinned against pycocotools -- the semantics below restate its published behaviour.
+
+    Ground truth comes from the dataset dicts: XYWH = (xmin, ymin, xmax - xmin, ymax - ymin), ``area`` as stored (the Cityscapes
+    loader stores the mask's pixel count, what D2's ``mask_util.area`` gives its RLE annotations), ``iscrowd`` regions are ignored
+    GT whose IoU with a detection is intersection over the detection's area.  Detections: XYXY -> XYWH, unrounded
+    (``instances_to_coco_json``).  Per (image, class) the top 100 by score (stable order) are matched at IoU .50:.05:.95 to the best
+    still-unmatched GT (non-ignored GT preferred; a detection matched to an ignored GT is ignored); area ranges all / small (<= 32^2)
+    / medium / large (> 96^2) judge the GT by ``area`` and unmatched detections by their box area; precision is made monotone from
+    the right and sampled at 101 recall points; classes without non-ignored GT are left out of the means.  Returns
+    ``{"bbox": {AP, AP50, AP75, APs, APm, APl, "AP-<class>"...}}`` in percent; NaN where nothing is defined (every key when there
+    are no detections at all)."""
+
+    def __init__(self, dataset_dicts, class_names):
+        self.class_names = list(class_names)
+        self._gt = {}
+        for d in dataset_dicts:
+            anns = d.get("annotations", [])
+            xyxy = np.array([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
+            xywh = np.concatenate([xyxy[:, :2], xyxy[:, 2:] - xyxy[:, :2]], axis=1)
+            area = np.array([a.get("area", (a["bbox"][2] - a["bbox"][0]) * (a["bbox"][3] - a["bbox"][1])) for a in anns], dtype=np.float64)
+            crowd = np.array([bool(a.get("iscrowd", 0)) for a in anns], dtype=bool)
+            cls = np.array([a["category_id"] for a in anns], dtype=np.int64)
+            self._gt[str(d["image_id"])] = (xywh, area, crowd, cls)
+        self.reset()
+
+    def reset(self):
+        self._predictions = {}           # image id -> (xywh [D,4], scores [D], classes [D])
+
+    def process(self, inputs, outputs):
+        for inp, out in zip(inputs, outputs):
+            inst = out["instances"]
+            b = inst.pred_boxes.tensor.detach().float().cpu().numpy().astype(np.float64).reshape(-1, 4)
+            xywh = np.concatenate([b[:, :2], b[:, 2:] - b[:, :2]], axis=1)
+            self._predictions[str(inp["image_id"])] = (xywh, inst.scores.detach().float().cpu().numpy().astype(np.float64),
+                                                       inst.pred_classes.detach().cpu().numpy().astype(np.int64))
+
+    def _gathered(self):
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return self._predictions
+        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+        dist.gather_object(self._predictions, parts, dst=0)
+        if dist.get_rank() != 0:
+            return None
+        merged = {}
+        for part in parts:
+            merged.update(part)
+        return merged
+
+    def evaluate(self):
+        preds = self._gathered()
+        if preds is None:
+            return None
+        metrics = ("AP", "AP50", "AP75", "APs", "APm", "APl")
+        res = OrderedDict()
+        if sum(len(p[1]) for p in preds.values()) == 0:
+            res.update({m: float("nan") for m in metrics})
+            res.update({"AP-" + n: float("nan") for n in self.class_names})
+            return {"bbox": res}
+        prec = coco_precision(self._gt, preds, len(self.class_names))
+
+        def mean(p):
+            p = p[p > -1]
+            return float(np.mean(p)) * 100 if p.size else float("nan")
+        res["AP"], res["AP50"], res["AP75"] = mean(prec[:, :, :, 0]), mean(prec[0, :, :, 0]), mean(prec[5, :, :, 0])
+        res["APs"], res["APm"], res["APl"] = mean(prec[:, :, :, 1]), mean(prec[:, :, :, 2]), mean(prec[:, :, :, 3])
+        for k, n in enumerate(self.class_names):
+            res["AP-" + n] = mean(prec[:, :, k, 0])
+        return {"bbox": res}
+
+
+def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_results=False):
+    """``--eval-only --datasets-root DIR``: every ``cfg.DATASETS.TEST`` name the catalog knows (the Cityscapes splits of
+    cddmsl_amd/cityscapes.py) -> COCO-style box AP, one printed line per set from rank 0; a name the catalog does not know
+    (e.g. ``bdd_100k_val``, which needs a COCO-json reader) is skipped with one printed line.  Returns the exit code (or
+    {name: result dict} on rank 0 with ``return_results``)."""
+    import torch.distributed as dist
+    from . import cityscapes
+    from .data import build_detection_test_loader
+    ws = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    assert world == ws, f"run_eval_only_catalog: world={world} but the process group has {ws} ranks"
+    results = OrderedDict()
+    for name in cfg.DATASETS.TEST:
+        if not cityscapes.is_cityscapes(name):
+            if rank == 0:
+                print(f"skipping {name}: not in the dataset catalog")
+            continue
+        dicts = cityscapes.load_cityscapes(name, datasets_root, device=cfg.MODEL.DEVICE)
+        loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
+        res = inference_on_dataset(model, loader, COCODetectionEvaluator(dicts, cityscapes.THING_CLASSES))
+        if rank == 0:
+            print(f"{name}: " + str({k: round(v, 4) for k, v in res["bbox"].items()}), flush=True)
+            results[name] = res
+    return results if return_results else 0

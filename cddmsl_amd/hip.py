@@ -85,6 +85,7 @@ def _L():
         L.cddmsl_attn_last_bwd.argtypes = [vp] * 6 + [ci] * 8 + [cf, ci, vp]
         L.cddmsl_contrastive_fwd.argtypes = [vp] * 4 + [ci, ci, vp]
         L.cddmsl_contrastive_bwd.argtypes = [vp] * 5 + [ci, ci, vp]
+        L.cddmsl_instance_boxes.argtypes = [vp] + [ci] * 4 + [vp, ci, vp, vp, vp, vp]
         _sigs_done = True
     return L
 
@@ -843,6 +844,46 @@ def workspace(key, nbytes, device):
         buf = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
         _WS[k] = buf
     return buf
+
+
+INSTANCE_ID_LO, INSTANCE_ID_HI = 24, 34000      # ids the instance-box kernel reports: [24, 34000)
+
+
+def instance_boxes(maps):
+    """Instance-id maps [B,H,W] (uint16 or int32, on the GPU) -> (records int32 [B,R,6], counts int32 [B]), enqueued on the current
+    stream, no synchronisation.  records[b,:counts[b]] = (id, xmin, ymin, xmax, ymax, npixels) for every id in [24, 34000) present in
+    map b, ascending id; counts[b] == -1 flags a map holding an id >= 34000 (``instance_boxes_host`` raises on it)."""
+    require_cuda(maps)
+    assert maps.dim() == 3 and maps.is_contiguous(), maps.shape
+    if maps.dtype not in (torch.uint16, torch.int32):
+        raise TypeError(f"instance maps must be uint16 or int32, got {maps.dtype}")
+    B, H, W = maps.shape
+    R = min(H * W, INSTANCE_ID_HI - INSTANCE_ID_LO)
+    records = torch.empty((B, R, 6), device=maps.device, dtype=torch.int32)
+    counts = torch.empty(B, device=maps.device, dtype=torch.int32)
+    dt = 0 if maps.dtype == torch.uint16 else 1
+    nbytes = ctypes.c_size_t(0)
+    check(_L().cddmsl_instance_boxes(ptr(maps), B, H, W, dt, None, R, None, None, ctypes.byref(nbytes), stream_ptr()),
+          "cddmsl_instance_boxes(size)")
+    ws = torch.empty(nbytes.value, device=maps.device, dtype=torch.uint8)      # torch's caching allocator, stream-ordered
+    check(_L().cddmsl_instance_boxes(ptr(maps), B, H, W, dt, ptr(records), R, ptr(counts), ptr(ws), ctypes.byref(nbytes), stream_ptr()),
+          "cddmsl_instance_boxes")
+    return records, counts
+
+
+def instance_boxes_host(maps):
+    """``instance_boxes`` + readback: a list of B numpy int32 arrays [n_b, 6].  Raises ``HipLibraryError`` (status 1,
+    CDDMSL_ERR_ARG) if a map holds an id >= 34000 -- such ids have no Cityscapes label and are never dropped silently."""
+    import numpy as np
+    from ._lib import HipLibraryError, Readback
+    records, counts = instance_boxes(maps)
+    n = Readback(counts).get().tolist()
+    bad = [b for b, c in enumerate(n) if c < 0]
+    if bad:
+        raise HipLibraryError(f"cddmsl_instance_boxes failed with status 1: map(s) {bad} hold an instance id >= {INSTANCE_ID_HI}")
+    top = max(n, default=0)
+    host = Readback(records[:, :top]).get().numpy() if top else None
+    return [host[b, :c].copy() if c else np.zeros((0, 6), dtype=np.int32) for b, c in enumerate(n)]
 
 
 @_timed("sort_desc")

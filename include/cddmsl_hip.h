@@ -273,6 +273,17 @@ int cddmsl_colsum(const void* x, float* out, long rows, int cols, int period, in
 int cddmsl_sgd_clip_step(float** params, const float** grads, float** moms, const long* sizes, int count, float* norm_ws,
                          float lr, float momentum, float wd, float clip, int first_step, void* stream);
 
+/* ---- Cityscapes instance boxes (input side, not the training step) -------------------------------------------------------
+ * replaces the per-id `inst_image == instance_id` + np.nonzero loop of data/datasets/cityscapes.py:501-540 (from_json=False).
+ * maps [B][H][W] instance ids, dtype 0 = uint16, 1 = int32.  For every map b, one record per id in [24, 34000) that occurs in it,
+ * in ascending id order: records[b][r][6] int32 = (id, xmin, ymin, xmax, ymax, npixels), the box being the inclusive pixel-index
+ * extent; counts[b] = number of records, or -1 if the map holds an id >= 34000 (no Cityscapes label: the reference's id2label
+ * raises; the device reports it here and the caller raises CDDMSL_ERR_ARG after its readback).  Ids below 24 are stuff and skipped.
+ * max_records >= min(H * W, 33976).  Workspace: call with ws == NULL to get *ws_bytes; it is zeroed on the stream by every call.
+ * Integer atomics only: the output is bit-identical from run to run. */
+int cddmsl_instance_boxes(const void* maps, int B, int H, int W, int dtype, int* records, int max_records, int* counts, void* ws,
+                          size_t* ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

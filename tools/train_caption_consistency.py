@@ -7,7 +7,9 @@
 One process per GPU (engine/launch.py:67-80): with --num-gpus > 1 this script re-launches itself under
 ``torch.distributed.run`` (RCCL over xGMI).  Datasets are not available offline, so by default the loader is the seeded synthetic
 paired-batch generator; ``--voc-root <VOCdevkit/VOC2007> --dt-data <twin dir>`` switches to the real paired VOC pipeline
-(cddmsl_amd/data.py), ``--eval-only --voc-root ...`` runs inference + Pascal VOC AP (cddmsl_amd/evaluation.py), and
+(cddmsl_amd/data.py), ``--eval-only --voc-root ...`` runs inference + Pascal VOC AP (cddmsl_amd/evaluation.py),
+``--datasets-root DIR`` does the same for the Cityscapes / Foggy Cityscapes splits of the AdverseWeather config (paired training
+loader; COCO-style box AP on every known DATASETS.TEST name; cddmsl_amd/cityscapes.py), and
 ``MODEL.WEIGHTS`` / ``--resume`` / ``MODEL.PRE_TRAINED_RCLIP_PATH`` go through cddmsl_amd/checkpoint.py.
 """
 import argparse
@@ -36,6 +38,9 @@ def default_argument_parser():
     p.add_argument("--dt-data", default="", help="directory name of the domain-translated twins next to the VOC root (e.g. clipart); "
                                                  "with --voc-root, train on the real paired loader instead of synthetic batches")
     p.add_argument("--voc-year", type=int, default=2007)
+    p.add_argument("--datasets-root", default="", metavar="DIR",
+                   help="directory holding cityscapes/{leftImg8bit,leftImg8bit_foggy,gtFine} (Detectron2's DETECTRON2_DATASETS): "
+                        "a Cityscapes DATASETS.TRAIN[0] trains on the real paired loader, --eval-only scores every known DATASETS.TEST name")
     p.add_argument("opts", default=None, nargs=argparse.REMAINDER)
     return p
 
@@ -51,7 +56,7 @@ def setup(args):
 
 def main(args):
     import torch
-    from cddmsl_amd import engine, synthetic
+    from cddmsl_amd import cityscapes, engine, synthetic
     rank, world = engine.init_distributed()
     from cddmsl_amd.config import auto_scale_workers
     cfg = auto_scale_workers(setup(args), world)                              # engine/defaults.py:374
@@ -75,12 +80,21 @@ def main(args):
         print(f"MODEL.PRE_TRAINED_RCLIP_PATH {rclip} not found: the offline (teacher) backbone keeps its loaded / synthetic weights")
     if args.eval_only:              # train_caption_consistency.py:143-152: model.eval(); inference over the test sets
         from cddmsl_amd import evaluation
-        assert args.voc_root, "--eval-only needs --voc-root (a VOC devkit year directory) : datasets are not shipped"
+        if args.datasets_root and not args.voc_root:
+            raise SystemExit(evaluation.run_eval_only_catalog(tr.model, cfg, args.datasets_root, rank, world))
+        assert args.voc_root, "--eval-only needs --voc-root (a VOC devkit year directory) or --datasets-root: datasets are not shipped"
         raise SystemExit(evaluation.run_eval_only(tr.model, cfg, args, rank, world))
     if args.voc_root and args.dt_data:      # real paired data; default: seeded synthetic batches
         from cddmsl_amd import data
         from cddmsl_amd.evaluation import VOC_CLASS_NAMES
         dicts = data.load_voc_instances(args.voc_root, "trainval", VOC_CLASS_NAMES[: cfg.MODEL.ROI_HEADS.NUM_CLASSES], dt_data=args.dt_data)
+        tr.data_loader = data.build_detection_train_loader(cfg, dicts, per_rank, rank, world, cfg.MODEL.DEVICE)
+        tr._data_loader_iter = iter(tr.data_loader)
+    elif args.datasets_root and cfg.DATASETS.TRAIN and cityscapes.is_cityscapes(cfg.DATASETS.TRAIN[0]):
+        from cddmsl_amd import data      # Cityscapes + Foggy twins (configs/AdverseWeather-Experiments)
+        dicts = cityscapes.load_cityscapes(cfg.DATASETS.TRAIN[0], args.datasets_root, device=cfg.MODEL.DEVICE)
+        if cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS:
+            dicts = cityscapes.filter_images_with_only_crowd_annotations(dicts)
         tr.data_loader = data.build_detection_train_loader(cfg, dicts, per_rank, rank, world, cfg.MODEL.DEVICE)
         tr._data_loader_iter = iter(tr.data_loader)
     max_iter = args.max_iter or cfg.SOLVER.MAX_ITER
