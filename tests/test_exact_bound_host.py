@@ -1,0 +1,202 @@
+"""The exact-product checker itself (tests/exact_gemm.py), on the CPU: the float64 reference against ATen, the bound against an f32
+convolution in another summation order, negative controls the bound must reject -- with the verdict of the old 2e-2 * max criterion
+printed next to it -- and the coverage of the bench's recorded launches by the GPU case table."""
+import json
+import os
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import exact_gemm as X
+import gemm_exact_cases as CASES
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+@pytest.mark.parametrize("K,stride,pad,pool", [(1, 1, 0, False), (3, 1, 1, False), (3, 2, 1, False), (1, 2, 0, False),
+                                               (3, 1, 0, False), (1, 56, 0, False), (3, 2, 0, False), (1, 1, 0, True)])
+def test_conv_exact_equals_aten_float64(K, stride, pad, pool):
+    N, H, W, Cin, Cout = 2, 9, 113 if stride == 56 else 13, 24, 16
+    if pool:
+        H, W = 11, 15
+    x = torch.randn(N, H, W, Cin, generator=_g(1), dtype=torch.float64)
+    w = torch.randn(Cout, K, K, Cin, generator=_g(2), dtype=torch.float64)
+    xin = x.permute(0, 3, 1, 2)
+    ref = F.conv2d(F.avg_pool2d(xin, 2) if pool else xin, w.permute(0, 3, 1, 2), stride=1 if pool else stride, padding=pad)
+    ref = ref.permute(0, 2, 3, 1).reshape(-1, Cout)
+    got, absp = X.conv_exact(x, w, stride, pad, pool)
+    assert got.shape == ref.shape
+    assert (got - ref).abs().max() <= 1e-12 * ref.abs().max()
+    ref_abs = F.conv2d(F.avg_pool2d(xin.abs(), 2) if pool else xin.abs(), w.abs().permute(0, 3, 1, 2), stride=1 if pool else stride,
+                       padding=pad).permute(0, 2, 3, 1).reshape(-1, Cout)
+    if not pool:           # (|mean| <= mean|.|: the pooled absprod is the product of the pooled operand's magnitude)
+        assert (absp - ref_abs).abs().max() <= 1e-12 * ref_abs.abs().max()
+    rows = X.sample_rows(got.shape[0], tile=16)
+    g2, a2 = X.conv_exact(x, w, stride, pad, pool, rows=rows)
+    assert torch.equal(g2, got[rows]) and torch.equal(a2, absp[rows])
+
+
+def test_wgrad_and_gemm_exact_equal_aten_float64():
+    N, H, W, Cin, Cout = 2, 7, 9, 16, 8
+    x = torch.randn(N, H, W, Cin, generator=_g(3), dtype=torch.float64)
+    dy = torch.randn(N, H, W, Cout, generator=_g(4), dtype=torch.float64)
+    w = torch.zeros(Cout, Cin, 3, 3, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x.permute(0, 3, 1, 2), w, padding=1).backward(dy.permute(0, 3, 1, 2))
+    got, _ = X.wgrad_exact(x, dy, 3, 3, 1, 1, chunk=37)
+    assert (got - w.grad.permute(0, 2, 3, 1).reshape(Cout, 9, Cin)).abs().max() <= 1e-12 * w.grad.abs().max()
+    got1, _ = X.wgrad_exact(x, dy, 3, 3, 1, 1, taps=[(2, 0)])
+    assert (got1[:, 0] - got[:, 6]).abs().max() <= 1e-12 * got.abs().max()
+    a = torch.randn(3, 20, 16, generator=_g(5), dtype=torch.float64)
+    b = torch.randn(3, 12, 16, generator=_g(6), dtype=torch.float64)
+    assert torch.allclose(X.gemm_exact(a, b)[0], torch.bmm(a, b.transpose(1, 2)), rtol=0, atol=1e-12)
+    c = torch.randn(3, 20, 12, generator=_g(7), dtype=torch.float64)
+    assert torch.allclose(X.gemm_exact(c, a, transpose_a=True)[0], torch.bmm(c.transpose(1, 2), a), rtol=0, atol=1e-12)
+
+
+def test_round_bf16_is_round_to_nearest_even():
+    v = torch.randn(200000, generator=_g(8), dtype=torch.float64) * 37
+    r = X.round_bf16(v)
+    lo = X.truncate_bf16(v)
+    hi = lo + torch.sign(v) * X.ulp_bf16(lo)
+    d_lo, d_hi = (v - lo).abs(), (hi - v).abs()
+    assert bool(((r == lo) | (r == hi)).all())
+    assert bool(torch.where(d_lo < d_hi, r == lo, torch.ones_like(r, dtype=torch.bool)).all())
+    assert bool(torch.where(d_hi < d_lo, r == hi, torch.ones_like(r, dtype=torch.bool)).all())
+    # ties go to the even neighbour; a value just past a tie in float64 (but a tie once in f32) goes away from the tie
+    t = torch.tensor([257.0, 259.0, -257.0, 257.0 + 2 ** -30], dtype=torch.float64)
+    assert X.round_bf16(t).tolist() == [256.0, 260.0, -256.0, 258.0]
+
+
+def test_sample_rows_covers_tiles_edges_and_2gib_crossings():
+    M, rb = 3211264, 1024                      # 3.06 GiB of 1 KiB rows
+    r = X.sample_rows(M, rb)
+    assert int(r[0]) == 0 and int(r[-1]) == M - 1
+    assert torch.equal(torch.unique(r // 256), torch.arange((M + 255) // 256))
+    assert bool((torch.bincount(r // 256) >= 1).all())
+    assert (2 ** 31) // rb in r.tolist() and (2 ** 31) // rb - 1 in r.tolist()
+    r2 = X.sample_rows(1000, 6)                # ragged last tile: every row
+    assert set(range(768, 1000)) <= set(r2.tolist())
+
+
+def _case_fwd(M=600, K=1024, Cout=512, seed=11):
+    x = torch.randn(M, K, generator=_g(seed)).bfloat16()
+    w = (torch.randn(Cout, K, generator=_g(seed + 1)) * K ** -0.5).bfloat16()
+    exact, absp = X.conv_exact(x.view(1, 1, M, K), w.view(Cout, 1, 1, K))
+    return x, w, exact, absp
+
+
+def test_bound_accepts_an_f32_convolution_in_another_order():
+    """ATen's CPU f32 convolution of the same bf16 operands (blocked, its own summation order), rounded RNE to bf16 -- and its
+    f32 result as an f32 output: both inside the bound, no rounding bias"""
+    N, H, W, Cin, Cout = 4, 31, 37, 64, 96
+    x = torch.randn(N, H, W, Cin, generator=_g(21)).bfloat16()
+    w = (torch.randn(Cout, 3, 3, Cin, generator=_g(22)) * (9 * Cin) ** -0.5).bfloat16()
+    scale = torch.rand(Cout, generator=_g(23)) + 0.5
+    bias = torch.randn(Cout, generator=_g(24)) * 0.1
+    f32 = F.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1).reshape(-1, Cout)
+    acc, absp = X.conv_exact(x, w, 1, 1)
+    exact = X.epilogue_exact(acc, scale, bias)
+    got = (f32 * scale + bias).bfloat16()
+    ok, ratio, _ = X.check_bound(got, exact, absp, torch.bfloat16, scale, bias)
+    assert ok, ratio
+    ok32, ratio32, _ = X.check_bound(f32, acc, absp, torch.float32)
+    assert ok32, ratio32
+    rb, n = X.rounding_bias(got, exact, absp, scale)
+    assert n >= 100000 and abs(rb) <= 0.02, (rb, n)
+    print(f"\nf32 conv (other order) -> bf16: worst |err|/bound {ratio:.3f}, f32 output {ratio32:.3f}, rounding bias {rb:+.4f} over {n}")
+
+
+def _mutants():
+    """(name, got, exact, absprod, out dtype, epilogue operands for the bound, reference of the old criterion)"""
+    out = []
+    # 1. one 32-wide K chunk dropped in one 256x256 tile
+    x, w, acc, absp = _case_fwd()
+    xa, wa = x.double(), w.double()
+    drop = xa[256:512, 64:96] @ wa[256:512, 64:96].t()
+    mut = acc.clone()
+    mut[256:512, 256:512] -= drop
+    out.append(("k-chunk dropped in one 256x256 tile", X.round_bf16(mut), acc, absp, torch.bfloat16, {}, acc))
+    # 2. one 32-row chunk dropped from a weight-gradient reduction at M = 66 400 (f32 output)
+    M, Cin, Cout = 66400, 64, 64
+    xg = torch.randn(1, 1, M, Cin, generator=_g(31)).bfloat16()
+    dy = torch.randn(1, 1, M, Cout, generator=_g(32)).bfloat16()
+    dw, dabs = X.wgrad_exact(xg, dy, 1, 1)
+    dw, dabs = dw[:, 0], dabs[:, 0]
+    part = dy.view(M, Cout)[40000:40032].double().t() @ xg.view(M, Cin)[40000:40032].double()
+    out.append(("32-row chunk dropped from a wgrad reduction (M=66400)", (dw - part).float(), dw, dabs, torch.float32, {}, dw))
+    # 3. truncation instead of round-to-nearest-even on the store
+    out.append(("truncating bf16 store", X.truncate_bf16(acc), acc, absp, torch.bfloat16, {}, acc))
+    # 4. the bias omitted from one column tile
+    bias = torch.randn(512, generator=_g(41)) * 0.1
+    ex = X.epilogue_exact(acc, None, bias)
+    mut = ex.clone()
+    mut[:, 256:512] -= bias[256:512].double()
+    out.append(("bias omitted from one column tile", X.round_bf16(mut), ex, absp, torch.bfloat16, {"bias": bias}, ex))
+    # 5. the residual read from the neighbouring row in the last ragged tile (M = 600: rows 512..599)
+    res = torch.randn(600, 512, generator=_g(51)).bfloat16().double()
+    ex = X.epilogue_exact(acc, None, None, res)
+    mut = ex.clone()
+    mut[512:599] += res[513:600] - res[512:599]
+    out.append(("residual from the neighbouring row in the ragged tile", X.round_bf16(mut), ex, absp, torch.bfloat16, {"residual": res}, ex))
+    return out
+
+
+def test_negative_controls_are_rejected_and_the_old_criterion_misses_some(capsys):
+    lines = ["", "negative controls (each must be rejected by the exact-product bound):"]
+    missed_by_old = 0
+    for name, got, exact, absp, odt, epi, ref in _mutants():
+        ok, ratio, _ = X.check_bound(got, exact, absp, odt, **epi)
+        rb = X.rounding_bias(got, exact, absp)[0] if odt == torch.bfloat16 else 0.0
+        rejected = not ok or abs(rb) > 0.02
+        old_ok = X.old_criterion(got, ref)
+        lines.append(f"  {name:55s} old 2e-2*max: {'ACCEPTS' if old_ok else 'rejects'}   new bound: {'rejects' if rejected else 'ACCEPTS'}"
+              f"  (worst |err|/bound {ratio:.3g}, rounding bias {rb:+.3f})")
+        assert rejected, name
+        missed_by_old += old_ok
+    with capsys.disabled():                 # (the verdicts are the point of this test: shown without -s)
+        print("\n".join(lines))
+    assert missed_by_old >= 1
+
+
+def test_rounding_bias_separates_rne_from_truncation():
+    _, _, acc, absp = _case_fwd(M=400, seed=61)
+    rne, n = X.rounding_bias(X.round_bf16(acc), acc, absp)
+    tr, _ = X.rounding_bias(X.truncate_bf16(acc), acc, absp)
+    assert n >= 100000 and abs(rne) <= 0.02 and -0.55 < tr < -0.45, (rne, tr, n)
+
+
+# ------------------------------------------------------------------------------------------------ coverage of the recorded launches
+def test_case_table_covers_every_recorded_launch_class_in_both_tiers():
+    with open(os.path.join(GOLDEN, "bench_gemm_launches.json")) as fh:
+        rec = json.load(fh)["entries"]
+    have = {}
+    for c in CASES.CASES:
+        for tier in c["tiers"]:
+            have.setdefault(CASES.launch_class(c["entry"], c["kid"], c["geom"], c["epi"]), set()).add(tier)
+    missing = []
+    for e in rec:
+        cls = CASES.launch_class(e["entry"], e["kernel_id"], e["geometry"], e["epilogue"])
+        if have.get(cls, set()) != {"A", "B"}:        # (the batched classes carry their strides: see launch_class)
+            missing.append((cls, sorted(have.get(cls, ()))))
+    assert not missing, missing
+
+
+def test_case_table_covers_every_instantiation_and_bench_shape():
+    variants = {v for c in CASES.CASES for v in c.get("variants", ())}
+    assert not set(CASES.REQUIRED_VARIANTS) - variants, sorted(set(CASES.REQUIRED_VARIANTS) - variants)
+    full = {(c["kid"]) for c in CASES.CASES if "full_m" in c.get("variants", ())}
+    assert CASES.BENCH_KERNELS <= full, CASES.BENCH_KERNELS - full
+    with open(os.path.join(GOLDEN, "bench_gemm_launches.json")) as fh:
+        launched = {e["kernel_id"] for e in json.load(fh)["entries"]}
+    assert launched <= CASES.BENCH_KERNELS, launched - CASES.BENCH_KERNELS
+    for shape in CASES.BENCH_SHAPES:
+        assert any(CASES.mnk(c) == shape[1:] and c["kid"] == shape[0] and "full_m" in c["variants"] for c in CASES.CASES), shape
+    big = [c for c in CASES.CASES if "over_2gib" in c.get("variants", ())]
+    assert {c["kid"] for c in big} >= {1, 3, 5, 6, 9}
+    for c in CASES.CASES:          # every case says what it targets and where dispatch selects it
+        assert c.get("why"), c["id"]

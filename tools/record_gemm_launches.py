@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""Record every distinct GEMM / convolution launch of one bench-shaped bf16 training step (16 and 32 images of 800x1333, built like
+tools/shape_profile.py): a recording shim around ``hip.conv_fwd``, ``hip.conv_wgrad``, ``hip.gemm_nt_batched`` and
+``hip.gemm_tn_batched`` notes each call's entry point, full geometry, epilogue flags and the kernel the library picked
+(``cddmsl_last_kernel``).  Writes tests/golden/bench_gemm_launches.json, which tests/test_gpu_gemm_exact.py replays in plan-only mode
+(dispatch still picks the recorded kernel) and tests/test_exact_bound_host.py checks against the exact-product case table.
+A change of dispatch or of the step's shapes must re-record it.  usage: python tools/record_gemm_launches.py [--batches 16 32] [--out F]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+OUT = os.path.join(ROOT, "tests", "golden", "bench_gemm_launches.json")
+
+
+def _dt(t):
+    return {torch.bfloat16: "bf16", torch.float32: "f32"}[t.dtype]
+
+
+class Recorder:
+    def __init__(self, hip):
+        self.hip, self.on, self.calls, self.batch = hip, False, {}, 0
+        self.orig = {n: getattr(hip, n) for n in ("conv_fwd", "conv_wgrad", "gemm_nt_batched", "gemm_tn_batched")}
+        for n in self.orig:
+            setattr(hip, n, self._wrap(n))
+
+    def restore(self):
+        for n, f in self.orig.items():
+            setattr(self.hip, n, f)
+
+    def _note(self, entry, geom, flags, nbytes):
+        kid = int(self.hip._L().cddmsl_last_kernel())
+        key = json.dumps([self.batch, entry, geom, flags, kid], sort_keys=True)
+        d = self.calls.setdefault(key, {"images": self.batch, "entry": entry, "geometry": geom, "epilogue": flags, "kernel_id": kid,
+                                        "kernel": self.hip._CONV_KERNEL.get(kid, "?"), "launches": 0, "max_operand_bytes": 0})
+        d["launches"] += 1
+        d["max_operand_bytes"] = max(d["max_operand_bytes"], int(nbytes))
+
+    def _wrap(self, name):
+        f = self.orig[name]
+        rec = self
+
+        def conv_fwd(x, w, scale=None, bias=None, residual=None, relu=False, relu_mask=None, stride=1, pad=0, pool=False,
+                     out_f32=False, residual_pooled=False, emit8=None, out_spec=None):
+            y = f(x, w, scale, bias, residual, relu, relu_mask, stride, pad, pool, out_f32, residual_pooled, emit8, out_spec)
+            if rec.on:
+                N, H, W, Cin = x.shape
+                Cout, KH, KW, _ = w.shape
+                res = None if residual is None else ("pooled" if residual_pooled else _dt(residual))
+                rec._note("conv_fwd", dict(N=N, H=H, W=W, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, pool=bool(pool),
+                                           ldy=Cout, dtype=_dt(x)),
+                          dict(scale=scale is not None, bias=bias is not None, residual=res, relu=bool(relu),
+                               relu_mask=relu_mask is not None, out_f32=bool(out_f32), emit8=emit8 is not None),
+                          max(x.numel() * x.element_size(), y.numel() * y.element_size()))
+            return y
+
+        def conv_wgrad(x, dy, w_shape, scale=None, stride=1, pad=0, pool=False, out=None):
+            r = f(x, dy, w_shape, scale, stride, pad, pool, out)
+            if rec.on:
+                N, H, W, Cin = x.shape
+                Cout, KH, KW, _ = w_shape
+                rec._note("conv_wgrad", dict(N=N, H=H, W=W, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, pool=bool(pool),
+                                             ldd=Cout, dtype=_dt(x)),
+                          dict(scale=scale is not None, accumulate=out is not None),
+                          max(x.numel() * x.element_size(), dy.numel() * dy.element_size()))
+            return r
+
+        def gemm_nt_batched(a, w, c, M, N, K, lda, ldb, ldc, batch, sa, sw, sc, a_off=0, w_off=0, c_off=0, bias=None):
+            r = f(a, w, c, M, N, K, lda, ldb, ldc, batch, sa, sw, sc, a_off, w_off, c_off, bias)
+            if rec.on:
+                rec._note("gemm_nt_batched", dict(M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, batch=batch, sa=sa, sw=sw, sc=sc, dtype=_dt(a)),
+                          dict(bias=bias is not None, out_f32=c.dtype == torch.float32 and a.dtype != torch.float32),
+                          max(a.numel() * a.element_size(), c.numel() * c.element_size()))
+            return r
+
+        def gemm_tn_batched(a, b, out, M, N, K, lda, ldb, ldo, batch, sa, sb, so, a_off=0, b_off=0, o_off=0, accumulate=False):
+            r = f(a, b, out, M, N, K, lda, ldb, ldo, batch, sa, sb, so, a_off, b_off, o_off, accumulate)
+            if rec.on:
+                rec._note("gemm_tn_batched", dict(M=M, N=N, K=K, lda=lda, ldb=ldb, ldo=ldo, batch=batch, sa=sa, sb=sb, so=so, dtype=_dt(a)),
+                          dict(accumulate=bool(accumulate), out=_dt(out)),
+                          max(a.numel() * a.element_size(), b.numel() * b.element_size()))
+            return r
+
+        return locals()[name]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[16, 32])
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--out", default=OUT)
+    args = ap.parse_args()
+    import bench
+    from cddmsl_amd import engine, hip, synthetic
+    rec = Recorder(hip)
+    for batch in args.batches:
+        cfg = bench.make_cfg(args.dtype)
+        cfg.MODEL.DEVICE = "cuda:0"
+        tr = engine.build_trainer(cfg, batch, 800, 1333)
+        tr.model.load_state_dict(synthetic.make_state_dict(0), strict=False)
+        tr.clipcap_model.load_state_dict(synthetic.make_mapper_state_dict(1))
+        tr.iter, tr.metrics_period = 20000, 0
+        tr.run_step()                      # (first step: lazy weight copies and buffers)
+        torch.cuda.synchronize()
+        rec.batch, rec.on = batch, True
+        tr.run_step()
+        torch.cuda.synchronize()
+        rec.on = False
+        del tr
+        torch.cuda.empty_cache()
+    rec.restore()
+    entries = sorted(rec.calls.values(), key=lambda d: (d["images"], d["entry"], d["kernel_id"], json.dumps(d["geometry"], sort_keys=True),
+                                                        json.dumps(d["epilogue"], sort_keys=True)))
+    doc = {"about": "distinct GEMM / convolution launches of one bench-shaped training step (tools/record_gemm_launches.py)",
+           "dtype": args.dtype, "images": args.batches, "entries": entries}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(doc, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(f"{len(entries)} distinct launches -> {args.out}")
+    for d in entries:
+        print(d["images"], d["entry"], d["kernel"], d["launches"], d["geometry"], d["epilogue"])
+
+
+if __name__ == "__main__":
+    main()
