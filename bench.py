@@ -2,6 +2,7 @@
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched under torch.distributed.run, one rank per GPU)
   python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed, DIR/<name>.npy)
+  python bench.py ... --full                           (also the figures and checks that take work of their own, below)
 
 Workload (config.workload): configs[1] of BASELINE.json -- VOC(labeled)+Clipart(unlabeled) CLIP RN50-C4 Faster R-CNN +
 caption consistency, 16 images/GPU of 800x1333, bf16 MFMA, iteration > 10000 so all three branches of
@@ -9,10 +10,13 @@ caption consistency, 16 images/GPU of 800x1333, bf16 MFMA, iteration > 10000 so 
 all-reduce, per-parameter clip + SGD).  Synthetic inputs and seeded random weights (no datasets/checkpoints offline);
 inputs are resident in HBM before the timed region.
 
-One JSON line on rank 0 with ``roofline`` (dominant kernel = the bf16 implicit-GEMM conv; achieved = algorithmic
-2*M*N*K FLOPs of its launches / their HIP-event durations, measured live over the timed steps on the launch stream)
-and ``cpu_baseline`` (the oracle = PyTorch-CPU restatement of the same step, a bounded sample timed on this box's
-host cores, rank 0 / N=1 only).
+A plain run sets up, warms up, times the K steps, writes the --dump-outputs arrays and prints one JSON line on rank 0.  The
+line carries ``roofline`` (dominant kernel = the bf16 implicit-GEMM conv; achieved = algorithmic 2*M*N*K FLOPs of its
+launches / their HIP-event durations, measured live in the last timed step on the launch stream) and the per-kernel table of
+the last warm-up step; both come from steps the run takes anyway.  ``--full`` adds what needs runs of its own (N=1 only):
+``forward_roofline`` (a forward-only loop after the timed steps), ``cpu_baseline`` (the oracle = PyTorch-CPU restatement of the
+same step, a bounded sample timed on this box's host cores), ``losses_gate`` (the first step's losses against the committed
+fixture; a mismatch exits non-zero) and, with --warmup 0, one instrumented step for the per-kernel table.
 """
 import argparse
 import json
@@ -46,6 +50,16 @@ def cpu_model_name():
     except OSError:
         pass
     return "unknown CPU"
+
+
+def host_cpus(env=os.environ):
+    """Host threads the CPU baseline may use: the CPUs this process may run on, no more than OMP_NUM_THREADS when that is set,
+    at most 64."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 8)
+    omp = env.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(min(n, 64), 1)
 
 
 def cpu_baseline(height, width, threads, batch=2, timed=3, budget_s=150.0):
@@ -179,7 +193,7 @@ def launch_plan(gpus, argv, env, device_count):
     return "spawn", cmd
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -190,15 +204,40 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "fp8"],
                     help="fp8 = BASELINE.json configs[4]: e4m3 forward GEMMs (MFMA-bound convs of layer3/4, RoI layer4, RPN; region x text "
                          "contraction), bf16 elsewhere and in backward; use with --batch 32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-forward-roofline", action="store_true", help="skip the extra forward-only loop (profiling runs: keeps the kernel mix = the timed steps)")
-    ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--cpu-baseline-steps", type=int, default=3, help="timed oracle steps (median reported), after one warm-up")
+    ap.add_argument("--full", action="store_true", help="also what takes work of its own (N=1): the forward-only roofline, the CPU "
+                    "baseline, the first-step losses gate and, with --warmup 0, an instrumented step for the per-kernel table")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-forward-roofline", action="store_true", help="with --full: skip the extra forward-only loop (profiling runs: "
+                    "keeps the kernel mix = the timed steps)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="with --full: host threads of the CPU baseline (0: host_cpus())")
+    ap.add_argument("--cpu-baseline-steps", type=int, default=3, help="with --full: timed oracle steps (median reported), after one warm-up")
     ap.add_argument("--dry-run", action="store_true", help="launcher rehearsal: start the ranks, form the process group (gloo when "
                     "no GPU is visible), barrier, print the rank layout; no model, no timing")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
                     "(rank 0): its losses, and a fixed, seeded sample of the updated parameters and of their gradients; the last "
                     "timed step starts from the seeded state, so the arrays depend on the arguments alone")
+    return ap
+
+
+def extra_legs(args, world):
+    """What a run does besides setting up, warming up, timing the steps, dumping their outputs and printing its line: nothing
+    unless --full.  Pure function of the arguments (tests/test_dist_cpu.py)."""
+    if not args.full:
+        return frozenset()
+    legs = set()
+    if args.warmup == 0:
+        legs.add("kernel_table_step")                  # no warm-up step to instrument: one more step after the timed region
+    if world == 1:
+        legs.add("losses_gate")
+        if (args.height, args.width) == (800, 1333) and not args.no_forward_roofline:
+            legs.add("forward_roofline")
+        if not args.no_cpu_baseline:
+            legs.add("cpu_baseline")
+    return frozenset(legs)
+
+
+def main():
+    ap = make_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -212,6 +251,7 @@ def main():
     rank, world = engine.init_distributed()
     if world != max(args.gpus, 1):
         raise SystemExit(f"bench.py: process group has {world} ranks but --gpus {args.gpus}")
+    legs = extra_legs(args, world)
     if args.dry_run:
         ranks = [None] * world
         if world > 1:
@@ -295,15 +335,15 @@ def main():
         dumped = step_outputs(last, tr.buckets.params)
         for name, arr in dumped.items():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
-    if full is None:                                   # --warmup 0: the instrumented step runs after the timed region
+    if "kernel_table_step" in legs:                    # --warmup 0: the instrumented step runs after the timed region
         hip.PROFILE.enable()
         tr.run_step()
         full = hip.PROFILE.collect()
-    # RN50-C4 supervised FORWARD alone (backbone to res4, RPN, RoIAlign, RoI layer4, attention pool, classifier, losses), the
+    # --full: RN50-C4 supervised FORWARD alone (backbone to res4, RPN, RoIAlign, RoI layer4, attention pool, classifier, losses), the
     # quantity BASELINE.json's roofline target is stated on: algorithmic 1.878 TFLOP per 800x1333 image (SURVEY.md 8(d):
     # 938.8 GMAC, query-0-only attention pool), timed outside the step timing above, rank 0's own clock
     fwd_ms = fwd_kernels = fwd_shapes = None
-    if world == 1 and (args.height, args.width) == (800, 1333) and not args.no_forward_roofline:
+    if "forward_roofline" in legs:
         data = next(tr._data_loader_iter)
         tr.model.share_source_pass = False
         for _ in range(2):
@@ -328,12 +368,12 @@ def main():
         dist.all_gather_object(dl, torch.cuda.current_device())
         devs = dl
     losses = {k: float(v.detach()) for k, v in last.items()}
-    # Outside the timed region: the FIRST step's losses (seeded weights, seeded batch, seeded samplers) against the fixture that
+    # --full, outside the timed region: the FIRST step's losses (seeded weights, seeded batch, seeded samplers) against the fixture that
     # tests/test_gpu_bench_gate.py ties to the exact-f32 step at these very launch shapes -- the bench is timing the gated computation.
     gate = None
     fpath = os.path.join(ROOT, "tests", "golden", "bench_step0_losses.json")
     fkey = f"{args.dtype}_b{args.batch}_{args.height}x{args.width}"
-    if world == 1 and os.path.exists(fpath):
+    if "losses_gate" in legs and os.path.exists(fpath):
         fx = json.load(open(fpath)).get(fkey)
         if fx is not None:
             s0 = {k: float(v.detach()) for k, v in step0.items()}
@@ -388,9 +428,11 @@ def main():
                          "launches_per_step": dom["launches"] / prof_steps,
                          "kernel_ms_per_step": dom["ms"] / prof_steps,
                          "measured_on": "HIP events around every launch of this kernel in the last timed step"},
-            "kernels_ms_per_step": {k: round(v["ms"], 3) for k, v in full.items()},
-            "kernels_ms_note": "one fully instrumented untimed step (event pairs on every launch: that step runs ~5 % slower)",
-            "kernels_tflops": {k: round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) for k, v in full.items() if v["ms"] > 0 and v["flops"] > 0},
+            "kernels_ms_per_step": None if full is None else {k: round(v["ms"], 3) for k, v in full.items()},
+            "kernels_ms_note": "one fully instrumented untimed step (event pairs on every launch: that step runs ~5 % slower)"
+                               if full is not None else "--warmup 0: no warm-up step to instrument (--full adds one after the timed steps)",
+            "kernels_tflops": None if full is None else {k: round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 1) for k, v in full.items()
+                                                         if v["ms"] > 0 and v["flops"] > 0},
             "losses": losses,
             "losses_gate": gate,
         }
@@ -403,8 +445,8 @@ def main():
                                        "frac": ftf / (fwd_ms * 1e-3) / peak, "images_per_sec_forward": args.batch / (fwd_ms * 1e-3),
                                        "kernels_ms": {k: round(v["ms"], 3) for k, v in fwd_kernels.items()},
                                        "kernels_ms_note": "one instrumented forward (event pairs on every launch); the ms above is un-instrumented"}
-        if world == 1 and not args.no_cpu_baseline:
-            threads = args.cpu_threads or min(os.cpu_count() or 8, 64)
+        if "cpu_baseline" in legs:
+            threads = args.cpu_threads or host_cpus()
             out["cpu_baseline"] = cpu_baseline(args.height, args.width, threads, timed=max(args.cpu_baseline_steps, 1))
         print(json.dumps(out))
         if gate is not None and not gate["ok"]:

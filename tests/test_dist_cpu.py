@@ -92,6 +92,24 @@ def test_bench_launch_plan():
     assert "needs 2 visible GPUs" in str(e.value)
 
 
+def test_bench_plain_run_does_nothing_extra():
+    """A plain bench run only sets up, warms up, times its steps and dumps; the forward-only loop, the CPU baseline, the losses gate
+    and the --warmup 0 instrumented step run under --full alone, and the --no-* switches still remove theirs there."""
+    b = _bench()
+    ap = b.make_parser()
+    for argv in ([], ["--steps", "3", "--warmup", "0"], ["--dump-outputs", "d"], ["--dtype", "fp8", "--batch", "32"]):
+        for world in (1, 2):
+            assert b.extra_legs(ap.parse_args(argv), world) == frozenset(), (argv, world)
+    full = ap.parse_args(["--full"])
+    assert b.extra_legs(full, 1) == {"losses_gate", "forward_roofline", "cpu_baseline"}
+    assert b.extra_legs(full, 2) == frozenset()
+    assert b.extra_legs(ap.parse_args(["--full", "--warmup", "0"]), 2) == {"kernel_table_step"}
+    assert b.extra_legs(ap.parse_args(["--full", "--no-cpu-baseline", "--no-forward-roofline"]), 1) == {"losses_gate"}
+    assert b.extra_legs(ap.parse_args(["--full", "--height", "512", "--width", "512"]), 1) == {"losses_gate", "cpu_baseline"}
+    n = b.host_cpus({})
+    assert 1 <= n <= 64 and b.host_cpus({"OMP_NUM_THREADS": "3"}) == min(n, 3) and b.host_cpus({"OMP_NUM_THREADS": "x"}) == n
+
+
 def test_bench_step_outputs_sample_is_fixed():
     """bench.py --dump-outputs: losses as float64, parameters and gradients (logical row-major order, channels_last included) as
     float32 at the same seeded positions on every call; a parameter set no larger than the sample is written whole."""

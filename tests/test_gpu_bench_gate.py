@@ -9,7 +9,7 @@ Here the trainer is built exactly as bench.py builds it (same config, seeds, syn
   2. the bf16 step -- production dispatch -- runs with those proposals forced in (which teacher-forces every index stage) and
      must stay inside the bf16 bounds of test_gpu_e2e.py on every loss and every gradient tensor;
   3. the bf16 step on its own proposals is what bench.py's first step computes: its losses are compared with the committed
-     fixture tests/golden/bench_step0_losses.json, which bench.py checks its own first step against as well
+     fixture tests/golden/bench_step0_losses.json, which bench.py --full checks its own first step against as well
      (``losses_gate`` in the bench line) -- so the number the bench prints belongs to the computation gated here;
   4. the same at 32 images per GPU for the fp8 configuration against bf16 (BASELINE.json configs[4]).
 """
