@@ -86,6 +86,10 @@ def _L():
         L.cddmsl_contrastive_fwd.argtypes = [vp] * 4 + [ci, ci, vp]
         L.cddmsl_contrastive_bwd.argtypes = [vp] * 5 + [ci, ci, vp]
         L.cddmsl_instance_boxes.argtypes = [vp] + [ci] * 4 + [vp, ci, vp, vp, vp, vp]
+        L.cddmsl_text_embed.argtypes = [vp] * 4 + [c_long, ci, ci, ci, ci, vp]
+        L.cddmsl_attn_causal_fwd.argtypes = [vp, vp] + [ci] * 6 + [cf, ci, vp]
+        L.cddmsl_quick_gelu.argtypes = [vp, c_long, ci, vp]
+        L.cddmsl_text_pool.argtypes = [vp] * 5 + [c_long, ci, ci, ci, cf, ci, vp]
         _sigs_done = True
     return L
 
@@ -1167,6 +1171,56 @@ def attn_small_bwd_qkv(qkv, do, t, heads, scale):
                                      c_void_p(gbase + d * 2), c_void_p(gbase + 4 * d), R // t, t, heads, d // heads, 3 * d, 3 * d, 3 * d, d,
                                      float(scale), 0, stream_ptr()), "cddmsl_attn_small_bwd")
     return dqkv
+
+
+@_timed("text_embed")
+def text_embed(ids, tok, pos):
+    """ids [n, t] int64 (contiguous, every id in [0, vocab)), tok [vocab, W] bf16 / f32, pos [>= t, W] f32 -> x [n*t, W] f32 =
+    tok[ids] + pos[position]"""
+    require_cuda(ids, tok, pos)
+    assert ids.dim() == 2 and ids.dtype == torch.int64 and ids.is_contiguous() and tok.is_contiguous() and pos.is_contiguous()
+    assert pos.dtype == torch.float32 and tok.shape[1] == pos.shape[1] and pos.shape[0] >= ids.shape[1]
+    n, t = ids.shape
+    W = tok.shape[1]
+    x = torch.empty((n * t, W), device=ids.device, dtype=torch.float32)
+    check(_L().cddmsl_text_embed(ptr(ids), ptr(tok), ptr(pos), ptr(x), n * t, t, W, tok.shape[0], DT[tok.dtype], stream_ptr()),
+          "cddmsl_text_embed")
+    return x
+
+
+@_timed("attn_causal")
+def attn_causal_fwd(qkv, t, heads, scale):
+    """qkv [n*t, 3W] bf16 (queries | keys | values, the in-projection's output) -> o [n*t, W] bf16, causal (keys j <= query i)"""
+    require_cuda(qkv)
+    assert qkv.dim() == 2 and qkv.is_contiguous() and qkv.dtype == torch.bfloat16 and qkv.shape[1] % 3 == 0 and qkv.shape[0] % t == 0
+    R, W = qkv.shape[0], qkv.shape[1] // 3
+    o = torch.empty((R, W), device=qkv.device, dtype=qkv.dtype)
+    check(_L().cddmsl_attn_causal_fwd(ptr(qkv), ptr(o), R // t, t, heads, W // heads, 3 * W, W, float(scale), 0, stream_ptr()),
+          "cddmsl_attn_causal_fwd")
+    return o
+
+
+@_timed("quick_gelu")
+def quick_gelu_(x):
+    """x * sigmoid(1.702 x) in place (bf16 or f32, contiguous); returns x"""
+    require_cuda(x)
+    assert x.is_contiguous()
+    check(_L().cddmsl_quick_gelu(ptr(x), x.numel(), DT[x.dtype], stream_ptr()), "cddmsl_quick_gelu")
+    return x
+
+
+@_timed("text_pool")
+def text_pool(x, rows, gamma, beta, group=1, out_dtype=torch.float32, eps=1e-5):
+    """x [R, W] f32, rows [nout * group] int64 (row indices into x) -> [nout, W] out_dtype: the mean over each group of ``group``
+    consecutive entries of rows of LayerNorm(x[row]) (gamma, beta)"""
+    require_cuda(x, rows, gamma, beta)
+    assert x.dtype == torch.float32 and x.is_contiguous() and rows.dtype == torch.int64 and rows.is_contiguous()
+    assert rows.numel() % group == 0 and gamma.numel() == beta.numel() == x.shape[1]
+    nout = rows.numel() // group
+    y = torch.empty((nout, x.shape[1]), device=x.device, dtype=out_dtype)
+    check(_L().cddmsl_text_pool(ptr(x), ptr(rows), ptr(gamma), ptr(beta), ptr(y), x.shape[0], nout, group, x.shape[1], eps,
+                                DT[out_dtype], stream_ptr()), "cddmsl_text_pool")
+    return y
 
 
 @_timed("attn_small")

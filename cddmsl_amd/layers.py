@@ -1274,3 +1274,27 @@ class SmallAttnQkvFn(torch.autograd.Function):
 
 def small_attention_qkv(qkv, t, heads, scale):
     return SmallAttnQkvFn.apply(qkv, t, heads, scale)
+
+
+# ------------------------------------------------------------------------------------------------
+# CLIP text encoder (modeling/text_encoder.py): frozen, forward only -- the reference never differentiates through it
+# (clip_rcnn.py:438-439), so these are plain calls, no autograd nodes.
+# ------------------------------------------------------------------------------------------------
+def text_embed(ids, tok, pos):
+    """ids [n, t] int64 -> [n*t, W] f32 = token embedding + positional embedding"""
+    return hip.text_embed(ids.contiguous(), tok, pos)
+
+
+def causal_attention(qkv, t, heads, scale):
+    """qkv [n*t, 3W] bf16 (one in-projection GEMM's output) -> [n*t, W] bf16, keys j <= query i"""
+    return hip.attn_causal_fwd(qkv.contiguous(), t, heads, scale)
+
+
+def quick_gelu_(x):
+    """x * sigmoid(1.702 x) in place"""
+    return hip.quick_gelu_(x)
+
+
+def text_pool(x2d, rows, gamma, beta, group=1, out_dtype=torch.float32):
+    """ln_final of the rows ``rows`` of the residual stream, averaged over groups of ``group`` consecutive entries"""
+    return hip.text_pool(x2d.contiguous(), rows.contiguous(), gamma.detach(), beta.detach(), group, out_dtype)

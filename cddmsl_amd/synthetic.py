@@ -188,3 +188,35 @@ def make_batch(batch_size, height=800, width=1333, rank=0, iteration=0, num_gt=3
                     "instances": {"gt_boxes": boxes.float(), "gt_classes": classes.long(),
                                   "image_size": (height, width)}})
     return out
+
+
+def make_text_state_dict(seed=0, width=512, layers=12, embed_dim=1024, vocab_size=49408, context_length=77) -> Dict[str, torch.Tensor]:
+    """CLIP text encoder (``CLIPLangEncoder``) state dict with the reference's names, no prefix.  Weights use the reference's init
+    stds (clip_backbone.py:770-784); the biases and LayerNorm affines, which that init leaves at 0 / 1, are drawn non-trivial so
+    that every epilogue term is exercised."""
+    g = torch.Generator().manual_seed(seed)
+    proj_std = width ** -0.5 * (2 * layers) ** -0.5
+    attn_std, fc_std = width ** -0.5, (2 * width) ** -0.5
+    sd: Dict[str, torch.Tensor] = {}
+    sd["token_embedding.weight"] = torch.randn(vocab_size, width, generator=g) * 0.02
+    sd["positional_embedding"] = torch.randn(context_length, width, generator=g) * 0.01
+
+    def ln(p, c):
+        sd[p + ".weight"] = 1.0 + 0.1 * torch.randn(c, generator=g)
+        sd[p + ".bias"] = 0.1 * torch.randn(c, generator=g)
+
+    for i in range(layers):
+        q = f"transformer.resblocks.{i}"
+        sd[q + ".attn.in_proj_weight"] = torch.randn(3 * width, width, generator=g) * attn_std
+        sd[q + ".attn.in_proj_bias"] = 0.02 * torch.randn(3 * width, generator=g)
+        sd[q + ".attn.out_proj.weight"] = torch.randn(width, width, generator=g) * proj_std
+        sd[q + ".attn.out_proj.bias"] = 0.02 * torch.randn(width, generator=g)
+        ln(q + ".ln_1", width)
+        sd[q + ".mlp.c_fc.weight"] = torch.randn(4 * width, width, generator=g) * fc_std
+        sd[q + ".mlp.c_fc.bias"] = 0.02 * torch.randn(4 * width, generator=g)
+        sd[q + ".mlp.c_proj.weight"] = torch.randn(width, 4 * width, generator=g) * proj_std
+        sd[q + ".mlp.c_proj.bias"] = 0.02 * torch.randn(width, generator=g)
+        ln(q + ".ln_2", width)
+    ln("ln_final", width)
+    sd["text_projection"] = torch.randn(width, embed_dim, generator=g) * width ** -0.5
+    return sd

@@ -210,6 +210,24 @@ int cddmsl_attn_last_fwd(const void* q, const void* kv, void* o, float* p, int n
 int cddmsl_attn_last_bwd(const void* q, const void* kv, const void* dout, const float* p, void* dq, void* dkv, int n, int t, int heads,
                          int dh, int ldq, int ldkv, int voff, int ldo, float scale, int dtype, void* stream);
 
+/* ---- CLIP text encoder (modeling/backbone/clip_backbone.py:273-317,732-877; forward only, the encoder is frozen).  The linears
+ * run on cddmsl_conv_fwd (1x1 over n*t rows) and the per-layer LayerNorms on cddmsl_layernorm_fwd; these four cover the rest.
+ * text_embed:  x [rows][W] f32 = tok[ids[r]] + pos[r % t]; ids [rows] int64 in [0, vocab), tok [vocab][W] in `dtype`, pos [>= t][W] f32;
+ *              W % 8 == 0, tok / pos / x 16-byte aligned.
+ * attn_causal_fwd: qkv [nseq*t][ldqkv] bf16 = the in-projection as it comes (q | k | v column blocks of W = heads*dh, head h at
+ *              column h*dh of its block, nn.MultiheadAttention order) -> o [nseq*t][ldo] bf16 = softmax(q k^T * scale + mask) v per
+ *              (sequence, head), the mask keeping keys j <= query i.  bf16 only (dtype 0), dh == 64, t <= 128, ld % 8 == 0.
+ * quick_gelu:  x = x * sigmoid(1.702 x) in place, numel % 8 == 0 (bf16) / % 4 == 0 (f32), 16-byte aligned.
+ * text_pool:   y [nout][W] (`dtype`) row r = (1/group) sum_{p < group} LayerNorm(x[rows[r*group + p]]) with gamma / beta, eps;
+ *              x [R][W] f32, rows int64 in [0, R), W % 64 == 0, W <= 1024. */
+int cddmsl_text_embed(const long* ids, const void* tok, const float* pos, float* x, long rows, int t, int W, int vocab, int dtype,
+                      void* stream);
+int cddmsl_attn_causal_fwd(const void* qkv, void* o, int nseq, int t, int heads, int dh, int ldqkv, int ldo, float scale, int dtype,
+                           void* stream);
+int cddmsl_quick_gelu(void* x, long numel, int dtype, void* stream);
+int cddmsl_text_pool(const float* x, const long* rows, const float* gamma, const float* beta, void* y, long R, int nout, int group,
+                     int W, float eps, int dtype, void* stream);
+
 /* ---- fp32 heads: cosine-logit classifier (modeling/roi_heads/fast_rcnn.py:546-572) and the contrastive loss over
  * the cosine-similarity matrix (modeling/meta_arch/rcnn.py:308-317,458-468) ------------------------------------ */
 int cddmsl_l2norm_fwd(const float* x, float* y, float* inv, long R, int D, float eps, void* stream);
