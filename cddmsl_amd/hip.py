@@ -90,6 +90,13 @@ def _L():
         L.cddmsl_attn_causal_fwd.argtypes = [vp, vp] + [ci] * 6 + [cf, ci, vp]
         L.cddmsl_quick_gelu.argtypes = [vp, c_long, ci, vp]
         L.cddmsl_text_pool.argtypes = [vp] * 5 + [c_long, ci, ci, ci, cf, ci, vp]
+        L.cddmsl_skinny_gemm_workspace.argtypes = [ci] * 3
+        L.cddmsl_skinny_gemm.argtypes = [vp] * 6 + [c_long] + [ci] * 4 + [vp]
+        L.cddmsl_lm_head_workspace.argtypes = [ci, ci]
+        L.cddmsl_lm_head_argmax.argtypes = [vp, vp, vp, ci, vp, vp, c_long, ci, ci, ci, vp]
+        L.cddmsl_decode_attn.argtypes = [vp] * 4 + [ci] * 6 + [cf, ci, vp]
+        L.cddmsl_pos_embed.argtypes = [vp, ci] + [vp] * 4 + [c_long] + [ci] * 6 + [vp]
+        L.cddmsl_gelu_new.argtypes = [vp, c_long, ci, vp]
         _sigs_done = True
     return L
 
@@ -1221,6 +1228,112 @@ def text_pool(x, rows, gamma, beta, group=1, out_dtype=torch.float32, eps=1e-5):
     check(_L().cddmsl_text_pool(ptr(x), ptr(rows), ptr(gamma), ptr(beta), ptr(y), x.shape[0], nout, group, x.shape[1], eps,
                                 DT[out_dtype], stream_ptr()), "cddmsl_text_pool")
     return y
+
+
+# ---- GPT-2 decoder (modeling/gpt2.py) ----------------------------------------------------------------------------------------
+_GPT2_WS = {}
+
+
+def gpt2_workspace(device, nbytes):
+    """a scratch buffer of at least ``nbytes`` for the skinny GEMM's split-K slabs and the LM head's per-tile partials, one per
+    device, grown on demand (the decode step's launches run in order on one stream, so they can share it)"""
+    key = torch.device(device).index or 0
+    ws = _GPT2_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
+        _GPT2_WS[key] = ws
+    return ws
+
+
+def skinny_gemm_workspace(M, N, K):
+    return int(_L().cddmsl_skinny_gemm_workspace(M, N, K))
+
+
+@_timed("skinny_gemm")
+def skinny_gemm(x, w, bias=None, residual=None, epi=0, out=None):
+    """x [M, K] bf16 (M <= 64) @ w [N, K]^T bf16 + bias f32 -> y: epi 0 bf16, 1 f32 (+ residual f32), 2 gelu_new -> bf16.
+    ``out`` may be ``residual`` (in place)."""
+    require_cuda(x, w, bias, residual, out)
+    assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.is_contiguous() and w.is_contiguous() and x.dim() == 2
+    M, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K
+    for v in (bias,):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == N)
+    assert residual is None or (epi == 1 and residual.dtype == torch.float32 and residual.is_contiguous() and residual.shape == (M, N))
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32 if epi == 1 else torch.bfloat16)
+    nb = skinny_gemm_workspace(M, N, K)
+    check(0 if nb >= 0 else 1, "cddmsl_skinny_gemm_workspace")
+    ws = gpt2_workspace(x.device, nb)
+    check(_L().cddmsl_skinny_gemm(ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), ptr(ws), ws.numel(), M, N, K, epi, stream_ptr()),
+          "cddmsl_skinny_gemm")
+    return out
+
+
+@_timed("lm_head_argmax")
+def lm_head_argmax(h, wte, ids=None, logits=False):
+    """h [M, K] bf16 (M <= 64), wte [V, K] bf16 -> ids [M] int64 = argmax over v of h @ wte^T (lowest index on ties);
+    ``ids`` may be a strided int64 column view to write into.  ``logits``: also return the f32 logits [M, V]."""
+    require_cuda(h, wte, ids)
+    assert h.dtype == torch.bfloat16 and wte.dtype == torch.bfloat16 and h.is_contiguous() and wte.is_contiguous()
+    M, K = h.shape
+    V = wte.shape[0]
+    assert wte.shape[1] == K
+    if ids is None:
+        ids = torch.empty(M, device=h.device, dtype=torch.int64)
+    assert ids.dtype == torch.int64 and ids.dim() == 1 and ids.numel() == M
+    lg = torch.empty((M, V), device=h.device, dtype=torch.float32) if logits else None
+    nb = int(_L().cddmsl_lm_head_workspace(M, V))
+    check(0 if nb >= 0 else 1, "cddmsl_lm_head_workspace")
+    ws = gpt2_workspace(h.device, nb)
+    check(_L().cddmsl_lm_head_argmax(ptr(h), ptr(wte), ptr(ids), ids.stride(0), ptr(lg), ptr(ws), ws.numel(), M, V, K, stream_ptr()),
+          "cddmsl_lm_head_argmax")
+    return (ids, lg) if logits else ids
+
+
+@_timed("decode_attn")
+def decode_attn(qkv, kc, vc, L, heads, scale, out=None):
+    """qkv [n, >= 3W] bf16 (this step's c_attn output), kc / vc [n, Lmax, W] bf16 caches holding positions 0..L-2 -> o [n, W] bf16;
+    writes this step's keys / values to position L - 1 of the caches"""
+    require_cuda(qkv, kc, vc, out)
+    n, Lmax, W = kc.shape
+    assert qkv.dtype == kc.dtype == vc.dtype == torch.bfloat16 and kc.is_contiguous() and vc.is_contiguous() and vc.shape == kc.shape
+    assert qkv.dim() == 2 and qkv.shape[0] == n and qkv.stride(1) == 1 and qkv.shape[1] >= 3 * W and W == heads * 64
+    if out is None:
+        out = torch.empty((n, W), device=qkv.device, dtype=torch.bfloat16)
+    check(_L().cddmsl_decode_attn(ptr(qkv), ptr(kc), ptr(vc), ptr(out), n, heads, 64, L, Lmax, qkv.stride(0), float(scale), 0,
+                                  stream_ptr()), "cddmsl_decode_attn")
+    return out
+
+
+@_timed("pos_embed")
+def pos_embed(wpe, pos0, t, ids=None, tab=None, src=None, out=None):
+    """x [rows, W] f32 = (tab[ids[r]] or src[r]) + wpe[pos0 + r % t]; ids a 1-D int64 (possibly strided) view, tab [vocab, W] bf16
+    or f32; src [rows, W] f32"""
+    require_cuda(wpe, ids, tab, src, out)
+    assert (ids is None) != (src is None) and wpe.dtype == torch.float32 and wpe.is_contiguous()
+    W = wpe.shape[1]
+    if ids is not None:
+        assert ids.dtype == torch.int64 and ids.dim() == 1 and tab is not None and tab.is_contiguous() and tab.shape[1] == W
+        rows, ld, vocab, dt = ids.numel(), ids.stride(0), tab.shape[0], DT[tab.dtype]
+    else:
+        assert src.dtype == torch.float32 and src.is_contiguous() and src.shape[-1] == W
+        rows, ld, vocab, dt = src.numel() // W, 1, 0, 1
+    if out is None:
+        out = torch.empty((rows, W), device=wpe.device, dtype=torch.float32)
+    check(_L().cddmsl_pos_embed(ptr(ids), max(ld, 1), ptr(tab), ptr(src), ptr(wpe), ptr(out), rows, t, pos0, W, vocab, wpe.shape[0], dt,
+                                stream_ptr()), "cddmsl_pos_embed")
+    return out
+
+
+@_timed("gelu_new")
+def gelu_new_(x):
+    """GPT-2's tanh GELU in place (bf16 or f32, contiguous); returns x"""
+    require_cuda(x)
+    assert x.is_contiguous()
+    check(_L().cddmsl_gelu_new(ptr(x), x.numel(), DT[x.dtype], stream_ptr()), "cddmsl_gelu_new")
+    return x
 
 
 @_timed("attn_small")

@@ -1298,3 +1298,36 @@ def quick_gelu_(x):
 def text_pool(x2d, rows, gamma, beta, group=1, out_dtype=torch.float32):
     """ln_final of the rows ``rows`` of the residual stream, averaged over groups of ``group`` consecutive entries"""
     return hip.text_pool(x2d.contiguous(), rows.contiguous(), gamma.detach(), beta.detach(), group, out_dtype)
+
+
+# ------------------------------------------------------------------------------------------------
+# GPT-2 decoder (modeling/gpt2.py): frozen, forward only, like the text encoder.
+# ------------------------------------------------------------------------------------------------
+def skinny_linear(x, w, bias=None, residual=None, gelu=False, out_f32=False, out=None):
+    """x [M <= 64, K] bf16 @ w [N, K]^T + bias: bf16 out, gelu_new -> bf16, or f32 out with the f32 residual added"""
+    epi = 2 if gelu else (1 if out_f32 or residual is not None else 0)
+    return hip.skinny_gemm(x.contiguous(), w, bias, residual, epi, out)
+
+
+def lm_head_argmax(h, wte, ids=None):
+    """greedy next token per row: argmax over the vocabulary of h @ wte^T, lowest index on ties"""
+    return hip.lm_head_argmax(h.contiguous(), wte, ids)
+
+
+def decode_attention(qkv, kc, vc, L, heads, scale, out=None):
+    """one query row per (sequence, head) over the cached positions plus this step's own; appends this step's k / v to the cache"""
+    return hip.decode_attn(qkv, kc, vc, L, heads, scale, out)
+
+
+def token_position_embed(ids, wte, wpe, pos, out=None):
+    """x [n, W] f32 = wte[ids] + wpe[pos]"""
+    return hip.pos_embed(wpe, pos, 1, ids=ids, tab=wte, out=out)
+
+
+def prefix_position_embed(prefix, wpe):
+    """prefix [n, P, W] f32 -> [n*P, W] f32 = prefix + wpe[0..P-1]"""
+    return hip.pos_embed(wpe, 0, prefix.shape[1], src=prefix.contiguous())
+
+
+def gelu_new_(x):
+    return hip.gelu_new_(x)

@@ -1,7 +1,8 @@
 """ClipCap vision-to-language mapper (frozen) -- detectron2/modeling/backbone/clipcap/clipcap.py:39-163,714-719.
 
-Only ``TransformerMapper`` is built (``ClipCaptionModel.clip_project``, engine/train_loop.py:281-288); GPT-2 is
-never constructed (it is off the hot path and needs a network fetch).  Parameter names match ``clip_project.*``.
+Only ``TransformerMapper`` is built here (``ClipCaptionModel.clip_project``, engine/train_loop.py:281-288): training never
+runs GPT-2.  Captioning (tools/gen_captions.py) builds it from the same ClipCap file's ``gpt.*`` entries: modeling/gpt2.py.
+Parameter names match ``clip_project.*``.
 The linears (31 M + 38 M frozen parameters, 3.13 GMAC/sample) run on the HIP MFMA GEMM with input-gradient only;
 LayerNorm is a fused HIP kernel (f32 residual stream in, GEMM operand out); the 80-token softmax(QK^T)V core is one fused
 bf16 MFMA kernel per direction (csrc/attn_small.hip) on the throughput path and fp32 torch ops on the exact-f32 parity path.

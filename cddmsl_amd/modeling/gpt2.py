@@ -1,0 +1,335 @@
+"""GPT-2 decoder (frozen) for ClipCap captioning -- ``ClipCaptionModel.gpt`` (detectron2/modeling/backbone/clipcap/clipcap.py) with
+the reference's ``generate2`` loop (clipcap.py:732-790, used by gen_captions.py): the 40 prefix rows of ``TransformerMapper`` are
+GPT-2's input embeddings, then tokens are appended one at a time.
+
+Greedy decoding.  ``generate2`` filters the logits with top-p before its arg-max; the top-p filter keeps the most probable token
+by construction, so the arg-max of the filtered logits is the arg-max of the raw logits: greedy decoding is exactly what it
+computes.  ``generate`` keeps a KV cache instead of recomputing the whole sequence every step (``torch_gpt2_logits`` /
+``torch_greedy`` restate the recomputing loop for tests and tools/caption_bench.py).
+
+Parameters follow GPT-2's names (``wte``, ``wpe``, ``h.{i}.{ln_1, attn.c_attn, attn.c_proj, ln_2, mlp.c_fc, mlp.c_proj}``, ``ln_f``),
+but the linear weights are stored [out, in] (GPT-2's Conv1D stores [in, out]; they are transposed once at load).  The LM head is
+tied to ``wte``.  The geometry comes from the tensors; heads = n_embd / 64 for every GPT-2 size.
+
+Two paths, as in the text encoder:
+* bf16 throughput path, f32 residual stream.  Prefill (prefix rows): the conv/GEMM kernel, LayerNorm, the causal attention kernel
+  and the gelu_new kernel.  Decode step (one row per caption): skinny GEMM (M <= 64 rows) with bias / residual / gelu_new
+  epilogues, decode attention over the KV cache, ln_f + the LM-head arg-max kernel (the logits are never written).
+* exact-f32 parity path (``compute_dtype=torch.float32``): the f32 GEMM instantiation for every linear, attention and the LM head
+  on torch f32 ops (no f32 kernel exists for them).
+"""
+import os
+import re
+from typing import Dict, Optional
+
+import torch
+from torch import nn
+
+from .. import hip, layers
+from .._lib import require_cuda
+
+HEAD_DIM = 64
+MAX_ROWS = 64            # decode-step rows per chunk: the skinny GEMM's and the LM head's M bound
+_IGNORED = re.compile(r"^h\.\d+\.attn\.(bias|masked_bias)$")     # the causal-mask buffers older transformers files carry
+
+
+class _Lin(nn.Module):
+    def __init__(self, i, o):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(o, i))       # [out, in]
+        self.bias = nn.Parameter(torch.empty(o))
+
+
+class _Attn(nn.Module):
+    def __init__(self, e):
+        super().__init__()
+        self.c_attn, self.c_proj = _Lin(e, 3 * e), _Lin(e, e)
+
+
+class _Mlp(nn.Module):
+    def __init__(self, e):
+        super().__init__()
+        self.c_fc, self.c_proj = _Lin(e, 4 * e), _Lin(4 * e, e)
+
+
+class _Block(nn.Module):
+    def __init__(self, e):
+        super().__init__()
+        self.ln_1, self.attn, self.ln_2, self.mlp = nn.LayerNorm(e), _Attn(e), nn.LayerNorm(e), _Mlp(e)
+
+
+class _Prepared:
+    """device copies: GEMM weights [N, K] in the compute dtype, biases / LayerNorm affines / wpe f32"""
+
+    def __init__(self, dec, dtype):
+        def w(t):
+            t = t.detach().float().contiguous()
+            return hip.weight_prep(t.view(t.shape[0], 1, 1, t.shape[1]), None, dtype, True, False)[0].view(t.shape)
+
+        def f(t):
+            return t.detach().float().contiguous()
+
+        self.wte = w(dec.wte.weight)
+        self.wpe = f(dec.wpe.weight)
+        self.layers = []
+        for b in dec.h:
+            self.layers.append((f(b.ln_1.weight), f(b.ln_1.bias), w(b.attn.c_attn.weight), f(b.attn.c_attn.bias),
+                                w(b.attn.c_proj.weight), f(b.attn.c_proj.bias), f(b.ln_2.weight), f(b.ln_2.bias),
+                                w(b.mlp.c_fc.weight), f(b.mlp.c_fc.bias), w(b.mlp.c_proj.weight), f(b.mlp.c_proj.bias)))
+        self.ln_w, self.ln_b = f(dec.ln_f.weight), f(dec.ln_f.bias)
+
+
+class GPT2Decoder(nn.Module):
+    def __init__(self, n_layer=12, n_embd=768, vocab_size=50257, n_positions=1024, compute_dtype=torch.bfloat16, eps=1e-5):
+        super().__init__()
+        assert n_embd % HEAD_DIM == 0, n_embd
+        self.n_embd, self.heads, self.n_positions, self.compute_dtype, self.eps = n_embd, n_embd // HEAD_DIM, n_positions, compute_dtype, eps
+        self.wte = nn.Embedding(vocab_size, n_embd)
+        self.wpe = nn.Embedding(n_positions, n_embd)
+        self.h = nn.ModuleList([_Block(n_embd) for _ in range(n_layer)])
+        self.ln_f = nn.LayerNorm(n_embd, eps=eps)
+        for p in self.parameters():
+            p.requires_grad = False
+        # decode-step linears: "skinny" (the M <= 64 kernel) or "gemm" (the conv/GEMM kernel, hip.linear_fwd): a measurement switch
+        self.decode_linear = os.environ.get("CDDMSL_GPT2_DECODE_LINEAR", "skinny")
+        self._prep = None
+
+    @property
+    def vocab_size(self):
+        return self.wte.num_embeddings
+
+    # ---------------------------------------------------------------- loading
+    @classmethod
+    def from_state_dict(cls, state: Dict[str, torch.Tensor], compute_dtype=torch.bfloat16):
+        """GPT-2 from a ClipCap file (``gpt.transformer.*`` + ``gpt.lm_head.weight``; the other entries, ``clip_project.*``, are
+        not GPT-2's and are skipped), a transformers ``GPT2LMHeadModel`` file (``transformer.*`` + ``lm_head.weight``) or bare
+        ``GPT2Model`` keys.  Conv1D weights [in, out] are transposed; ``lm_head.weight`` must equal ``wte.weight`` (tied)."""
+        if "gpt.transformer.wte.weight" in state:
+            body, head = "gpt.transformer.", "gpt.lm_head.weight"
+            own = {k for k in state if k.startswith("gpt.")}
+        elif "transformer.wte.weight" in state:
+            body, head, own = "transformer.", "lm_head.weight", set(state)
+        elif "wte.weight" in state:
+            body, head, own = "", "lm_head.weight", set(state)
+        else:
+            raise KeyError("no GPT-2 weights: none of 'gpt.transformer.wte.weight', 'transformer.wte.weight', 'wte.weight' is present")
+        sd = {k[len(body):]: v for k, v in state.items() if k in own and k.startswith(body)}
+        unexpected = sorted(k for k in own if not k.startswith(body) and k != head)
+        pat = re.compile(r"^h\.(\d+)\.")
+        n_layer = len({m.group(1) for m in map(pat.match, sd) if m})
+        wte, wpe = sd["wte.weight"], sd.get("wpe.weight")
+        if wpe is None:
+            raise KeyError(f"GPT-2 tensors missing: ['{body}wpe.weight']")
+        dec = cls(n_layer, wte.shape[1], wte.shape[0], wpe.shape[0], compute_dtype=compute_dtype)
+        expected = set(dec.state_dict())
+        missing = sorted(body + k for k in expected if k not in sd)
+        unexpected += sorted(body + k for k in sd if k not in expected and not _IGNORED.match(k))
+        if missing or unexpected:
+            raise KeyError(f"GPT-2 state dict does not match: missing {missing[:8]}{' ...' if len(missing) > 8 else ''}, "
+                           f"unexpected {unexpected[:8]}{' ...' if len(unexpected) > 8 else ''}")
+        own_sd = {}
+        for k in expected:
+            v = sd[k]
+            if re.match(r"^h\.\d+\.(attn\.c_attn|attn\.c_proj|mlp\.c_fc|mlp\.c_proj)\.weight$", k):
+                v = v.t()                                                   # Conv1D [in, out] -> [out, in]
+            if tuple(v.shape) != tuple(dec.state_dict()[k].shape):
+                raise ValueError(f"{body + k}: shape {tuple(sd[k].shape)} does not fit GPT-2 with n_embd {dec.n_embd}")
+            own_sd[k] = v.contiguous()
+        if head in state and not torch.equal(state[head].to(wte.dtype), wte):
+            raise ValueError(f"{head} differs from {body}wte.weight: only a tied LM head is supported")
+        dec.load_state_dict(own_sd, strict=True)
+        return dec
+
+    def _prepared(self):
+        key = (self.compute_dtype, tuple((p.data_ptr(), p._version) for p in self.parameters()))
+        if self._prep is None or self._prep[0] != key:
+            self._prep = (key, _Prepared(self, self.compute_dtype))
+        return self._prep[1]
+
+    # ---------------------------------------------------------------- generation
+    @torch.no_grad()
+    def generate(self, prefix_embeds, max_tokens=67, stop_id: Optional[int] = None, return_logits=False, check_every=4):
+        """prefix_embeds [N, P, n_embd] f32 -> (tokens [N, max_tokens] int64, lengths [N] int64[, logits [N, steps, V] f32]).
+        Greedy decoding with a KV cache.  A sequence ends after it emits ``stop_id`` (kept in it); the batch ends when every
+        sequence has ended (tested every ``check_every`` steps) or after ``max_tokens``.  Entries at and after ``lengths[n]``
+        are -1; a sequence's tokens do not depend on the other sequences of the batch.  Batches above 64 rows run in chunks of
+        64.  ``return_logits``: the logits of every step run (the LM head's optional output on the bf16 path)."""
+        require_cuda(self.wte.weight)
+        dev = self.wte.weight.device
+        N, P, E = prefix_embeds.shape
+        assert E == self.n_embd and max_tokens >= 1
+        if P + max_tokens - 1 > min(self.n_positions, 1024) or (self.compute_dtype == torch.bfloat16 and P > 128):
+            raise ValueError(f"prefix {P} + {max_tokens} tokens does not fit n_positions {self.n_positions}")
+        prefix_embeds = prefix_embeds.to(dev, torch.float32).contiguous()
+        Pm = self._prepared()                        # once per call: the key walks every parameter
+        toks, lens, logs = [], [], []
+        for c0 in range(0, N, MAX_ROWS):
+            t, lg = self._generate_chunk(Pm, prefix_embeds[c0:c0 + MAX_ROWS], max_tokens, stop_id, return_logits, check_every)
+            toks.append(t)
+            logs.append(lg)
+        tokens = torch.cat(toks) if toks else torch.empty((0, max_tokens), dtype=torch.int64, device=dev)
+        tokens, lengths = finish_tokens(tokens, stop_id)
+        if not return_logits:
+            return tokens, lengths
+        steps = max(lg.shape[1] for lg in logs) if logs else 0
+        logits = torch.full((N, steps, self.vocab_size), float("nan"), device=dev)
+        r = 0
+        for lg in logs:
+            logits[r:r + lg.shape[0], :lg.shape[1]] = lg
+            r += lg.shape[0]
+        return tokens, lengths, logits
+
+    def _generate_chunk(self, Pm, prefix, max_tokens, stop_id, want_logits, check_every):
+        T = self.compute_dtype
+        n, P, E = prefix.shape
+        H, scale = self.heads, HEAD_DIM ** -0.5
+        dev = prefix.device
+        Lmax = P + max_tokens - 1
+        kc = torch.empty((len(Pm.layers), n, Lmax, E), device=dev, dtype=T)
+        vc = torch.empty_like(kc)
+        tokens = torch.full((n, max_tokens), -1, device=dev, dtype=torch.int64)
+        logits = [] if want_logits else None
+
+        # prefill: the P prefix rows of every sequence
+        x = layers.prefix_position_embed(prefix, Pm.wpe)
+        mask = None
+        for li, (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr) in enumerate(Pm.layers):
+            y = hip.layernorm_fwd(x, ln1w, ln1b, T, self.eps)[0]
+            qkv = hip.linear_fwd(y, wqkv, bias=bqkv)                                  # [n*P, 3E] in T
+            q3 = qkv.view(n, P, 3, E)
+            kc[li, :, :P] = q3[:, :, 1]
+            vc[li, :, :P] = q3[:, :, 2]
+            if T == torch.bfloat16:
+                o = layers.causal_attention(qkv, P, H, scale)
+            else:
+                if mask is None:
+                    mask = torch.full((P, P), float("-inf"), device=dev).triu_(1)
+                q, k, v = q3.view(n, P, 3, H, HEAD_DIM).permute(2, 0, 3, 1, 4)
+                att = torch.softmax((q @ k.transpose(-1, -2)) * scale + mask, dim=-1)
+                o = (att @ v).permute(0, 2, 1, 3).reshape(n * P, E).contiguous()
+            x = hip.linear_fwd(o, wo, bias=bo, residual=x, out_f32=True)
+            y = hip.layernorm_fwd(x, ln2w, ln2b, T, self.eps)[0]
+            h = layers.gelu_new_(hip.linear_fwd(y, wfc, bias=bfc))
+            x = hip.linear_fwd(h, wpr, bias=bpr, residual=x, out_f32=True)
+        x = x.view(n, P, E)[:, P - 1].contiguous()
+        self._head(Pm, x, tokens[:, 0], logits)
+
+        xb = torch.empty((n, E), device=dev, dtype=torch.float32)
+        for s in range(1, max_tokens):
+            if stop_id is not None and s % check_every == 0 and bool((tokens[:, :s] == stop_id).any(dim=1).all()):
+                break
+            L = P + s
+            x = layers.token_position_embed(tokens[:, s - 1], Pm.wte, Pm.wpe, L - 1, out=xb)
+            for li, (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr) in enumerate(Pm.layers):
+                y = hip.layernorm_fwd(x, ln1w, ln1b, T, self.eps)[0]
+                if T == torch.bfloat16 and self.decode_linear == "skinny":
+                    qkv = layers.skinny_linear(y, wqkv, bqkv)
+                    o = layers.decode_attention(qkv, kc[li], vc[li], L, H, scale)
+                    x = layers.skinny_linear(o, wo, bo, residual=x, out=x)
+                    y = hip.layernorm_fwd(x, ln2w, ln2b, T, self.eps)[0]
+                    h = layers.skinny_linear(y, wfc, bfc, gelu=True)
+                    x = layers.skinny_linear(h, wpr, bpr, residual=x, out=x)
+                    continue
+                qkv = hip.linear_fwd(y, wqkv, bias=bqkv)
+                if T == torch.bfloat16:
+                    o = layers.decode_attention(qkv, kc[li], vc[li], L, H, scale)
+                else:
+                    q3 = qkv.view(n, 3, H, HEAD_DIM)
+                    kc[li, :, L - 1] = qkv[:, E:2 * E]
+                    vc[li, :, L - 1] = qkv[:, 2 * E:]
+                    kk = kc[li, :, :L].view(n, L, H, HEAD_DIM).transpose(1, 2)          # [n, H, L, 64]
+                    vv = vc[li, :, :L].view(n, L, H, HEAD_DIM).transpose(1, 2)
+                    att = torch.softmax((q3[:, 0].unsqueeze(2) @ kk.transpose(-1, -2)) * scale, dim=-1)   # [n, H, 1, L]
+                    o = (att @ vv).reshape(n, E).contiguous()
+                x = hip.linear_fwd(o, wo, bias=bo, residual=x, out_f32=True)
+                y = hip.layernorm_fwd(x, ln2w, ln2b, T, self.eps)[0]
+                h = layers.gelu_new_(hip.linear_fwd(y, wfc, bias=bfc))
+                x = hip.linear_fwd(h, wpr, bias=bpr, residual=x, out_f32=True)
+            self._head(Pm, x, tokens[:, s], logits)
+        return tokens, (torch.stack(logits, dim=1) if want_logits else None)
+
+    def _head(self, Pm, x, out_ids, logits):
+        """ln_f + the tied LM head's arg-max of rows x [n, E] f32 into out_ids (a strided column of the token buffer)"""
+        y = hip.layernorm_fwd(x, Pm.ln_w, Pm.ln_b, self.compute_dtype, self.eps)[0]
+        if self.compute_dtype == torch.bfloat16:
+            r = hip.lm_head_argmax(y, Pm.wte, ids=out_ids, logits=logits is not None)
+            if logits is not None:
+                logits.append(r[1])
+            return
+        lg = y @ Pm.wte.t()
+        out_ids.copy_(lg.argmax(dim=1))
+        if logits is not None:
+            logits.append(lg)
+
+
+def finish_tokens(tokens, stop_id: Optional[int]):
+    """tokens [N, T] as generated (-1 where a step was not run) -> (tokens with every entry after a sequence's stop token set to -1,
+    lengths [N]): a sequence's length runs to its first ``stop_id`` inclusive, else to its first -1 or T"""
+    N, T = tokens.shape
+    pos = torch.arange(T, device=tokens.device).expand(N, T)
+    end = torch.where(tokens < 0, pos, torch.full_like(pos, T)).min(dim=1).values
+    if stop_id is not None:
+        hit = torch.where(tokens == stop_id, pos + 1, torch.full_like(pos, T)).min(dim=1).values
+        end = torch.minimum(end, hit)
+    out = torch.where(pos < end.unsqueeze(1), tokens, torch.full_like(tokens, -1))
+    return out, end
+
+
+def torch_gpt2_logits(dec: GPT2Decoder, embeds, dtype=torch.float32):
+    """GPT-2's forward restated on plain torch ops: input embeddings [N, T, E] -> logits [N, T, V] (wpe[0..T-1] added, causal
+    attention, tied LM head).  The yardstick of the tests and tools/caption_bench.py; never called by the decoder itself."""
+    dev = dec.wte.weight.device
+    x = embeds.to(dev, dtype)
+    N, T, E = x.shape
+    H = dec.heads
+
+    def lin(v, m):
+        return v @ m.weight.to(dtype).t() + m.bias.to(dtype)
+
+    def ln(v, m):
+        return torch.nn.functional.layer_norm(v, (E,), m.weight.to(dtype), m.bias.to(dtype), dec.eps)
+
+    x = x + dec.wpe.weight.to(dtype)[:T]
+    mask = torch.full((T, T), float("-inf"), device=dev, dtype=dtype).triu_(1)
+    for b in dec.h:
+        q, k, v = lin(ln(x, b.ln_1), b.attn.c_attn).view(N, T, 3, H, HEAD_DIM).permute(2, 0, 3, 1, 4)
+        att = torch.softmax((q @ k.transpose(-1, -2)) * HEAD_DIM ** -0.5 + mask, dim=-1)
+        x = x + lin((att @ v).permute(0, 2, 1, 3).reshape(N, T, E), b.attn.c_proj)
+        h = lin(ln(x, b.ln_2), b.mlp.c_fc)
+        h = 0.5 * h * (1.0 + torch.tanh(0.7978845608028654 * (h + 0.044715 * h ** 3)))
+        x = x + lin(h, b.mlp.c_proj)
+    return ln(x, dec.ln_f) @ dec.wte.weight.to(dtype).t()
+
+
+def torch_greedy(dec: GPT2Decoder, prefix, max_tokens=67, stop_id: Optional[int] = None, dtype=torch.float32):
+    """the reference's loop (generate2 without its top-p filter, which never removes the arg-max): the full sequence recomputed
+    every step -> (tokens [N, max_tokens] int64 (-1 after a stop), lengths [N], per-step last-row logits [N, steps, V])"""
+    dev = dec.wte.weight.device
+    emb = prefix.to(dev, dtype)
+    N = emb.shape[0]
+    toks, logs = [], []
+    done = torch.zeros(N, dtype=torch.bool, device=dev)
+    for _ in range(max_tokens):
+        lg = torch_gpt2_logits(dec, emb, dtype)[:, -1]
+        t = lg.argmax(dim=1)
+        toks.append(t)
+        logs.append(lg)
+        if stop_id is not None:
+            done |= t == stop_id
+            if bool(done.all()):
+                break
+        emb = torch.cat([emb, dec.wte.weight.to(dtype)[t].unsqueeze(1)], dim=1)
+    tokens = torch.full((N, max_tokens), -1, dtype=torch.int64, device=dev)
+    tokens[:, :len(toks)] = torch.stack(toks, dim=1)
+    tokens, lengths = finish_tokens(tokens, stop_id)
+    return tokens, lengths, torch.stack(logs, dim=1)
+
+
+def load_gpt2(path: str, compute_dtype=torch.bfloat16) -> GPT2Decoder:
+    """GPT-2 from a file holding a ClipCap / transformers / bare state dict (``torch.load``; a ``{"model": ...}`` wrapper is opened)"""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"GPT-2 weights not found: {path}")
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(state, dict) and "model" in state and isinstance(state["model"], dict):
+        state = state["model"]
+    return GPT2Decoder.from_state_dict(state, compute_dtype)

@@ -233,6 +233,21 @@ class GeneralizedRCNN(nn.Module):
             results = self.roi_heads.forward_with_given_boxes(feats, [x.to(self.device) for x in detected_instances])
         return self._postprocess(results, batched_inputs, sizes) if do_postprocess else results
 
+    @torch.no_grad()
+    def inference_with_region_embeddings(self, batched_inputs: List[Dict]):
+        """eval only: ``inference`` (proposals, box head, per-class NMS) with each kept detection's attention-pool embedding as the
+        ``region_embeds`` field of its Instances, boxes rescaled to the original image by ``detector_postprocess`` (which drops
+        empty boxes together with their embeddings)"""
+        assert not self.training
+        images, sizes = self.preprocess_image(batched_inputs, "image")
+        res4 = self.backbone.forward_nhwc(images, want_res5=False)["res4"]
+        proposals, _ = self.proposal_generator.forward_nhwc(sizes, res4, None)
+        results, embeds = self.roi_heads.inference_with_region_embeddings({"res4": to_nchw(res4)}, proposals, res5=self.backbone.layer4,
+                                                                          attnpool=self.backbone.attnpool)
+        for r, e in zip(results, embeds):
+            r.region_embeds = e
+        return self._postprocess(results, batched_inputs, sizes)
+
     @staticmethod
     def _postprocess(instances, batched_inputs, image_sizes):
         """rcnn.py:770-784: rescale to the dataset dict's original ``height`` / ``width``"""

@@ -105,12 +105,16 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
     return ki[scores[ki].sort(descending=True, stable=True)[1]]
 
 
-def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, nms_thresh, topk_per_image):
+def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, nms_thresh, topk_per_image, proposal_indices=False):
     """fast_rcnn.py:130-209 (hard NMS): drop non-finite rows, clip, score threshold per (proposal, class), per-class NMS,
-    keep the top-k.  boxes [R, 4K], scores [R, K+1] -> (Instances, indices of the kept proposals)."""
+    keep the top-k.  boxes [R, 4K], scores [R, K+1] -> (Instances, indices of the kept proposals).  As in the reference, those
+    indices count the rows left after the non-finite ones are dropped; ``proposal_indices=True`` maps them back to rows of the
+    input (the proposal each detection came from)."""
     valid = torch.isfinite(boxes).all(dim=1) & torch.isfinite(scores).all(dim=1)
+    rows = None
     if not bool(valid.all()):
         boxes, scores = boxes[valid], scores[valid]
+        rows = valid.nonzero()[:, 0]
     scores = scores[:, :-1]
     k = boxes.shape[1] // 4
     b = Boxes(boxes.reshape(-1, 4))
@@ -125,7 +129,8 @@ def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, n
         keep = keep[:topk_per_image]
     res = Instances(tuple(image_shape))
     res.pred_boxes, res.scores, res.pred_classes = Boxes(boxes[keep]), scores[keep], inds[keep, 1]
-    return res, inds[keep, 0]
+    kept = inds[keep, 0]
+    return res, (rows[kept] if proposal_indices and rows is not None else kept)
 
 
 class FastRCNNOutputLayers(nn.Module):
@@ -240,14 +245,15 @@ class FastRCNNOutputLayers(nn.Module):
         scores, _ = predictions
         return F.softmax(scores.float(), dim=-1).split([len(p) for p in proposals], dim=0)
 
-    def inference(self, predictions, proposals):
-        """fast_rcnn.py:691-724 -> (list[Instances(pred_boxes, scores, pred_classes)], list[kept proposal indices])"""
+    def inference(self, predictions, proposals, proposal_indices=False):
+        """fast_rcnn.py:691-724 -> (list[Instances(pred_boxes, scores, pred_classes)], list[kept proposal indices]); the indices
+        count finite rows only unless ``proposal_indices`` (fast_rcnn_inference_single_image)"""
         boxes = self.predict_boxes(predictions, proposals)
         scores = self.predict_probs(predictions, proposals)
         if self.multiply_rpn_score and not self.training:   # geometric mean with the RPN objectness (fast_rcnn.py:708-710)
             scores = [(s * p.objectness_logits[:, None]) ** 0.5 for s, p in zip(scores, proposals)]
         out = [fast_rcnn_inference_single_image(b, s, p.image_size, self.test_score_thresh, self.test_nms_thresh,
-                                                self.test_topk_per_image) for b, s, p in zip(boxes, scores, proposals)]
+                                                self.test_topk_per_image, proposal_indices) for b, s, p in zip(boxes, scores, proposals)]
         return [o[0] for o in out], [o[1] for o in out]
 
     def _log_stats(self, scores, gt_classes):
@@ -389,6 +395,16 @@ class CLIPRes5ROIHeads(nn.Module):
         pred_instances, _ = self.box_predictor.inference(predictions, proposals)     # clip_roi_heads.py:171-174
         return self.forward_with_given_boxes(features, pred_instances, res5), {}
 
+    @torch.no_grad()
+    def inference_with_region_embeddings(self, features, proposals, res5=None, attnpool=None):
+        """eval only: ``forward``'s inference plus, per image, the attention-pool embeddings [k, D] of the proposals the kept
+        detections came from (what the reference's tools/extract_region_features.py saves as ``att_feats[keep_indices]``)"""
+        assert not self.training and attnpool is not None
+        att = self._pooled_embeddings(to_nhwc(features[self.in_features[0]]), [p.proposal_boxes for p in proposals], res5, attnpool)
+        pred_instances, kept = self.box_predictor.inference(self.box_predictor(att), proposals, proposal_indices=True)
+        per_image = att.split([len(p) for p in proposals])
+        return pred_instances, [a[k] for a, k in zip(per_image, kept)]
+
     def forward_with_given_boxes(self, features, instances, res5=None):
         """clip_roi_heads.py:176-199 with MASK_ON False: nothing to add"""
         assert not self.training
@@ -419,6 +435,9 @@ class Res5ROIHeads(CLIPRes5ROIHeads):
             return [], self.box_predictor.losses(predictions, proposals)
         pred_instances, _ = self.box_predictor.inference(predictions, proposals)     # roi_heads.py:497-500
         return self.forward_with_given_boxes(features, pred_instances), {}
+
+    def inference_with_region_embeddings(self, features, proposals, res5=None, attnpool=None):
+        raise NotImplementedError("Res5ROIHeads has no CLIP attention-pool region embedding: captioning regions needs CLIPRes5ROIHeads")
 
 
 def build_roi_heads(cfg, input_shape):

@@ -220,3 +220,38 @@ def make_text_state_dict(seed=0, width=512, layers=12, embed_dim=1024, vocab_siz
     ln("ln_final", width)
     sd["text_projection"] = torch.randn(width, embed_dim, generator=g) * width ** -0.5
     return sd
+
+
+def make_gpt2_state_dict(seed=0, n_layer=12, n_embd=768, vocab=50257, n_positions=1024) -> Dict[str, torch.Tensor]:
+    """GPT-2 (``GPT2Model``) state dict under the bare names (``wte.weight``, ``h.{i}.attn.c_attn.weight``, .., ``ln_f.bias``), Conv1D
+    weights stored [in, out] as in transformers files.  numpy-seeded (``RandomState(seed)``), so every machine draws the same tensors.
+    The token embedding uses std 0.1 (GPT-2's init uses 0.02): the tied LM head's logits then have top-2 margins that bf16 rounding
+    does not flip at most steps; biases and LayerNorm affines are non-trivial so every epilogue term is exercised."""
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    E = n_embd
+
+    def rn(*shape, std):
+        return torch.from_numpy((rs.standard_normal(shape) * std).astype(np.float32))
+
+    sd: Dict[str, torch.Tensor] = {"wte.weight": rn(vocab, E, std=0.1), "wpe.weight": rn(n_positions, E, std=0.02)}
+
+    def ln(p):
+        sd[p + ".weight"] = 1.0 + rn(E, std=0.1)
+        sd[p + ".bias"] = rn(E, std=0.05)
+
+    proj_std = 0.02 / (2 * n_layer) ** 0.5 * 4
+    for i in range(n_layer):
+        q = f"h.{i}"
+        ln(q + ".ln_1")
+        sd[q + ".attn.c_attn.weight"] = rn(E, 3 * E, std=0.05)
+        sd[q + ".attn.c_attn.bias"] = rn(3 * E, std=0.02)
+        sd[q + ".attn.c_proj.weight"] = rn(E, E, std=proj_std)
+        sd[q + ".attn.c_proj.bias"] = rn(E, std=0.02)
+        ln(q + ".ln_2")
+        sd[q + ".mlp.c_fc.weight"] = rn(E, 4 * E, std=0.03)
+        sd[q + ".mlp.c_fc.bias"] = rn(4 * E, std=0.02)
+        sd[q + ".mlp.c_proj.weight"] = rn(4 * E, E, std=proj_std)
+        sd[q + ".mlp.c_proj.bias"] = rn(E, std=0.02)
+    ln("ln_f")
+    return sd

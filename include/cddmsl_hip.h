@@ -228,6 +228,35 @@ int cddmsl_quick_gelu(void* x, long numel, int dtype, void* stream);
 int cddmsl_text_pool(const float* x, const long* rows, const float* gamma, const float* beta, void* y, long R, int nout, int group,
                      int W, float eps, int dtype, void* stream);
 
+/* ---- GPT-2 decoder for ClipCap captioning (gen_captions.py, clipcap.py generate2; forward only).  The prefill runs on
+ * cddmsl_conv_fwd, cddmsl_layernorm_fwd and cddmsl_attn_causal_fwd; these cover the rest and the decode step.
+ * skinny_gemm: y [M][N] = x [M][K] bf16 @ w [N][K]^T bf16 + bias [N] f32 (optional), f32 accumulation, 1 <= M <= 64, N % 8 == 0,
+ *              K % 64 == 0, all pointers 16-byte aligned.  epi 0: y bf16; 1: y f32 (+ residual [M][N] f32 if given; y may be
+ *              residual); 2: y bf16 = gelu_new (tanh form).  A fixed split of K that depends on (N, K) only goes through ws
+ *              (ws_bytes >= cddmsl_skinny_gemm_workspace(M, N, K)): a row's result does not depend on M or the other rows.
+ * skinny_gemm_workspace: the bytes skinny_gemm needs in ws, -1 outside the contract.
+ * lm_head_argmax: ids[m * ld_ids] (int64) = argmax_v (h [M][K] bf16 @ wte [V][K]^T bf16)[m][v], the lowest index among equal
+ *              maxima; 1 <= M <= 64, K % 64 == 0; logits [M][V] f32 written only when non-NULL; ws_bytes >=
+ *              cddmsl_lm_head_workspace(M, V).
+ * decode_attn: per (sequence s, head h), dh == 64: o [nseq][heads*64] bf16 = softmax(q k^T * scale) v over positions 0..L-1;
+ *              qkv [nseq][ldqkv] bf16 = this step's c_attn output (q | k | v blocks of heads*64 columns), kc / vc [nseq][Lmax][heads*64]
+ *              bf16 hold positions 0..L-2; this step's k / v (position L-1) are read from qkv and written to kc / vc.
+ *              1 <= L <= min(Lmax, 1024), bf16 only (dtype 0).
+ * pos_embed:   x [rows][W] f32 = row value + wpe[pos0 + r % t]; the row value is tab[ids[r * ld_ids]] (tab [vocab][W] in `dtype`)
+ *              when ids is given, else src [rows][W] f32 (exactly one of ids / src); pos0 + t <= npos, W % 8 == 0.
+ * gelu_new:    x = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) in place, numel % 8 == 0 (bf16) / % 4 == 0 (f32). */
+int cddmsl_skinny_gemm_workspace(int M, int N, int K);
+int cddmsl_skinny_gemm(const void* x, const void* w, const float* bias, const float* residual, void* y, float* ws, long ws_bytes, int M,
+                       int N, int K, int epi, void* stream);
+int cddmsl_lm_head_workspace(int M, int V);
+int cddmsl_lm_head_argmax(const void* h, const void* wte, long* ids, int ld_ids, float* logits, void* ws, long ws_bytes, int M, int V,
+                          int K, void* stream);
+int cddmsl_decode_attn(const void* qkv, void* kc, void* vc, void* o, int nseq, int heads, int dh, int L, int Lmax, int ldqkv, float scale,
+                       int dtype, void* stream);
+int cddmsl_pos_embed(const long* ids, int ld_ids, const void* tab, const float* src, const float* wpe, float* x, long rows, int t, int pos0,
+                     int W, int vocab, int npos, int dtype, void* stream);
+int cddmsl_gelu_new(void* x, long numel, int dtype, void* stream);
+
 /* ---- fp32 heads: cosine-logit classifier (modeling/roi_heads/fast_rcnn.py:546-572) and the contrastive loss over
  * the cosine-similarity matrix (modeling/meta_arch/rcnn.py:308-317,458-468) ------------------------------------ */
 int cddmsl_l2norm_fwd(const float* x, float* y, float* inv, long R, int D, float eps, void* stream);
