@@ -782,14 +782,16 @@ def test_roi_align_row_sliding_kernel_equals_the_tap_kernel(sr, monkeypatch):
         assert len(zero) == (2 if sr == 0 else 1) and all(bool((got["1"][0][i] == 0).all()) for i in zero)
 
 
-@pytest.mark.parametrize("premask", [False, True])
-def test_attention_pool_input_gradient_fused_epilogue(premask, monkeypatch):
+@pytest.mark.parametrize("premask,K", [pytest.param(False, 300, id="False"), pytest.param(True, 300, id="True"),
+                                       pytest.param(True, 544, id="True-K544"), pytest.param(True, 8192, id="True-K8192")])
+def test_attention_pool_input_gradient_fused_epilogue(premask, K, monkeypatch):
     """cddmsl_attnpool_dx (the token-gradient product with the map's gradient, the ReLU mask as bit words and the positional
     embedding's gradient in its epilogue) against the stored-dtok route (CDDMSL_ATTNPOOL_DX=0: product, ``dtok[:, 0] +=``,
     cddmsl_attn_tokens_bwd): the map's gradient, every parameter gradient of the pool, and -- the kernel alone -- against an f32
-    torch evaluation of its definition.  300 regions (run boundaries of the streaming kernel: 8-region blocks + a tail)."""
+    torch evaluation of its definition.  300 regions (run boundaries of the streaming kernel: 8-region blocks + a tail), and the
+    bench's 544 and 8192 (8- and 32-region runs)."""
     from cddmsl_amd import hip, layers
-    K, C, H, P, TP = 300, 2048, 32, 49, 56
+    C, H, P, TP = 2048, 32, 49, 56
     g = torch.Generator().manual_seed(5)
     # the kernel against its definition
     pds = (torch.randn(K, 2 * H, TP, generator=g) * 0.3).bfloat16().cuda()
