@@ -32,6 +32,12 @@ __device__ __forceinline__ unsigned int pack2bf(float lo, float hi) {
   return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2_));
 }
 
+// the two frozen towers' MLP activations (the in-place kernel of text_encoder.hip; gelu_new also in gpt2.hip's skinny epilogue)
+// QuickGELU: x * sigmoid(1.702 x)
+__device__ __forceinline__ float qgelu(float v) { return v * (1.f / (1.f + __expf(-1.702f * v))); }
+// gelu_new (transformers.activations.NewGELUActivation): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))
+__device__ __forceinline__ float gelu_new(float v) { return 0.5f * v * (1.f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v))); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -9,9 +9,9 @@
 //                  (max, index) per row, then one reduction launch per row.  Optional f32 logits for tests.
 //   decode_attn    one query row per (sequence, head) against a KV cache of positions 0..L-2 plus this step's own key / value, which
 //                  it appends to the cache at position L-1 (the cache is never copied).
-//   pos_embed      x[r] = (tab[ids[r]] or src[r]) + wpe[pos0 + r % t]: the decode step's token + position and the prefill's prefix +
-//                  position (text_embed's r % t has no offset).
-//   gelu_new       GPT-2's tanh GELU in place on the prefill's c_fc output.
+//   pos_embed      x[r] = (tab[ids[r]] or src[r]) + wpe[pos0 + r % t]: the decode step's token + position, the prefill's prefix +
+//                  position, and the CLIP text encoder's token + position (text_embed: contiguous ids, pos0 = 0).
+// The prefill's in-place gelu_new runs on text_encoder.hip's activation kernel.
 #include "common.h"
 
 namespace {
@@ -120,9 +120,6 @@ __global__ __launch_bounds__(256) void k_skinny_partial(const char* __restrict__
       if (m < M) ps[(long)m * N + n] = acc[mt][g];
     }
 }
-
-// gelu_new (transformers.activations.NewGELUActivation): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))
-__device__ __forceinline__ float gelu_new(float v) { return 0.5f * v * (1.f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v))); }
 
 // epilogue: 4 columns per thread; y = sum_s part[s] (s ascending) + bias [+ residual] -> f32, or -> bf16, or gelu_new -> bf16
 __global__ __launch_bounds__(256) void k_skinny_epilogue(const float* __restrict__ part, const float* __restrict__ bias,
@@ -329,20 +326,14 @@ __global__ __launch_bounds__(256) void k_pos_embed(const long* __restrict__ ids,
   out[1] = make_float4(v[4] + p1.x, v[5] + p1.y, v[6] + p1.z, v[7] + p1.w);
 }
 
-__global__ __launch_bounds__(256) void k_gelu_new_bf16(u32x4* x, long n16) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n16) return;
-  u32x4 u = x[i];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) u[e] = pack2bf(gelu_new(bf2f(u[e] & 0xffff)), gelu_new(bf2f(u[e] >> 16)));
-  x[i] = u;
-}
-__global__ __launch_bounds__(256) void k_gelu_new_f32(float4* x, long n16) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n16) return;
-  float4 v = x[i];
-  v.x = gelu_new(v.x); v.y = gelu_new(v.y); v.z = gelu_new(v.z); v.w = gelu_new(v.w);
-  x[i] = v;
+int launch_pos_embed(const long* ids, int ld_ids, const void* tab, const float* src, const float* wpe, float* x, long rows, int t, int pos0,
+                     int W, int vocab, int dtype, void* stream) {
+  if (rows == 0) return CDDMSL_OK;
+  const long n = rows * (W / 8);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (dtype == 0) hipLaunchKernelGGL(k_pos_embed<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, ids, ld_ids, tab, src, wpe, x, rows, t, pos0, W, vocab);
+  else hipLaunchKernelGGL(k_pos_embed<float>, grid, dim3(256), 0, (hipStream_t)stream, ids, ld_ids, tab, src, wpe, x, rows, t, pos0, W, vocab);
+  return launch_status();
 }
 
 }  // namespace
@@ -406,20 +397,12 @@ extern "C" int cddmsl_pos_embed(const long* ids, int ld_ids, const void* tab, co
   if (rows < 0 || t <= 0 || pos0 < 0 || pos0 + t > npos || W <= 0 || (W & 7) || (dtype != 0 && dtype != 1)) return CDDMSL_ERR_ARG;
   if ((ids == nullptr) == (src == nullptr) || (ids && (tab == nullptr || ld_ids < 1 || vocab <= 0 || !al16(tab))) || (src && !al16(src))) return CDDMSL_ERR_ARG;
   if (!al16(wpe) || !al16(x)) return CDDMSL_ERR_ARG;
-  if (rows == 0) return CDDMSL_OK;
-  const long n = rows * (W / 8);
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == 0) hipLaunchKernelGGL(k_pos_embed<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, ids, ld_ids, tab, src, wpe, x, rows, t, pos0, W, vocab);
-  else hipLaunchKernelGGL(k_pos_embed<float>, grid, dim3(256), 0, (hipStream_t)stream, ids, ld_ids, tab, src, wpe, x, rows, t, pos0, W, vocab);
-  return launch_status();
+  return launch_pos_embed(ids, ld_ids, tab, src, wpe, x, rows, t, pos0, W, vocab, dtype, stream);
 }
 
-extern "C" int cddmsl_gelu_new(void* x, long numel, int dtype, void* stream) {
-  if (numel < 0 || (dtype != 0 && dtype != 1) || !al16(x) || (numel % (dtype == 0 ? 8 : 4))) return CDDMSL_ERR_ARG;
-  if (numel == 0) return CDDMSL_OK;
-  const long n16 = numel / (dtype == 0 ? 8 : 4);
-  const dim3 grid((unsigned)((n16 + 255) / 256));
-  if (dtype == 0) hipLaunchKernelGGL(k_gelu_new_bf16, grid, dim3(256), 0, (hipStream_t)stream, (u32x4*)x, n16);
-  else hipLaunchKernelGGL(k_gelu_new_f32, grid, dim3(256), 0, (hipStream_t)stream, (float4*)x, n16);
-  return launch_status();
+extern "C" int cddmsl_text_embed(const long* ids, const void* tok, const float* pos, float* x, long rows, int t, int W, int vocab, int dtype,
+                                 void* stream) {
+  if (rows < 0 || t <= 0 || W <= 0 || (W & 7) || vocab <= 0 || (dtype != 0 && dtype != 1)) return CDDMSL_ERR_ARG;
+  if (!al16(tok) || !al16(pos) || !al16(x)) return CDDMSL_ERR_ARG;
+  return launch_pos_embed(ids, 1, tok, nullptr, pos, x, rows, t, 0, W, vocab, dtype, stream);
 }

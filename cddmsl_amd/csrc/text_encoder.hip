@@ -1,49 +1,14 @@
 // CLIP text encoder (RegionCLIP's language tower: detectron2/modeling/backbone/clip_backbone.py:273-317,732-877), forward only --
 // the reference freezes it (clip_rcnn.py:438-439).  The linears run on the conv/GEMM kernels (gemm_conv.hip) and the two per-layer
-// LayerNorms on the mapper's LayerNorm kernel (losses.hip); this file holds what those do not cover:
-//   text_embed    x [n*t][W] f32 = token_embedding[id] + positional_embedding[t]          (encode_text's first two lines)
+// LayerNorms on the mapper's LayerNorm kernel (losses.hip), and the token + positional embedding (encode_text's first two lines) on
+// pos_embed (gpt2.hip); this file holds what those do not cover:
 //   attn_causal   o = softmax(q k^T dh^-0.5 + mask) v per (sequence, head), keys j <= query i (build_attention_mask), dh = 64
-//   quick_gelu    x * sigmoid(1.702 x) in place on the c_fc output                          (QuickGELU)
+//   quick_gelu    x * sigmoid(1.702 x) in place on the c_fc output (QuickGELU), and gelu_new, GPT-2's tanh GELU, on its prefill's:
+//                 one in-place kernel for both
 //   text_pool     ln_final of each sequence's EOT row, optionally averaged over groups of consecutive rows (the concept mean)
 #include "common.h"
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// token + positional embedding.  One thread per 8 output columns: one 16-byte table read (bf16) or two (f32), two of pos.
-template <typename T> struct Tab8;
-template <> struct Tab8<__bf16> {
-  __device__ static __forceinline__ void get(const void* row, int c8, float (&v)[8]) {
-    const u32x4 u = ((const u32x4*)row)[c8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = bf2f(u[e] & 0xffff); v[2 * e + 1] = bf2f(u[e] >> 16); }
-  }
-};
-template <> struct Tab8<float> {
-  __device__ static __forceinline__ void get(const void* row, int c8, float (&v)[8]) {
-    const float4 a = ((const float4*)row)[2 * c8], b = ((const float4*)row)[2 * c8 + 1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_text_embed(const long* __restrict__ ids, const void* __restrict__ tok, const float* __restrict__ pos,
-                                                    float* __restrict__ x, long rows, int t, int W, int vocab) {
-  const int per_row = W / 8;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= rows * per_row) return;
-  const long row = idx / per_row;
-  const int c8 = (int)(idx - row * per_row);
-  long id = ids[row];
-  id = (id < 0 || id >= vocab) ? 0 : id;         // (memory safety only: the host rejects such ids before they get here)
-  float v[8];
-  Tab8<T>::get((const char*)tok + id * (long)W * sizeof(T), c8, v);
-  const float4* pr = (const float4*)(pos + (long)(row % t) * W) + 2 * c8;
-  const float4 p0 = pr[0], p1 = pr[1];
-  float4* out = (float4*)(x + row * W) + 2 * c8;
-  out[0] = make_float4(v[0] + p0.x, v[1] + p0.y, v[2] + p0.z, v[3] + p0.w);
-  out[1] = make_float4(v[4] + p1.x, v[5] + p1.y, v[6] + p1.z, v[7] + p1.w);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Causal attention for short sequences (CLIP's text transformer: t <= 77 tokens, heads of 64).  bf16 MFMA
@@ -185,23 +150,21 @@ __global__ __launch_bounds__(256) void k_attn_causal_fwd(const char* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// QuickGELU in place, 16 bytes per thread
-__device__ __forceinline__ float qgelu(float v) { return v * (1.f / (1.f + __expf(-1.702f * v))); }
-
-__global__ __launch_bounds__(256) void k_quick_gelu_bf16(u32x4* x, long n16) {
+// In-place activation F (qgelu / gelu_new, common.h) on T = __bf16 or float, 16 bytes per thread
+template <float (*F)(float), typename T>
+__global__ __launch_bounds__(256) void k_act_inplace(void* x, long n16) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n16) return;
-  u32x4 u = x[i];
+  if constexpr (sizeof(T) == 2) {
+    u32x4 u = ((u32x4*)x)[i];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) u[e] = pack2bf(qgelu(bf2f(u[e] & 0xffff)), qgelu(bf2f(u[e] >> 16)));
-  x[i] = u;
-}
-__global__ __launch_bounds__(256) void k_quick_gelu_f32(float4* x, long n16) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n16) return;
-  float4 v = x[i];
-  v.x = qgelu(v.x); v.y = qgelu(v.y); v.z = qgelu(v.z); v.w = qgelu(v.w);
-  x[i] = v;
+    for (int e = 0; e < 4; ++e) u[e] = pack2bf(F(bf2f(u[e] & 0xffff)), F(bf2f(u[e] >> 16)));
+    ((u32x4*)x)[i] = u;
+  } else {
+    float4 v = ((float4*)x)[i];
+    v.x = F(v.x); v.y = F(v.y); v.z = F(v.z); v.w = F(v.w);
+    ((float4*)x)[i] = v;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -251,19 +214,18 @@ __global__ __launch_bounds__(256) void k_text_pool(const float* __restrict__ x, 
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-}  // namespace
-
-extern "C" int cddmsl_text_embed(const long* ids, const void* tok, const float* pos, float* x, long rows, int t, int W, int vocab, int dtype,
-                                 void* stream) {
-  if (rows < 0 || t <= 0 || W <= 0 || (W & 7) || vocab <= 0 || (dtype != 0 && dtype != 1)) return CDDMSL_ERR_ARG;
-  if (!al16(tok) || !al16(pos) || !al16(x)) return CDDMSL_ERR_ARG;
-  if (rows == 0) return CDDMSL_OK;
-  const long n = rows * (W / 8);
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if (dtype == 0) hipLaunchKernelGGL(k_text_embed<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, ids, tok, pos, x, rows, t, W, vocab);
-  else hipLaunchKernelGGL(k_text_embed<float>, grid, dim3(256), 0, (hipStream_t)stream, ids, tok, pos, x, rows, t, W, vocab);
+template <float (*F)(float)>
+int act_inplace(void* x, long numel, int dtype, void* stream) {
+  if (numel < 0 || (dtype != 0 && dtype != 1) || !al16(x) || (numel % (dtype == 0 ? 8 : 4))) return CDDMSL_ERR_ARG;
+  if (numel == 0) return CDDMSL_OK;
+  const long n16 = numel / (dtype == 0 ? 8 : 4);
+  const dim3 grid((unsigned)((n16 + 255) / 256));
+  if (dtype == 0) hipLaunchKernelGGL((k_act_inplace<F, __bf16>), grid, dim3(256), 0, (hipStream_t)stream, x, n16);
+  else hipLaunchKernelGGL((k_act_inplace<F, float>), grid, dim3(256), 0, (hipStream_t)stream, x, n16);
   return launch_status();
 }
+
+}  // namespace
 
 extern "C" int cddmsl_attn_causal_fwd(const void* qkv, void* o, int nseq, int t, int heads, int dh, int ldqkv, int ldo, float scale, int dtype,
                                       void* stream) {
@@ -285,15 +247,8 @@ extern "C" int cddmsl_attn_causal_fwd(const void* qkv, void* o, int nseq, int t,
   return launch_status();
 }
 
-extern "C" int cddmsl_quick_gelu(void* x, long numel, int dtype, void* stream) {
-  if (numel < 0 || (dtype != 0 && dtype != 1) || !al16(x) || (numel % (dtype == 0 ? 8 : 4))) return CDDMSL_ERR_ARG;
-  if (numel == 0) return CDDMSL_OK;
-  const long n16 = numel / (dtype == 0 ? 8 : 4);
-  const dim3 grid((unsigned)((n16 + 255) / 256));
-  if (dtype == 0) hipLaunchKernelGGL(k_quick_gelu_bf16, grid, dim3(256), 0, (hipStream_t)stream, (u32x4*)x, n16);
-  else hipLaunchKernelGGL(k_quick_gelu_f32, grid, dim3(256), 0, (hipStream_t)stream, (float4*)x, n16);
-  return launch_status();
-}
+extern "C" int cddmsl_quick_gelu(void* x, long numel, int dtype, void* stream) { return act_inplace<qgelu>(x, numel, dtype, stream); }
+extern "C" int cddmsl_gelu_new(void* x, long numel, int dtype, void* stream) { return act_inplace<gelu_new>(x, numel, dtype, stream); }
 
 extern "C" int cddmsl_text_pool(const float* x, const long* rows, const float* gamma, const float* beta, void* y, long R, int nout, int group,
                                 int W, float eps, int dtype, void* stream) {

@@ -849,7 +849,7 @@ _WS = {}
 def workspace(key, nbytes, device):
     """Persistent scratch buffers (NMS masks, sort temp storage ...): allocated once per (key, size) and reused, so the
     hot loop never goes back to the allocator for its 100+ MB workspaces."""
-    k = (key, str(device))
+    k = (key, device)         # (a torch.device hashes by type and index; a str() per call shows on the GPT-2 decode step)
     buf = _WS.get(k)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
@@ -1231,20 +1231,6 @@ def text_pool(x, rows, gamma, beta, group=1, out_dtype=torch.float32, eps=1e-5):
 
 
 # ---- GPT-2 decoder (modeling/gpt2.py) ----------------------------------------------------------------------------------------
-_GPT2_WS = {}
-
-
-def gpt2_workspace(device, nbytes):
-    """a scratch buffer of at least ``nbytes`` for the skinny GEMM's split-K slabs and the LM head's per-tile partials, one per
-    device, grown on demand (the decode step's launches run in order on one stream, so they can share it)"""
-    key = torch.device(device).index or 0
-    ws = _GPT2_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        _GPT2_WS[key] = ws
-    return ws
-
-
 def skinny_gemm_workspace(M, N, K):
     return int(_L().cddmsl_skinny_gemm_workspace(M, N, K))
 
@@ -1265,7 +1251,7 @@ def skinny_gemm(x, w, bias=None, residual=None, epi=0, out=None):
         out = torch.empty((M, N), device=x.device, dtype=torch.float32 if epi == 1 else torch.bfloat16)
     nb = skinny_gemm_workspace(M, N, K)
     check(0 if nb >= 0 else 1, "cddmsl_skinny_gemm_workspace")
-    ws = gpt2_workspace(x.device, nb)
+    ws = workspace("gpt2", max(nb, 1 << 20), x.device)    # shared with the LM head (one stream, in order); not regrown up to M = 64
     check(_L().cddmsl_skinny_gemm(ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(out), ptr(ws), ws.numel(), M, N, K, epi, stream_ptr()),
           "cddmsl_skinny_gemm")
     return out
@@ -1286,7 +1272,7 @@ def lm_head_argmax(h, wte, ids=None, logits=False):
     lg = torch.empty((M, V), device=h.device, dtype=torch.float32) if logits else None
     nb = int(_L().cddmsl_lm_head_workspace(M, V))
     check(0 if nb >= 0 else 1, "cddmsl_lm_head_workspace")
-    ws = gpt2_workspace(h.device, nb)
+    ws = workspace("gpt2", max(nb, 1 << 20), h.device)
     check(_L().cddmsl_lm_head_argmax(ptr(h), ptr(wte), ptr(ids), ids.stride(0), ptr(lg), ptr(ws), ws.numel(), M, V, K, stream_ptr()),
           "cddmsl_lm_head_argmax")
     return (ids, lg) if logits else ids

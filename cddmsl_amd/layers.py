@@ -1290,11 +1290,6 @@ def causal_attention(qkv, t, heads, scale):
     return hip.attn_causal_fwd(qkv.contiguous(), t, heads, scale)
 
 
-def quick_gelu_(x):
-    """x * sigmoid(1.702 x) in place"""
-    return hip.quick_gelu_(x)
-
-
 def text_pool(x2d, rows, gamma, beta, group=1, out_dtype=torch.float32):
     """ln_final of the rows ``rows`` of the residual stream, averaged over groups of ``group`` consecutive entries"""
     return hip.text_pool(x2d.contiguous(), rows.contiguous(), gamma.detach(), beta.detach(), group, out_dtype)
@@ -1307,11 +1302,6 @@ def skinny_linear(x, w, bias=None, residual=None, gelu=False, out_f32=False, out
     """x [M <= 64, K] bf16 @ w [N, K]^T + bias: bf16 out, gelu_new -> bf16, or f32 out with the f32 residual added"""
     epi = 2 if gelu else (1 if out_f32 or residual is not None else 0)
     return hip.skinny_gemm(x.contiguous(), w, bias, residual, epi, out)
-
-
-def lm_head_argmax(h, wte, ids=None):
-    """greedy next token per row: argmax over the vocabulary of h @ wte^T, lowest index on ties"""
-    return hip.lm_head_argmax(h.contiguous(), wte, ids)
 
 
 def decode_attention(qkv, kc, vc, L, heads, scale, out=None):
@@ -1327,7 +1317,3 @@ def token_position_embed(ids, wte, wpe, pos, out=None):
 def prefix_position_embed(prefix, wpe):
     """prefix [n, P, W] f32 -> [n*P, W] f32 = prefix + wpe[0..P-1]"""
     return hip.pos_embed(wpe, 0, prefix.shape[1], src=prefix.contiguous())
-
-
-def gelu_new_(x):
-    return hip.gelu_new_(x)

@@ -12,14 +12,15 @@ but the linear weights are stored [out, in] (GPT-2's Conv1D stores [in, out]; th
 tied to ``wte``.  The geometry comes from the tensors; heads = n_embd / 64 for every GPT-2 size.
 
 Two paths, as in the text encoder:
-* bf16 throughput path, f32 residual stream.  Prefill (prefix rows): the conv/GEMM kernel, LayerNorm, the causal attention kernel
-  and the gelu_new kernel.  Decode step (one row per caption): skinny GEMM (M <= 64 rows) with bias / residual / gelu_new
+* bf16 throughput path, f32 residual stream.  Prefill (prefix rows): ``causal_stack.prefill`` with gelu_new, which also fills the
+  KV cache.  Decode step (one row per caption): skinny GEMM (M <= 64 rows) with bias / residual / gelu_new
   epilogues, decode attention over the KV cache, ln_f + the LM-head arg-max kernel (the logits are never written).
 * exact-f32 parity path (``compute_dtype=torch.float32``): the f32 GEMM instantiation for every linear, attention and the LM head
   on torch f32 ops (no f32 kernel exists for them).
 """
 import os
 import re
+from functools import partial
 from typing import Dict, Optional
 
 import torch
@@ -27,8 +28,8 @@ from torch import nn
 
 from .. import hip, layers
 from .._lib import require_cuda
+from .causal_stack import HEAD_DIM, FrozenCausalStack, Layer, _Prepared, f32, gemm_weight, prefill
 
-HEAD_DIM = 64
 MAX_ROWS = 64            # decode-step rows per chunk: the skinny GEMM's and the LM head's M bound
 _IGNORED = re.compile(r"^h\.\d+\.attn\.(bias|masked_bias)$")     # the causal-mask buffers older transformers files carry
 
@@ -58,28 +59,7 @@ class _Block(nn.Module):
         self.ln_1, self.attn, self.ln_2, self.mlp = nn.LayerNorm(e), _Attn(e), nn.LayerNorm(e), _Mlp(e)
 
 
-class _Prepared:
-    """device copies: GEMM weights [N, K] in the compute dtype, biases / LayerNorm affines / wpe f32"""
-
-    def __init__(self, dec, dtype):
-        def w(t):
-            t = t.detach().float().contiguous()
-            return hip.weight_prep(t.view(t.shape[0], 1, 1, t.shape[1]), None, dtype, True, False)[0].view(t.shape)
-
-        def f(t):
-            return t.detach().float().contiguous()
-
-        self.wte = w(dec.wte.weight)
-        self.wpe = f(dec.wpe.weight)
-        self.layers = []
-        for b in dec.h:
-            self.layers.append((f(b.ln_1.weight), f(b.ln_1.bias), w(b.attn.c_attn.weight), f(b.attn.c_attn.bias),
-                                w(b.attn.c_proj.weight), f(b.attn.c_proj.bias), f(b.ln_2.weight), f(b.ln_2.bias),
-                                w(b.mlp.c_fc.weight), f(b.mlp.c_fc.bias), w(b.mlp.c_proj.weight), f(b.mlp.c_proj.bias)))
-        self.ln_w, self.ln_b = f(dec.ln_f.weight), f(dec.ln_f.bias)
-
-
-class GPT2Decoder(nn.Module):
+class GPT2Decoder(FrozenCausalStack):
     def __init__(self, n_layer=12, n_embd=768, vocab_size=50257, n_positions=1024, compute_dtype=torch.bfloat16, eps=1e-5):
         super().__init__()
         assert n_embd % HEAD_DIM == 0, n_embd
@@ -92,7 +72,6 @@ class GPT2Decoder(nn.Module):
             p.requires_grad = False
         # decode-step linears: "skinny" (the M <= 64 kernel) or "gemm" (the conv/GEMM kernel, hip.linear_fwd): a measurement switch
         self.decode_linear = os.environ.get("CDDMSL_GPT2_DECODE_LINEAR", "skinny")
-        self._prep = None
 
     @property
     def vocab_size(self):
@@ -140,11 +119,13 @@ class GPT2Decoder(nn.Module):
         dec.load_state_dict(own_sd, strict=True)
         return dec
 
-    def _prepared(self):
-        key = (self.compute_dtype, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if self._prep is None or self._prep[0] != key:
-            self._prep = (key, _Prepared(self, self.compute_dtype))
-        return self._prep[1]
+    def _prepare(self):
+        w, f = partial(gemm_weight, dtype=self.compute_dtype), f32
+        blocks = [Layer(f(b.ln_1.weight), f(b.ln_1.bias), w(b.attn.c_attn.weight), f(b.attn.c_attn.bias),
+                        w(b.attn.c_proj.weight), f(b.attn.c_proj.bias), f(b.ln_2.weight), f(b.ln_2.bias),
+                        w(b.mlp.c_fc.weight), f(b.mlp.c_fc.bias), w(b.mlp.c_proj.weight), f(b.mlp.c_proj.bias))
+                  for b in self.h]
+        return _Prepared(blocks, wte=w(self.wte.weight), wpe=f(self.wpe.weight), ln_w=f(self.ln_f.weight), ln_b=f(self.ln_f.bias))
 
     # ---------------------------------------------------------------- generation
     @torch.no_grad()
@@ -190,27 +171,8 @@ class GPT2Decoder(nn.Module):
         tokens = torch.full((n, max_tokens), -1, device=dev, dtype=torch.int64)
         logits = [] if want_logits else None
 
-        # prefill: the P prefix rows of every sequence
-        x = layers.prefix_position_embed(prefix, Pm.wpe)
-        mask = None
-        for li, (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr) in enumerate(Pm.layers):
-            y = hip.layernorm_fwd(x, ln1w, ln1b, T, self.eps)[0]
-            qkv = hip.linear_fwd(y, wqkv, bias=bqkv)                                  # [n*P, 3E] in T
-            q3 = qkv.view(n, P, 3, E)
-            kc[li, :, :P] = q3[:, :, 1]
-            vc[li, :, :P] = q3[:, :, 2]
-            if T == torch.bfloat16:
-                o = layers.causal_attention(qkv, P, H, scale)
-            else:
-                if mask is None:
-                    mask = torch.full((P, P), float("-inf"), device=dev).triu_(1)
-                q, k, v = q3.view(n, P, 3, H, HEAD_DIM).permute(2, 0, 3, 1, 4)
-                att = torch.softmax((q @ k.transpose(-1, -2)) * scale + mask, dim=-1)
-                o = (att @ v).permute(0, 2, 1, 3).reshape(n * P, E).contiguous()
-            x = hip.linear_fwd(o, wo, bias=bo, residual=x, out_f32=True)
-            y = hip.layernorm_fwd(x, ln2w, ln2b, T, self.eps)[0]
-            h = layers.gelu_new_(hip.linear_fwd(y, wfc, bias=bfc))
-            x = hip.linear_fwd(h, wpr, bias=bpr, residual=x, out_f32=True)
+        # prefill: the P prefix rows of every sequence, their keys and values into the cache
+        x = prefill(Pm.layers, layers.prefix_position_embed(prefix, Pm.wpe), n, P, H, T, hip.gelu_new_, self.eps, kv=(kc, vc))
         x = x.view(n, P, E)[:, P - 1].contiguous()
         self._head(Pm, x, tokens[:, 0], logits)
 
@@ -220,17 +182,17 @@ class GPT2Decoder(nn.Module):
                 break
             L = P + s
             x = layers.token_position_embed(tokens[:, s - 1], Pm.wte, Pm.wpe, L - 1, out=xb)
-            for li, (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr) in enumerate(Pm.layers):
-                y = hip.layernorm_fwd(x, ln1w, ln1b, T, self.eps)[0]
+            for li, B in enumerate(Pm.layers):
+                y = hip.layernorm_fwd(x, B.ln1_w, B.ln1_b, T, self.eps)[0]
                 if T == torch.bfloat16 and self.decode_linear == "skinny":
-                    qkv = layers.skinny_linear(y, wqkv, bqkv)
+                    qkv = layers.skinny_linear(y, B.w_qkv, B.b_qkv)
                     o = layers.decode_attention(qkv, kc[li], vc[li], L, H, scale)
-                    x = layers.skinny_linear(o, wo, bo, residual=x, out=x)
-                    y = hip.layernorm_fwd(x, ln2w, ln2b, T, self.eps)[0]
-                    h = layers.skinny_linear(y, wfc, bfc, gelu=True)
-                    x = layers.skinny_linear(h, wpr, bpr, residual=x, out=x)
+                    x = layers.skinny_linear(o, B.w_out, B.b_out, residual=x, out=x)
+                    y = hip.layernorm_fwd(x, B.ln2_w, B.ln2_b, T, self.eps)[0]
+                    h = layers.skinny_linear(y, B.w_fc, B.b_fc, gelu=True)
+                    x = layers.skinny_linear(h, B.w_proj, B.b_proj, residual=x, out=x)
                     continue
-                qkv = hip.linear_fwd(y, wqkv, bias=bqkv)
+                qkv = hip.linear_fwd(y, B.w_qkv, bias=B.b_qkv)
                 if T == torch.bfloat16:
                     o = layers.decode_attention(qkv, kc[li], vc[li], L, H, scale)
                 else:
@@ -241,10 +203,10 @@ class GPT2Decoder(nn.Module):
                     vv = vc[li, :, :L].view(n, L, H, HEAD_DIM).transpose(1, 2)
                     att = torch.softmax((q3[:, 0].unsqueeze(2) @ kk.transpose(-1, -2)) * scale, dim=-1)   # [n, H, 1, L]
                     o = (att @ vv).reshape(n, E).contiguous()
-                x = hip.linear_fwd(o, wo, bias=bo, residual=x, out_f32=True)
-                y = hip.layernorm_fwd(x, ln2w, ln2b, T, self.eps)[0]
-                h = layers.gelu_new_(hip.linear_fwd(y, wfc, bias=bfc))
-                x = hip.linear_fwd(h, wpr, bias=bpr, residual=x, out_f32=True)
+                x = hip.linear_fwd(o, B.w_out, bias=B.b_out, residual=x, out_f32=True)
+                y = hip.layernorm_fwd(x, B.ln2_w, B.ln2_b, T, self.eps)[0]
+                h = hip.gelu_new_(hip.linear_fwd(y, B.w_fc, bias=B.b_fc))
+                x = hip.linear_fwd(h, B.w_proj, bias=B.b_proj, residual=x, out_f32=True)
             self._head(Pm, x, tokens[:, s], logits)
         return tokens, (torch.stack(logits, dim=1) if want_logits else None)
 

@@ -5,10 +5,8 @@ features over a class's prompts.  Parameter names are the reference's (``token_e
 ``ln_final.*``, ``text_projection``); the geometry comes from the tensors, so RN50 (width 512, 8 heads, 1024 out) and RN50x4
 (640, 10, 640) load alike, from RegionCLIP files (``lang_encoder.*``) or OpenAI CLIP files (top level).
 
-Forward only, two paths like the ClipCap mapper's:
-* bf16 throughput path: f32 residual stream; LayerNorm kernel -> bf16 GEMM operand; in-projection -> bf16 q | k | v; fused causal
-  attention kernel; out-projection and c_proj add the f32 residual in the GEMM epilogue; QuickGELU kernel on the c_fc output;
-* exact-f32 parity path (``compute_dtype=torch.float32``): the f32 GEMM instantiation, attention on torch f32 ops.
+Forward only: the token + positional embedding, the layers on ``causal_stack.prefill`` with QuickGELU (its bf16 throughput path, or
+its exact-f32 parity path with ``compute_dtype=torch.float32``), then ln_final and the projection of the EOT rows.
 
 Truncation.  The mask lets position i attend to keys j <= i only, so no position <= the EOT depends on any later position, and
 the only rows read out (one per sequence, at the EOT) come out the same whether the batch runs at 77 tokens or cut to
@@ -20,6 +18,7 @@ The last layer is run in full: an EOT-rows-only last layer (as the mapper's ``_l
 GEMM work here and was not built.
 """
 import re
+from functools import partial
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -28,8 +27,7 @@ from torch import nn
 from .. import hip, layers
 from .._lib import require_cuda
 from ..clip_text import BPETokenizer, concept_prompts, tokenize_prompts
-
-HEAD_DIM = 64
+from .causal_stack import HEAD_DIM, FrozenCausalStack, Layer, _Prepared, f32, gemm_weight, prefill
 
 
 class _Attn(nn.Module):
@@ -60,29 +58,7 @@ class _Transformer(nn.Module):
         self.resblocks = nn.ModuleList([ResidualAttentionBlock(w) for _ in range(n)])
 
 
-class _Prepared:
-    """device copies in the compute dtype: GEMM weights [N, K], biases / LayerNorm affines f32"""
-
-    def __init__(self, enc, dtype):
-        def w(t):      # f32 master [N, K] -> compute-dtype GEMM operand (cddmsl_weight_prep)
-            t = t.detach().float().contiguous()
-            return hip.weight_prep(t.view(t.shape[0], 1, 1, t.shape[1]), None, dtype, True, False)[0].view(t.shape)
-
-        def f(t):
-            return t.detach().float().contiguous()
-
-        self.tok = w(enc.token_embedding.weight)
-        self.pos = f(enc.positional_embedding)
-        self.layers = []
-        for b in enc.transformer.resblocks:
-            self.layers.append((f(b.ln_1.weight), f(b.ln_1.bias), w(b.attn.in_proj_weight), f(b.attn.in_proj_bias),
-                                w(b.attn.out_proj.weight), f(b.attn.out_proj.bias), f(b.ln_2.weight), f(b.ln_2.bias),
-                                w(b.mlp.c_fc.weight), f(b.mlp.c_fc.bias), w(b.mlp.c_proj.weight), f(b.mlp.c_proj.bias)))
-        self.ln_w, self.ln_b = f(enc.ln_final.weight), f(enc.ln_final.bias)
-        self.proj = w(enc.text_projection.detach().t())         # [D, W]
-
-
-class CLIPTextEncoder(nn.Module):
+class CLIPTextEncoder(FrozenCausalStack):
     def __init__(self, width=512, layers=12, embed_dim=1024, vocab_size=49408, context_length=77, compute_dtype=torch.bfloat16):
         super().__init__()
         assert width % HEAD_DIM == 0, width
@@ -94,7 +70,6 @@ class CLIPTextEncoder(nn.Module):
         self.text_projection = nn.Parameter(torch.empty(width, embed_dim))
         for p in self.parameters():
             p.requires_grad = False
-        self._prep = None
 
     # ---------------------------------------------------------------- construction / loading
     @staticmethod
@@ -131,11 +106,14 @@ class CLIPTextEncoder(nn.Module):
         enc.matched = pairs
         return enc
 
-    def _prepared(self):
-        key = (self.compute_dtype, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if self._prep is None or self._prep[0] != key:
-            self._prep = (key, _Prepared(self, self.compute_dtype))
-        return self._prep[1]
+    def _prepare(self):
+        w, f = partial(gemm_weight, dtype=self.compute_dtype), f32
+        blocks = [Layer(f(b.ln_1.weight), f(b.ln_1.bias), w(b.attn.in_proj_weight), f(b.attn.in_proj_bias),
+                        w(b.attn.out_proj.weight), f(b.attn.out_proj.bias), f(b.ln_2.weight), f(b.ln_2.bias),
+                        w(b.mlp.c_fc.weight), f(b.mlp.c_fc.bias), w(b.mlp.c_proj.weight), f(b.mlp.c_proj.bias))
+                  for b in self.transformer.resblocks]
+        return _Prepared(blocks, tok=w(self.token_embedding.weight), pos=f(self.positional_embedding), ln_w=f(self.ln_final.weight),
+                         ln_b=f(self.ln_final.bias), proj=w(self.text_projection.detach().t()))         # proj [D, W]
 
     # ---------------------------------------------------------------- forward
     def _check_ids(self, ids):
@@ -169,29 +147,9 @@ class CLIPTextEncoder(nn.Module):
 
     def _residual_stream(self, ids):
         """ids [n, t] on the device -> the residual stream after the last block, [n*t, W] f32"""
-        T = self.compute_dtype
         P = self._prepared()
         n, t = ids.shape
-        H, scale = self.heads, HEAD_DIM ** -0.5
-        x = layers.text_embed(ids, P.tok, P.pos)
-        mask = None
-        for ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr in P.layers:
-            y = hip.layernorm_fwd(x, ln1w, ln1b, T)[0]
-            qkv = hip.linear_fwd(y, wqkv, bias=bqkv)                                   # [n*t, 3W] in T
-            if T == torch.bfloat16:
-                o = layers.causal_attention(qkv, t, H, scale)
-            else:
-                # exact-f32 parity path: the same arithmetic on torch ops (the fused kernel is bf16-only)
-                if mask is None:
-                    mask = torch.full((t, t), float("-inf"), device=x.device).triu_(1)
-                q, k, v = qkv.view(n, t, 3, H, HEAD_DIM).permute(2, 0, 3, 1, 4)
-                att = torch.softmax((q @ k.transpose(-1, -2)) * scale + mask, dim=-1)
-                o = (att @ v).permute(0, 2, 1, 3).reshape(n * t, self.width).contiguous()
-            x = hip.linear_fwd(o, wo, bias=bo, residual=x, out_f32=True)               # x + out_proj(o): residual in the epilogue
-            y = hip.layernorm_fwd(x, ln2w, ln2b, T)[0]
-            h = layers.quick_gelu_(hip.linear_fwd(y, wfc, bias=bfc))                   # [n*t, 4W] in T
-            x = hip.linear_fwd(h, wpr, bias=bpr, residual=x, out_f32=True)
-        return x
+        return prefill(P.layers, layers.text_embed(ids, P.tok, P.pos), n, t, self.heads, self.compute_dtype, hip.quick_gelu_)
 
     def encode_prompt_ids(self, ids, counts: Sequence[int], chunk=8192, truncate=True):
         """ids [S, 77] int64 (CPU), the prompts of class c being ``counts[c]`` consecutive rows -> [C, D] f32, the mean over each

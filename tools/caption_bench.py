@@ -34,10 +34,11 @@ def timed(fn, reps):
 def kernel_rates(dec, reps=200):
     from cddmsl_amd import hip
     P = dec._prepared()
-    _, _, wqkv, bqkv, wo, bo, _, _, wfc, bfc, wpr, bpr = P.layers[0]
+    B = P.layers[0]
     rows = []
     for M in (1, 16, 64):
-        for name, w, b in (("c_attn", wqkv, bqkv), ("attn.c_proj", wo, bo), ("c_fc", wfc, bfc), ("mlp.c_proj", wpr, bpr)):
+        for name, w, b in (("c_attn", B.w_qkv, B.b_qkv), ("attn.c_proj", B.w_out, B.b_out), ("c_fc", B.w_fc, B.b_fc),
+                           ("mlp.c_proj", B.w_proj, B.b_proj)):
             x = torch.randn(M, w.shape[1], device=w.device).to(torch.bfloat16)
             t = timed(lambda: hip.skinny_gemm(x, w, b, epi=0), reps)
             tg = timed(lambda: hip.linear_fwd(x, w, bias=b), reps)
