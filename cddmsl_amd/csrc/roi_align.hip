@@ -258,7 +258,9 @@ __global__ __launch_bounds__(256) void k_roi_align_fwd_rows(const char* x, const
   const int opw = pw / RP;                                     // outputs per row
   const int c = threadIdx.x;                                   // channel chunk of this lane
   const bool inb = g.b >= 0 && g.b < N;
-  if (nx > ROI_MAXS || 2 * ny > ROW_MAXY) {                    // a sampling grid beyond the tables (block-uniform): bins evaluated tap by tap
+  // a sampling grid beyond the tables, or an inverted box (x1 < x0: its x samples DESCEND along the row, or its adaptive grid is negative),
+  // which the sliding window below cannot walk (block-uniform): bins evaluated tap by tap
+  if (nx > ROI_MAXS || 2 * ny > ROW_MAXY || g.bw < 0.f) {
     if (c >= cch) return;
     const u32x4* xb = (const u32x4*)x + (long)(inb ? g.b : 0) * H * W * cch + c;
     const float inv = 1.0f / ((float)max(g.gh * g.gw, 1) * (float)(RP * RP));
