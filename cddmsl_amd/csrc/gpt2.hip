@@ -9,6 +9,10 @@
 //                  (max, index) per row, then one reduction launch per row.  Optional f32 logits for tests.
 //   decode_attn    one query row per (sequence, head) against a KV cache of positions 0..L-2 plus this step's own key / value, which
 //                  it appends to the cache at position L-1 (the cache is never copied).
+//   lm_head_topk   the row's B best (logit, index) pairs in the arg-max's order and its log-sum-exp, for beam search
+//   beam_step      length-normalised beam selection, one wave per caption; permutes the token history and the cache ancestry table
+//   decode_attn_beam  decode_attn over a prefix cache shared by a caption's beams and a generated cache read through the ancestry
+//                  table: beams change owner every step and no cache row is ever copied
 //   pos_embed      x[r] = (tab[ids[r]] or src[r]) + wpe[pos0 + r % t]: the decode step's token + position, the prefill's prefix +
 //                  position, and the CLIP text encoder's token + position (text_embed: contiguous ids, pos0 = 0).
 // The prefill's in-place gelu_new runs on text_encoder.hip's activation kernel.
@@ -212,6 +216,186 @@ __global__ __launch_bounds__(256) void k_lm_head_final(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// LM head top-B with log-normaliser (beam search).  The per-tile candidates are merged through the logits buffer: the LM-head tile
+// writes the f32 logits [M][V] (the caller's, or workspace), then one 512-thread workgroup per row reads its row twice.  Pass 1: thread
+// t walks columns t, t + 512, .. in ascending order and keeps its 8 best under better() sorted in registers; B rounds of "best head
+// over the workgroup, its owner pops" emit the row's top B.  better() is a total order, so the result is the row's top B whatever the
+// tree.  Pass 2: logZ = m + log(sum_j exp(l_j - m)), m = the row maximum: per thread in ascending column order, the 64 lanes by the
+// xor butterfly, the 8 waves in wave order -- fixed by V alone.  A row's outputs depend on its own logits only, and those do not depend
+// on M (tile_dot), so they are bitwise independent of M and of the other rows.  No atomics.
+constexpr int TK_MAXB = 8;
+constexpr int TK_THREADS = 512;
+
+template <int MT>
+__global__ __launch_bounds__(256) void k_lm_head_logits(const char* __restrict__ h, const char* __restrict__ wte, float* __restrict__ logits,
+                                                        int M, int V, int K) {
+  __shared__ float red[3 * MT * 16 * 64];
+  const int n0 = blockIdx.x * 32;
+  f32x16 acc[MT];
+  tile_dot<MT>(h, wte, M, V, K, n0, 0, K / 64, acc, red);
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x, c = lane & 31, hh = lane >> 5, n = n0 + c;
+  if (n >= V) return;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      const int m = mt * 32 + crow(g, hh);
+      if (m < M) logits[(long)m * V + n] = acc[mt][g];
+    }
+}
+
+__global__ __launch_bounds__(TK_THREADS) void k_lm_head_topk(const float* __restrict__ logits, float* __restrict__ vals, int* __restrict__ idx,
+                                                             float* __restrict__ logZ, int V, int B) {
+  __shared__ float sv[TK_THREADS / 64];
+  __shared__ int si[TK_THREADS / 64];
+  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float* row = logits + (long)m * V;
+  float tv[TK_MAXB];
+  int ti[TK_MAXB];
+#pragma unroll
+  for (int q = 0; q < TK_MAXB; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
+  for (int j0 = tid; j0 < V; j0 += 8 * TK_THREADS) {           // eight loads in flight, then the inserts in ascending column order
+    float x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { const int j = j0 + u * TK_THREADS; x[u] = j < V ? row[j] : -INFINITY; }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int j = j0 + u * TK_THREADS;
+      if (j < V && better(x[u], j, tv[TK_MAXB - 1], ti[TK_MAXB - 1])) {
+        tv[TK_MAXB - 1] = x[u];
+        ti[TK_MAXB - 1] = j;
+#pragma unroll
+        for (int q = TK_MAXB - 1; q > 0; --q)
+          if (better(tv[q], ti[q], tv[q - 1], ti[q - 1])) {
+            const float a = tv[q]; tv[q] = tv[q - 1]; tv[q - 1] = a;
+            const int ia = ti[q]; ti[q] = ti[q - 1]; ti[q - 1] = ia;
+          }
+      }
+    }
+  }
+  float mx = -INFINITY;
+  for (int r = 0; r < B; ++r) {
+    float v = tv[0];
+    int iv = ti[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(v, o, 64);
+      const int oi = __shfl_xor(iv, o, 64);
+      if (better(ov, oi, v, iv)) { v = ov; iv = oi; }
+    }
+    if (lane == 0) { sv[wv] = v; si[wv] = iv; }
+    __syncthreads();
+    v = sv[0];
+    iv = si[0];
+#pragma unroll
+    for (int q = 1; q < TK_THREADS / 64; ++q)
+      if (better(sv[q], si[q], v, iv)) { v = sv[q]; iv = si[q]; }
+    __syncthreads();                                   // every thread has read sv / si before the next round writes them
+    if (tid == 0) { vals[(long)m * B + r] = v; idx[(long)m * B + r] = iv == 0x7fffffff ? 0 : iv; }   // (NaN rows: index 0)
+    if (r == 0) mx = v;
+    if (iv == ti[0]) {                                 // the owner pops (column indices are unique)
+#pragma unroll
+      for (int q = 0; q < TK_MAXB - 1; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
+      tv[TK_MAXB - 1] = -INFINITY;
+      ti[TK_MAXB - 1] = 0x7fffffff;
+    }
+  }
+  float sum = 0.f;
+  for (int j0 = tid; j0 < V; j0 += 8 * TK_THREADS) {
+    float x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { const int j = j0 + u * TK_THREADS; x[u] = j < V ? row[j] : -INFINITY; }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (j0 + u * TK_THREADS < V) sum += expf(x[u] - mx);
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) sv[wv] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    float a = sv[0];
+    for (int q = 1; q < TK_THREADS / 64; ++q) a += sv[q];
+    logZ[m] = mx + logf(a);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Beam selection, one wave per caption.  Lane (b = lane / B, k = lane % B) holds the k-th best token of beam b: logp = logit - logZ_b,
+// cand_sum = sum_b + logp, cand_len = len_b + 1, key = cand_sum / cand_len (IEEE division), all f32 in this order.  A stopped beam
+// offers itself once (lane k = 0: its own sum and length, token column 0).  A candidate's rank is the number of candidates that beat
+// it: larger key, then lower (beam, token) -- a total order, so ranks 0..B-1 each have one owner.  New beam j takes rank j: its
+// source's history and ancestry (old tables read, new tables written), the token unless the source was stopped, and for the cache
+// the source's slot as the owner of the step just run.  step == 0: one row per caption, beam j takes the row's j-th (value, index).
+__global__ __launch_bounds__(64) void k_beam_step(const float* __restrict__ vals, const int* __restrict__ idx, const float* __restrict__ logZ,
+                                                  const float* __restrict__ sum_in, const int* __restrict__ len_in,
+                                                  const unsigned char* __restrict__ stop_in, const int* __restrict__ hist_in,
+                                                  const unsigned char* __restrict__ anc_in, float* __restrict__ sum_out,
+                                                  int* __restrict__ len_out, unsigned char* __restrict__ stop_out, int* __restrict__ hist_out,
+                                                  unsigned char* __restrict__ anc_out, int* __restrict__ src, long* __restrict__ next_tok,
+                                                  int B, int T, int step, int stop_id) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  const int b = lane / B, k = lane - b * B;
+  int valid = 0, v = 0, clen = 0, sstop = 0, rank = 0;
+  float csum = 0.f, key = 0.f;
+  if (step == 0) {
+    valid = lane < B;
+    if (valid) {
+      v = idx[(long)c * B + k];
+      csum = vals[(long)c * B + k] - logZ[c];
+      clen = 1;
+    }
+    rank = k;
+  } else {
+    valid = lane < B * B;
+    if (valid) {
+      const long row = (long)c * B + b;
+      sstop = stop_in[row] != 0;
+      const float s = sum_in[row];
+      const int l = len_in[row];
+      if (sstop) {
+        valid = k == 0;
+        csum = s;
+        clen = l;
+      } else {
+        v = idx[row * B + k];
+        const float logp = vals[row * B + k] - logZ[row];
+        csum = s + logp;
+        clen = l + 1;
+      }
+      key = __fdiv_rn(csum, (float)clen);
+    }
+    for (int l2 = 0; l2 < B * B; ++l2) {
+      const int ok2 = __shfl(valid, l2, 64), v2 = __shfl(v, l2, 64);
+      const float key2 = __shfl(key, l2, 64);
+      const int b2 = l2 / B;
+      rank += ok2 && (key2 > key || (key2 == key && (b2 < b || (b2 == b && v2 < v))));
+    }
+  }
+  const int ld = T - 1;
+  for (int j = 0; j < B; ++j) {
+    const unsigned long long owners = __ballot(valid && rank == j);
+    if (!owners) continue;                              // (NaN keys only: ranks collide)
+    const int w = __ffsll((long long)owners) - 1;
+    const int sb = __shfl(b, w, 64), tok = __shfl(v, w, 64), was = __shfl(sstop, w, 64), nl = __shfl(clen, w, 64);
+    const float ns = __shfl(csum, w, 64);
+    const long nr = (long)c * B + j, sr = (long)c * B + sb;
+    for (int t = lane; t < step; t += 64) hist_out[nr * T + t] = hist_in[sr * T + t];
+    for (int t = lane; t < step - 1; t += 64) anc_out[nr * ld + t] = anc_in[sr * ld + t];
+    if (lane == 0) {
+      const int stopped = was || tok == stop_id;
+      sum_out[nr] = ns;
+      len_out[nr] = nl;
+      stop_out[nr] = (unsigned char)stopped;
+      src[nr] = sb;
+      next_tok[nr] = stopped ? stop_id : tok;
+      hist_out[nr * T + step] = was ? -1 : tok;
+      if (step >= 1) anc_out[nr * ld + step - 1] = (unsigned char)sb;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Decode attention.  One 256-thread workgroup per (sequence s, head h); head dim 64.  qkv row s = c_attn's output of this step
 // (q | k | v column blocks of W = heads * 64).  Keys / values of positions j < L - 1 come from the cache kc / vc [nseq][Lmax][W], the
 // key / value of position L - 1 from qkv itself; the workgroup also writes them to the cache at L - 1 for the next steps.
@@ -224,8 +408,34 @@ __device__ __forceinline__ void row8(const unsigned short* p, float (&v)[8]) {
   for (int e = 0; e < 4; ++e) { v[2 * e] = bf2f(u[e] & 0xffff); v[2 * e + 1] = bf2f(u[e] >> 16); }
 }
 
+// Beam search (BEAM): row s = caption * B + beam.  Positions j < P come from the caption's prefix cache pk / pv [captions][P][W], which its
+// beams share; positions P <= j < L - 1 from the generated cache kc / vc [rows][Lmax][W] at row caption * B + anc[s][j - P], position
+// j - P, where anc [rows][ldanc] names the beam slot that wrote step j - P of this beam's history (k_beam_step keeps it); position L - 1
+// from qkv, written to the generated cache at row s, position L - 1 - P.  No cache row ever moves.  The arithmetic and its order are
+// the same in both instantiations.
+struct BeamKV {
+  const unsigned short* pk;
+  const unsigned short* pv;
+  const unsigned char* anc;
+  int B, P, ldanc;
+};
+
+template <bool BEAM>
+__device__ __forceinline__ const unsigned short* kv_row(const unsigned short* cache, const unsigned short* pre, const BeamKV& bm, int s,
+                                                        int j, int Lmax, int W) {
+  if constexpr (!BEAM) return cache + ((long)s * Lmax + j) * W;
+  const int cap = s / bm.B;
+  if (j < bm.P) return pre + ((long)cap * bm.P + j) * W;
+  const int t = j - bm.P;
+  int a = bm.anc[(long)s * bm.ldanc + t];
+  a = a < bm.B ? a : bm.B - 1;                       // (memory safety only: k_beam_step writes slots < B)
+  return cache + ((long)(cap * bm.B + a) * Lmax + t) * W;
+}
+
+template <bool BEAM>
 __global__ __launch_bounds__(256) void k_decode_attn(const unsigned short* __restrict__ qkv, unsigned short* kc, unsigned short* vc,
-                                                     unsigned short* __restrict__ o, int heads, int L, int Lmax, int ldqkv, float scale) {
+                                                     unsigned short* __restrict__ o, int heads, int L, int Lmax, int ldqkv, float scale,
+                                                     BeamKV bm) {
   __shared__ float q[64];
   __shared__ float sc[DA_MAXL];
   __shared__ float red[32 * 64];
@@ -236,14 +446,14 @@ __global__ __launch_bounds__(256) void k_decode_attn(const unsigned short* __res
   const unsigned short* qr = qkv + (long)s * ldqkv + h * 64;
   const unsigned short* knew = qr + W;
   const unsigned short* vnew = qr + 2 * W;
-  const long cbase = (long)s * Lmax * W + h * 64;
+  const long wbase = ((long)s * Lmax + (BEAM ? L - 1 - bm.P : L - 1)) * W + h * 64;      // where this step's key / value go
   if (tid < 64) q[tid] = bf2f(qr[tid]);
-  else if (tid < 72) ((u32x4*)(kc + cbase + (long)(L - 1) * W))[tid - 64] = ((const u32x4*)knew)[tid - 64];
-  else if (tid < 80) ((u32x4*)(vc + cbase + (long)(L - 1) * W))[tid - 72] = ((const u32x4*)vnew)[tid - 72];
+  else if (tid < 72) ((u32x4*)(kc + wbase))[tid - 64] = ((const u32x4*)knew)[tid - 64];
+  else if (tid < 80) ((u32x4*)(vc + wbase))[tid - 72] = ((const u32x4*)vnew)[tid - 72];
   __syncthreads();
   float m = -INFINITY;
   for (int j = tid; j < L; j += 256) {
-    const unsigned short* kr = j == L - 1 ? knew : kc + cbase + (long)j * W;
+    const unsigned short* kr = j == L - 1 ? knew : kv_row<BEAM>(kc, bm.pk, bm, s, j, Lmax, W) + h * 64;
     float d = 0.f;
 #pragma unroll
     for (int c8 = 0; c8 < 8; ++c8) {
@@ -272,7 +482,7 @@ __global__ __launch_bounds__(256) void k_decode_attn(const unsigned short* __res
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
   for (int j = grp; j < L; j += 32) {
-    const unsigned short* vr = j == L - 1 ? vnew : vc + cbase + (long)j * W;
+    const unsigned short* vr = j == L - 1 ? vnew : kv_row<BEAM>(vc, bm.pv, bm, s, j, Lmax, W) + h * 64;
     float vv[8];
     row8(vr + c8 * 8, vv);
     const float p = sc[j];
@@ -387,8 +597,58 @@ extern "C" int cddmsl_decode_attn(const void* qkv, void* kc, void* vc, void* o, 
   if (nseq == 0) return CDDMSL_OK;
   const long wgs = (long)nseq * heads;
   if (wgs > 0x7fffffffL) return CDDMSL_ERR_ARG;
-  hipLaunchKernelGGL(k_decode_attn, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)qkv, (unsigned short*)kc,
-                     (unsigned short*)vc, (unsigned short*)o, heads, L, Lmax, ldqkv, scale);
+  hipLaunchKernelGGL(k_decode_attn<false>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)qkv,
+                     (unsigned short*)kc, (unsigned short*)vc, (unsigned short*)o, heads, L, Lmax, ldqkv, scale, BeamKV{});
+  return launch_status();
+}
+
+extern "C" int cddmsl_lm_head_topk_workspace(int M, int V) {
+  if (M < 1 || M > SK_MAXM || V <= 0 || V > (1 << 22)) return -1;
+  return M * V * 4;
+}
+
+extern "C" int cddmsl_lm_head_topk(const void* h, const void* wte, float* vals, int* idx, float* logZ, float* logits, void* ws, long ws_bytes,
+                                   int M, int V, int K, int B, void* stream) {
+  if (M < 1 || M > SK_MAXM || V <= 0 || V > (1 << 22) || K <= 0 || (K & 63) || B < 1 || B > TK_MAXB || B > V) return CDDMSL_ERR_ARG;
+  if (!al16(h) || !al16(wte) || !vals || !idx || !logZ) return CDDMSL_ERR_ARG;
+  if (!logits) {
+    if (!ws || ws_bytes < (long)M * V * 4) return CDDMSL_ERR_ARG;
+    logits = (float*)ws;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const int tiles = (V + 31) / 32;
+  if (M <= 32) hipLaunchKernelGGL(k_lm_head_logits<1>, dim3(tiles), dim3(256), 0, st, (const char*)h, (const char*)wte, logits, M, V, K);
+  else hipLaunchKernelGGL(k_lm_head_logits<2>, dim3(tiles), dim3(256), 0, st, (const char*)h, (const char*)wte, logits, M, V, K);
+  hipLaunchKernelGGL(k_lm_head_topk, dim3(M), dim3(TK_THREADS), 0, st, (const float*)logits, vals, idx, logZ, V, B);
+  return launch_status();
+}
+
+extern "C" int cddmsl_beam_step(const float* vals, const int* idx, const float* logZ, const float* sum_in, const int* len_in,
+                                const unsigned char* stop_in, const int* hist_in, const unsigned char* anc_in, float* sum_out, int* len_out,
+                                unsigned char* stop_out, int* hist_out, unsigned char* anc_out, int* src, long* next_tok, int n, int B, int T,
+                                int step, int stop_id, void* stream) {
+  if (n < 0 || B < 1 || B > TK_MAXB || T < 1 || step < 0 || step >= T || stop_id < -1) return CDDMSL_ERR_ARG;
+  if (!vals || !idx || !logZ || !sum_out || !len_out || !stop_out || !hist_out || !src || !next_tok) return CDDMSL_ERR_ARG;
+  if (step >= 1 && (!sum_in || !len_in || !stop_in || !hist_in || !anc_in || !anc_out)) return CDDMSL_ERR_ARG;
+  if (n == 0) return CDDMSL_OK;
+  hipLaunchKernelGGL(k_beam_step, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, vals, idx, logZ, sum_in, len_in, stop_in, hist_in, anc_in,
+                     sum_out, len_out, stop_out, hist_out, anc_out, src, next_tok, B, T, step, stop_id);
+  return launch_status();
+}
+
+extern "C" int cddmsl_decode_attn_beam(const void* qkv, const void* pk, const void* pv, void* gk, void* gv, const unsigned char* anc, void* o,
+                                       int rows, int B, int heads, int dh, int P, int L, int Tg, int ldanc, int ldqkv, float scale, int dtype,
+                                       void* stream) {
+  if (dtype != 0 || dh != 64 || rows < 0 || B < 1 || B > TK_MAXB || rows % B || heads <= 0 || P < 0 || L < P + 1 || L - P > Tg ||
+      L > DA_MAXL || ldanc < L - 1 - P || (ldqkv & 7) || ldqkv < 3 * heads * 64)
+    return CDDMSL_ERR_ARG;
+  if (!al16(qkv) || !al16(pk) || !al16(pv) || !al16(gk) || !al16(gv) || !al16(o) || (L - 1 - P > 0 && !anc)) return CDDMSL_ERR_ARG;
+  if (rows == 0) return CDDMSL_OK;
+  const long wgs = (long)rows * heads;
+  if (wgs > 0x7fffffffL) return CDDMSL_ERR_ARG;
+  const BeamKV bm{(const unsigned short*)pk, (const unsigned short*)pv, anc, B, P, ldanc};
+  hipLaunchKernelGGL(k_decode_attn<true>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)qkv,
+                     (unsigned short*)gk, (unsigned short*)gv, (unsigned short*)o, heads, L, Tg, ldqkv, scale, bm);
   return launch_status();
 }
 

@@ -97,6 +97,10 @@ def _L():
         L.cddmsl_decode_attn.argtypes = [vp] * 4 + [ci] * 6 + [cf, ci, vp]
         L.cddmsl_pos_embed.argtypes = [vp, ci] + [vp] * 4 + [c_long] + [ci] * 6 + [vp]
         L.cddmsl_gelu_new.argtypes = [vp, c_long, ci, vp]
+        L.cddmsl_lm_head_topk_workspace.argtypes = [ci, ci]
+        L.cddmsl_lm_head_topk.argtypes = [vp] * 7 + [c_long] + [ci] * 4 + [vp]
+        L.cddmsl_beam_step.argtypes = [vp] * 15 + [ci] * 5 + [vp]
+        L.cddmsl_decode_attn_beam.argtypes = [vp] * 7 + [ci] * 9 + [cf, ci, vp]
         _sigs_done = True
     return L
 
@@ -1310,6 +1314,87 @@ def pos_embed(wpe, pos0, t, ids=None, tab=None, src=None, out=None):
         out = torch.empty((rows, W), device=wpe.device, dtype=torch.float32)
     check(_L().cddmsl_pos_embed(ptr(ids), max(ld, 1), ptr(tab), ptr(src), ptr(wpe), ptr(out), rows, t, pos0, W, vocab, wpe.shape[0], dt,
                                 stream_ptr()), "cddmsl_pos_embed")
+    return out
+
+
+@_timed("lm_head_topk")
+def lm_head_topk(h, wte, B, logits=False):
+    """h [M, K] bf16 (M <= 64), wte [V, K] bf16 -> (vals [M, B] f32, idx [M, B] int32, logZ [M] f32[, logits [M, V] f32]): per row
+    the B largest logits of h @ wte^T, larger value first and lower index among equal values, and the row's log-sum-exp"""
+    require_cuda(h, wte)
+    assert h.dtype == torch.bfloat16 and wte.dtype == torch.bfloat16 and h.is_contiguous() and wte.is_contiguous() and h.dim() == 2
+    M, K = h.shape
+    V = wte.shape[0]
+    assert wte.shape[1] == K
+    vals = torch.empty((M, max(B, 0)), device=h.device, dtype=torch.float32)
+    idx = torch.empty((M, max(B, 0)), device=h.device, dtype=torch.int32)
+    logZ = torch.empty(M, device=h.device, dtype=torch.float32)
+    lg, ws = None, None
+    if logits:
+        lg = torch.empty((M, V), device=h.device, dtype=torch.float32)
+    else:
+        nb = int(_L().cddmsl_lm_head_topk_workspace(M, V))
+        check(0 if nb >= 0 else 1, "cddmsl_lm_head_topk_workspace")
+        ws = workspace("gpt2_topk", nb, h.device)
+    check(_L().cddmsl_lm_head_topk(ptr(h), ptr(wte), ptr(vals), ptr(idx), ptr(logZ), ptr(lg), ptr(ws), 0 if ws is None else ws.numel(),
+                                   M, V, K, B, stream_ptr()), "cddmsl_lm_head_topk")
+    return (vals, idx, logZ, lg) if logits else (vals, idx, logZ)
+
+
+class BeamState:
+    """the per-beam tables of one chunk of captions, as ``beam_step`` reads and writes them: sum [n, B] f32, len [n, B] int32,
+    stop [n, B] uint8, hist [n, B, T] int32 (-1 past a beam's length), anc [n * B, T - 1] uint8 (which beam slot wrote step t of the
+    beam's cache history), and of the last step src [n, B] int32 and next_tok [n * B] int64"""
+
+    def __init__(self, n, B, T, device):
+        self.n, self.B, self.T = n, B, T
+        self.sum = torch.zeros((n, B), device=device, dtype=torch.float32)
+        self.len = torch.zeros((n, B), device=device, dtype=torch.int32)
+        self.stop = torch.zeros((n, B), device=device, dtype=torch.uint8)
+        self.hist = torch.full((n, B, T), -1, device=device, dtype=torch.int32)
+        self.anc = torch.zeros((n * B, max(T - 1, 1)), device=device, dtype=torch.uint8)[:, :T - 1]
+        self.src = torch.zeros((n, B), device=device, dtype=torch.int32)
+        self.next_tok = torch.zeros(n * B, device=device, dtype=torch.int64)
+
+
+@_timed("beam_step")
+def beam_step(vals, idx, logZ, old, new, step, stop_id=None):
+    """one beam-selection step: reads the rows' top-B ``vals`` / ``idx`` / ``logZ`` (``lm_head_topk``) and the BeamState ``old``,
+    writes the BeamState ``new`` (a distinct object: every permuted table is double-buffered).  ``step`` = tokens already in the
+    history; step 0 takes one row per caption and ignores ``old``'s contents."""
+    n, B, T = new.n, new.B, new.T
+    require_cuda(vals, idx, logZ, old.sum, new.sum)
+    rows = n if step == 0 else n * B
+    assert old is not new and (old.n, old.B, old.T) == (n, B, T)
+    assert vals.dtype == torch.float32 and idx.dtype == torch.int32 and logZ.dtype == torch.float32
+    assert vals.is_contiguous() and idx.is_contiguous() and logZ.is_contiguous()
+    assert tuple(vals.shape) == tuple(idx.shape) == (rows, B) and logZ.numel() == rows
+    anc_in, anc_out = (old.anc, new.anc) if T > 1 else (None, None)
+    assert anc_in is None or (anc_in.stride(0) == max(T - 1, 1) and anc_out.stride(0) == max(T - 1, 1))
+    check(_L().cddmsl_beam_step(ptr(vals), ptr(idx), ptr(logZ), ptr(old.sum), ptr(old.len), ptr(old.stop), ptr(old.hist), ptr(anc_in),
+                                ptr(new.sum), ptr(new.len), ptr(new.stop), ptr(new.hist), ptr(anc_out), ptr(new.src), ptr(new.next_tok),
+                                n, B, T, step, -1 if stop_id is None else int(stop_id), stream_ptr()), "cddmsl_beam_step")
+    return new
+
+
+@_timed("decode_attn_beam")
+def decode_attn_beam(qkv, pk, pv, gk, gv, anc, L, B, heads, scale, out=None):
+    """qkv [rows, >= 3W] bf16 (row = caption * B + beam), prefix caches pk / pv [rows / B, P, W] bf16 shared by a caption's beams,
+    generated caches gk / gv [rows, Tg, W] bf16 read through anc [rows, >= L - 1 - P] uint8 (row stride anc.stride(0)) -> o [rows, W]
+    bf16; writes this step's keys / values to position L - 1 - P of row r of the generated caches"""
+    require_cuda(qkv, pk, pv, gk, gv, anc, out)
+    rows, Tg, W = gk.shape
+    ncap, P, _ = pk.shape
+    assert qkv.dtype == pk.dtype == pv.dtype == gk.dtype == gv.dtype == torch.bfloat16 and anc.dtype == torch.uint8
+    assert pk.is_contiguous() and pv.is_contiguous() and gk.is_contiguous() and gv.is_contiguous()
+    assert pv.shape == pk.shape and gv.shape == gk.shape and pk.shape[2] == W and W == heads * 64 and (rows % B or ncap * B == rows)
+    assert qkv.dim() == 2 and qkv.shape[0] == rows and qkv.stride(1) == 1 and qkv.shape[1] >= 3 * W
+    assert anc.dim() == 2 and anc.shape[0] == rows and anc.shape[1] >= L - 1 - P and (anc.shape[1] == 0 or anc.stride(1) == 1)
+    ldanc = anc.stride(0) if anc.shape[1] else 0
+    if out is None:
+        out = torch.empty((rows, W), device=qkv.device, dtype=torch.bfloat16)
+    check(_L().cddmsl_decode_attn_beam(ptr(qkv), ptr(pk), ptr(pv), ptr(gk), ptr(gv), ptr(anc if anc.shape[1] else None), ptr(out), rows, B,
+                                       heads, 64, P, L, Tg, ldanc, qkv.stride(0), float(scale), 0, stream_ptr()), "cddmsl_decode_attn_beam")
     return out
 
 

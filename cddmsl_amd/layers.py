@@ -1309,6 +1309,11 @@ def decode_attention(qkv, kc, vc, L, heads, scale, out=None):
     return hip.decode_attn(qkv, kc, vc, L, heads, scale, out)
 
 
+def decode_attention_beam(qkv, pk, pv, gk, gv, anc, L, beams, heads, scale, out=None):
+    """decode_attention for beam search: the prefix cache is per caption, the generated cache is read through the ancestry table"""
+    return hip.decode_attn_beam(qkv, pk, pv, gk, gv, anc, L, beams, heads, scale, out)
+
+
 def token_position_embed(ids, wte, wpe, pos, out=None):
     """x [n, W] f32 = wte[ids] + wpe[pos]"""
     return hip.pos_embed(wpe, pos, 1, ids=ids, tab=wte, out=out)

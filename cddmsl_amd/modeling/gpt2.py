@@ -11,12 +11,23 @@ Parameters follow GPT-2's names (``wte``, ``wpe``, ``h.{i}.{ln_1, attn.c_attn, a
 but the linear weights are stored [out, in] (GPT-2's Conv1D stores [in, out]; they are transposed once at load).  The LM head is
 tied to ``wte``.  The geometry comes from the tensors; heads = n_embd / 64 for every GPT-2 size.
 
+Beam search.  ClipCap's other decoding mode (``inference(prefix, use_beam_search=True)``, clipcap.py:196-205; the reference names
+``generate_beam`` there and defines it nowhere) is ``generate_beam``: length-normalised beam search of width B <= 8.  Every live
+beam offers the B largest logits of its row (within a beam the key is monotone in the logit, so these are all it can contribute), a
+stopped beam offers itself; the B candidates with the largest ``sum of log-probabilities / length`` survive, ties to the lower
+(beam, token).  The prefix is prefilled once per caption and shared by its beams; the cache of the generated positions is never
+reordered: an ancestry table [rows, T - 1] says which beam slot wrote each step of a beam's history, the selection kernel permutes
+that table (and the token history) instead of the cache, and the attention kernel reads keys and values through it.
+``torch_beam`` restates the semantics with a full recompute on torch ops.
+
 Two paths, as in the text encoder:
 * bf16 throughput path, f32 residual stream.  Prefill (prefix rows): ``causal_stack.prefill`` with gelu_new, which also fills the
   KV cache.  Decode step (one row per caption): skinny GEMM (M <= 64 rows) with bias / residual / gelu_new
-  epilogues, decode attention over the KV cache, ln_f + the LM-head arg-max kernel (the logits are never written).
+  epilogues, decode attention over the KV cache, ln_f + the LM-head arg-max kernel (the logits are never written).  Beam search:
+  the same step on captions x B rows with ``decode_attention_beam``, the LM-head top-B + log-sum-exp kernel and ``beam_step``.
 * exact-f32 parity path (``compute_dtype=torch.float32``): the f32 GEMM instantiation for every linear, attention and the LM head
-  on torch f32 ops (no f32 kernel exists for them).
+  on torch f32 ops (no f32 kernel exists for them); beam search gathers its caches through the same ancestry table, takes the top B
+  by a stable descending sort and selects with the same ``beam_step`` kernel.
 """
 import os
 import re
@@ -31,6 +42,7 @@ from .._lib import require_cuda
 from .causal_stack import HEAD_DIM, FrozenCausalStack, Layer, _Prepared, f32, gemm_weight, prefill
 
 MAX_ROWS = 64            # decode-step rows per chunk: the skinny GEMM's and the LM head's M bound
+MAX_BEAMS = 8            # beam_step holds a caption's B x B candidates in one wave
 _IGNORED = re.compile(r"^h\.\d+\.attn\.(bias|masked_bias)$")     # the causal-mask buffers older transformers files carry
 
 
@@ -176,39 +188,47 @@ class GPT2Decoder(FrozenCausalStack):
         x = x.view(n, P, E)[:, P - 1].contiguous()
         self._head(Pm, x, tokens[:, 0], logits)
 
+        def attend(li, qkv):
+            if T == torch.bfloat16:
+                return layers.decode_attention(qkv, kc[li], vc[li], L, H, scale)
+            q3 = qkv.view(n, 3, H, HEAD_DIM)
+            kc[li, :, L - 1] = qkv[:, E:2 * E]
+            vc[li, :, L - 1] = qkv[:, 2 * E:]
+            kk = kc[li, :, :L].view(n, L, H, HEAD_DIM).transpose(1, 2)          # [n, H, L, 64]
+            vv = vc[li, :, :L].view(n, L, H, HEAD_DIM).transpose(1, 2)
+            att = torch.softmax((q3[:, 0].unsqueeze(2) @ kk.transpose(-1, -2)) * scale, dim=-1)   # [n, H, 1, L]
+            return (att @ vv).reshape(n, E).contiguous()
+
         xb = torch.empty((n, E), device=dev, dtype=torch.float32)
         for s in range(1, max_tokens):
             if stop_id is not None and s % check_every == 0 and bool((tokens[:, :s] == stop_id).any(dim=1).all()):
                 break
             L = P + s
-            x = layers.token_position_embed(tokens[:, s - 1], Pm.wte, Pm.wpe, L - 1, out=xb)
-            for li, B in enumerate(Pm.layers):
-                y = hip.layernorm_fwd(x, B.ln1_w, B.ln1_b, T, self.eps)[0]
-                if T == torch.bfloat16 and self.decode_linear == "skinny":
-                    qkv = layers.skinny_linear(y, B.w_qkv, B.b_qkv)
-                    o = layers.decode_attention(qkv, kc[li], vc[li], L, H, scale)
-                    x = layers.skinny_linear(o, B.w_out, B.b_out, residual=x, out=x)
-                    y = hip.layernorm_fwd(x, B.ln2_w, B.ln2_b, T, self.eps)[0]
-                    h = layers.skinny_linear(y, B.w_fc, B.b_fc, gelu=True)
-                    x = layers.skinny_linear(h, B.w_proj, B.b_proj, residual=x, out=x)
-                    continue
-                qkv = hip.linear_fwd(y, B.w_qkv, bias=B.b_qkv)
-                if T == torch.bfloat16:
-                    o = layers.decode_attention(qkv, kc[li], vc[li], L, H, scale)
-                else:
-                    q3 = qkv.view(n, 3, H, HEAD_DIM)
-                    kc[li, :, L - 1] = qkv[:, E:2 * E]
-                    vc[li, :, L - 1] = qkv[:, 2 * E:]
-                    kk = kc[li, :, :L].view(n, L, H, HEAD_DIM).transpose(1, 2)          # [n, H, L, 64]
-                    vv = vc[li, :, :L].view(n, L, H, HEAD_DIM).transpose(1, 2)
-                    att = torch.softmax((q3[:, 0].unsqueeze(2) @ kk.transpose(-1, -2)) * scale, dim=-1)   # [n, H, 1, L]
-                    o = (att @ vv).reshape(n, E).contiguous()
-                x = hip.linear_fwd(o, B.w_out, bias=B.b_out, residual=x, out_f32=True)
-                y = hip.layernorm_fwd(x, B.ln2_w, B.ln2_b, T, self.eps)[0]
-                h = hip.gelu_new_(hip.linear_fwd(y, B.w_fc, bias=B.b_fc))
-                x = hip.linear_fwd(h, B.w_proj, bias=B.b_proj, residual=x, out_f32=True)
+            x = self._decode_step(Pm, layers.token_position_embed(tokens[:, s - 1], Pm.wte, Pm.wpe, L - 1, out=xb), attend)
             self._head(Pm, x, tokens[:, s], logits)
         return tokens, (torch.stack(logits, dim=1) if want_logits else None)
+
+    def _decode_step(self, Pm, x, attend):
+        """one decode step: the rows x [rows, E] f32 (one per sequence) through every layer -> [rows, E] f32.  ``attend(li, qkv)`` is
+        layer li's attention of this step's c_attn output over its cache (which it also extends) -> o [rows, E]."""
+        T = self.compute_dtype
+        for li, B in enumerate(Pm.layers):
+            y = hip.layernorm_fwd(x, B.ln1_w, B.ln1_b, T, self.eps)[0]
+            if T == torch.bfloat16 and self.decode_linear == "skinny":
+                qkv = layers.skinny_linear(y, B.w_qkv, B.b_qkv)
+                o = attend(li, qkv)
+                x = layers.skinny_linear(o, B.w_out, B.b_out, residual=x, out=x)
+                y = hip.layernorm_fwd(x, B.ln2_w, B.ln2_b, T, self.eps)[0]
+                h = layers.skinny_linear(y, B.w_fc, B.b_fc, gelu=True)
+                x = layers.skinny_linear(h, B.w_proj, B.b_proj, residual=x, out=x)
+                continue
+            qkv = hip.linear_fwd(y, B.w_qkv, bias=B.b_qkv)
+            o = attend(li, qkv)
+            x = hip.linear_fwd(o, B.w_out, bias=B.b_out, residual=x, out_f32=True)
+            y = hip.layernorm_fwd(x, B.ln2_w, B.ln2_b, T, self.eps)[0]
+            h = hip.gelu_new_(hip.linear_fwd(y, B.w_fc, bias=B.b_fc))
+            x = hip.linear_fwd(h, B.w_proj, bias=B.b_proj, residual=x, out_f32=True)
+        return x
 
     def _head(self, Pm, x, out_ids, logits):
         """ln_f + the tied LM head's arg-max of rows x [n, E] f32 into out_ids (a strided column of the token buffer)"""
@@ -222,6 +242,86 @@ class GPT2Decoder(FrozenCausalStack):
         out_ids.copy_(lg.argmax(dim=1))
         if logits is not None:
             logits.append(lg)
+
+
+    # ---------------------------------------------------------------- beam search
+    @torch.no_grad()
+    def generate_beam(self, prefix_embeds, beam_size=5, max_tokens=67, stop_id: Optional[int] = None, check_every=4):
+        """prefix_embeds [N, P, n_embd] f32 -> (tokens [N, B, max_tokens] int64, lengths [N, B] int64, scores [N, B] f32), B =
+        ``beam_size`` <= 8: length-normalised beam search (the module docstring has the rule), a caption's beams sorted by score =
+        sum of the tokens' log-probabilities / length, best first, ties to the lower beam.  A beam ends after it emits ``stop_id``
+        (kept in it); decoding ends when every beam of the chunk has ended (tested every ``check_every`` steps) or after
+        ``max_tokens``.  Entries at and after a beam's length are -1; a caption's result does not depend on the other captions.
+        Chunks hold 64 // B captions.  ``beam_size=1`` gives ``generate``'s tokens."""
+        require_cuda(self.wte.weight)
+        dev = self.wte.weight.device
+        N, P, E = prefix_embeds.shape
+        assert E == self.n_embd and max_tokens >= 1
+        if not 1 <= beam_size <= min(MAX_BEAMS, self.vocab_size):
+            raise ValueError(f"beam_size {beam_size} outside 1..{min(MAX_BEAMS, self.vocab_size)}")
+        if P + max_tokens - 1 > min(self.n_positions, 1024) or (self.compute_dtype == torch.bfloat16 and P > 128):
+            raise ValueError(f"prefix {P} + {max_tokens} tokens does not fit n_positions {self.n_positions}")
+        prefix_embeds = prefix_embeds.to(dev, torch.float32).contiguous()
+        Pm = self._prepared()
+        per = MAX_ROWS // beam_size
+        outs = [self._beam_chunk(Pm, prefix_embeds[c0:c0 + per], beam_size, max_tokens, stop_id, check_every) for c0 in range(0, N, per)]
+        if not outs:
+            return (torch.empty((0, beam_size, max_tokens), dtype=torch.int64, device=dev),
+                    torch.empty((0, beam_size), dtype=torch.int64, device=dev), torch.empty((0, beam_size), device=dev))
+        return tuple(torch.cat(v) for v in zip(*outs))
+
+    def _beam_chunk(self, Pm, prefix, B, max_tokens, stop_id, check_every):
+        T = self.compute_dtype
+        n, P, E = prefix.shape
+        rows, H, scale, nl = n * B, self.heads, HEAD_DIM ** -0.5, len(Pm.layers)
+        dev = prefix.device
+        pk = torch.empty((nl, n, P, E), device=dev, dtype=T)                 # the prefix's keys / values: per caption, shared by its beams
+        pv = torch.empty_like(pk)
+        gk = torch.empty((nl, rows, max(max_tokens - 1, 1), E), device=dev, dtype=T)   # generated positions: written once, never moved
+        gv = torch.empty_like(gk)
+        cur, nxt = hip.BeamState(n, B, max_tokens, dev), hip.BeamState(n, B, max_tokens, dev)
+
+        x = prefill(Pm.layers, layers.prefix_position_embed(prefix, Pm.wpe), n, P, H, T, hip.gelu_new_, self.eps, kv=(pk, pv))
+        x = x.view(n, P, E)[:, P - 1].contiguous()
+        hip.beam_step(*self._head_topk(Pm, x, B), nxt, cur, 0, stop_id)      # step 0: one row per caption
+
+        cap = torch.arange(rows, device=dev) // B                            # (exact-f32 path) a row's caption, its first row
+        base, steps = (cap * B).unsqueeze(1), torch.arange(max(max_tokens - 1, 1), device=dev)
+
+        def attend(li, qkv):
+            if T == torch.bfloat16:
+                return layers.decode_attention_beam(qkv, pk[li], pv[li], gk[li], gv[li], cur.anc, L, B, H, scale)
+            t = L - 1 - P                                                    # this step's generated position
+            gk[li, :, t] = qkv[:, E:2 * E]
+            gv[li, :, t] = qkv[:, 2 * E:]
+            own = base + cur.anc[:, :t].long()                               # [rows, t]: the row that holds step j of this beam's history
+            kk = torch.cat([pk[li][cap], gk[li][own, steps[:t]], qkv[:, None, E:2 * E]], 1).view(rows, L, H, HEAD_DIM).transpose(1, 2)
+            vv = torch.cat([pv[li][cap], gv[li][own, steps[:t]], qkv[:, None, 2 * E:]], 1).view(rows, L, H, HEAD_DIM).transpose(1, 2)
+            att = torch.softmax((qkv.view(rows, 3, H, HEAD_DIM)[:, 0].unsqueeze(2) @ kk.transpose(-1, -2)) * scale, dim=-1)
+            return (att @ vv).reshape(rows, E).contiguous()
+
+        xb = torch.empty((rows, E), device=dev, dtype=torch.float32)
+        for s in range(1, max_tokens):
+            if stop_id is not None and s % check_every == 0 and bool(cur.stop.all()):
+                break
+            L = P + s
+            x = self._decode_step(Pm, layers.token_position_embed(cur.next_tok, Pm.wte, Pm.wpe, L - 1, out=xb), attend)
+            hip.beam_step(*self._head_topk(Pm, x, B), cur, nxt, s, stop_id)
+            cur, nxt = nxt, cur
+        scores = cur.sum / cur.len.float()
+        order = torch.sort(scores, dim=1, descending=True, stable=True).indices
+        tokens = cur.hist.long().gather(1, order.unsqueeze(2).expand(n, B, max_tokens))
+        return tokens, cur.len.long().gather(1, order), scores.gather(1, order)
+
+    def _head_topk(self, Pm, x, B):
+        """ln_f + the tied LM head of rows x [m, E] f32 -> (vals [m, B] f32, idx [m, B] int32, logZ [m] f32): each row's B largest
+        logits (larger value, then lower index) and its log-sum-exp"""
+        y = hip.layernorm_fwd(x, Pm.ln_w, Pm.ln_b, self.compute_dtype, self.eps)[0]
+        if self.compute_dtype == torch.bfloat16:
+            return hip.lm_head_topk(y, Pm.wte, B)
+        lg = y @ Pm.wte.t()
+        top = torch.sort(lg, dim=1, descending=True, stable=True)
+        return top.values[:, :B].contiguous(), top.indices[:, :B].to(torch.int32).contiguous(), torch.logsumexp(lg, dim=1)
 
 
 def finish_tokens(tokens, stop_id: Optional[int]):
@@ -285,6 +385,75 @@ def torch_greedy(dec: GPT2Decoder, prefix, max_tokens=67, stop_id: Optional[int]
     tokens[:, :len(toks)] = torch.stack(toks, dim=1)
     tokens, lengths = finish_tokens(tokens, stop_id)
     return tokens, lengths, torch.stack(logs, dim=1)
+
+
+def torch_beam(dec: GPT2Decoder, prefix, beam_size=5, max_tokens=67, stop_id: Optional[int] = None, dtype=torch.float32):
+    """``generate_beam``'s rule restated with the full sequence recomputed every step on plain torch ops (any device) -> (tokens
+    [N, B, max_tokens] int64, lengths [N, B], scores [N, B] f32, gaps [N, steps] f32).  The logits are computed in ``dtype``, the
+    selection in f32.  ``gaps[n, s]`` is the distance between the B-th and the (B+1)-th key of step s (inf when there is no
+    (B+1)-th candidate): where it is small, another summation order may select differently.  Every beam offers B + 1 tokens here so
+    that the (B+1)-th key is the true one; the B survivors are the same as with B tokens per beam."""
+    dev = dec.wte.weight.device
+    B, T, V = beam_size, max_tokens, dec.vocab_size
+    N, P, E = prefix.shape
+    K1 = min(B + 1, V)
+    stop = -1 if stop_id is None else int(stop_id)
+    wte = dec.wte.weight.to(dtype)
+    inf = torch.tensor(float("inf"), device=dev)
+
+    def top(lg):                                       # [..., V] f32 -> the K1 largest (larger value, then lower index), log-sum-exp
+        st = torch.sort(lg, dim=-1, descending=True, stable=True)
+        return st.values[..., :K1], st.indices[..., :K1], torch.logsumexp(lg, dim=-1)
+
+    # step 0: the last prefix row's B best tokens
+    vals, idx, logZ = top(torch_gpt2_logits(dec, prefix.to(dev, dtype), dtype)[:, -1].float())
+    logp = vals - logZ.unsqueeze(1)
+    bsum, blen = logp[:, :B].clone(), torch.ones((N, B), dtype=torch.int64, device=dev)
+    hist = torch.full((N, B, T), -1, dtype=torch.int64, device=dev)
+    hist[:, :, 0] = idx[:, :B]
+    stopped = idx[:, :B] == stop
+    gaps = [logp[:, B - 1] - logp[:, B] if K1 > B else inf.expand(N)]
+    emb = prefix.to(dev, dtype).unsqueeze(1).expand(N, B, P, E)
+    feed = torch.where(stopped, torch.full_like(idx[:, :B], max(stop, 0)), idx[:, :B])
+    ar = torch.arange(N, device=dev).unsqueeze(1)
+    for s in range(1, T):
+        if bool(stopped.all()):
+            break
+        emb = torch.cat([emb, wte[feed].unsqueeze(2)], dim=2)                           # [N, B, P + s, E]
+        vals, idx, logZ = top(torch_gpt2_logits(dec, emb.reshape(N * B, P + s, E), dtype)[:, -1].float().view(N, B, V))
+        csum = bsum.unsqueeze(2) + (vals - logZ.unsqueeze(2))                           # [N, B, K1]
+        clen = (blen + 1).unsqueeze(2).expand(N, B, K1).clone()
+        valid = torch.ones((N, B, K1), dtype=torch.bool, device=dev)
+        tok = idx.clone()
+        # a stopped beam offers itself once, as token column 0
+        first = torch.zeros(K1, dtype=torch.bool, device=dev)
+        first[0] = True
+        sb = stopped.unsqueeze(2)
+        csum = torch.where(sb, bsum.unsqueeze(2).expand_as(csum), csum)
+        clen = torch.where(sb, blen.unsqueeze(2).expand_as(clen), clen)
+        tok = torch.where(sb, torch.zeros_like(tok), tok)
+        valid &= ~sb | first
+        key = csum / clen.float()
+        flat = torch.arange(B, device=dev).view(1, B, 1) * V + tok
+        key = torch.where(valid, key, -inf).view(N, B * K1)
+        flat = torch.where(valid, flat, torch.full_like(flat, B * V)).view(N, B * K1)
+        o1 = torch.sort(flat, dim=1, stable=True).indices                               # lower flat index first among equal keys
+        o2 = torch.sort(key.gather(1, o1), dim=1, descending=True, stable=True).indices
+        order = o1.gather(1, o2)                                                        # [N, B * K1], best first
+        kbest, vbest = key.gather(1, order), valid.view(N, B * K1).gather(1, order)
+        gaps.append(torch.where(vbest[:, B], kbest[:, B - 1] - kbest[:, B], inf) if B * K1 > B else inf.expand(N))
+        win = order[:, :B]
+        src = win // K1
+        wtok, was = tok.view(N, B * K1).gather(1, win), stopped.gather(1, src)
+        bsum, blen = csum.reshape(N, B * K1).gather(1, win), clen.reshape(N, B * K1).gather(1, win)
+        hist = hist[ar, src]
+        hist[:, :, s] = torch.where(was, torch.full_like(wtok, -1), wtok)
+        stopped = was | (wtok == stop)
+        emb = emb[ar, src]
+        feed = torch.where(stopped, torch.full_like(wtok, max(stop, 0)), wtok)
+    scores = bsum / blen.float()
+    order = torch.sort(scores, dim=1, descending=True, stable=True).indices
+    return hist[ar, order], blen.gather(1, order), scores.gather(1, order), torch.stack(gaps, dim=1)
 
 
 def load_gpt2(path: str, compute_dtype=torch.bfloat16) -> GPT2Decoder:

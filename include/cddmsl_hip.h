@@ -244,7 +244,24 @@ int cddmsl_text_pool(const float* x, const long* rows, const float* gamma, const
  *              1 <= L <= min(Lmax, 1024), bf16 only (dtype 0).
  * pos_embed:   x [rows][W] f32 = row value + wpe[pos0 + r % t]; the row value is tab[ids[r * ld_ids]] (tab [vocab][W] in `dtype`)
  *              when ids is given, else src [rows][W] f32 (exactly one of ids / src); pos0 + t <= npos, W % 8 == 0.
- * gelu_new:    x = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) in place, numel % 8 == 0 (bf16) / % 4 == 0 (f32). */
+ * gelu_new:    x = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) in place, numel % 8 == 0 (bf16) / % 4 == 0 (f32).
+ * Beam search (length-normalised, beam width 1 <= B <= 8; row = caption * B + beam):
+ * lm_head_topk: per row m of h [M][K] bf16 @ wte [V][K]^T bf16: vals [M][B] f32 / idx [M][B] int32 = the B largest logits in the order
+ *              "larger value, then lower index" (lm_head_argmax's), logZ [M] f32 = max + log(sum exp(logit - max)).  The f32 logits
+ *              go to `logits` [M][V] when non-NULL, else to ws (ws_bytes >= cddmsl_lm_head_topk_workspace(M, V)).  1 <= M <= 64,
+ *              K % 64 == 0, B <= V.  No atomics; a row's outputs do not depend on M or on the other rows.
+ * beam_step:   one selection step for n captions.  step >= 1: vals / idx [n*B][B] and logZ [n*B] of the rows' logits; the state
+ *              sum [n*B] f32, len [n*B] int32, stop [n*B] uint8, hist [n*B][T] int32 (tokens, -1 past the length) and the ancestry
+ *              table anc [n*B][T-1] uint8 are read from *_in and written to *_out (distinct buffers).  A live beam offers its B
+ *              tokens with key (sum + (logit - logZ)) / (len + 1), a stopped beam itself with key sum / len; the B largest keys
+ *              survive, ties to the lower (beam, token); new beam j = the j-th survivor: src [n*B] int32 its source beam, next_tok
+ *              [n*B] int64 the token it appended (stop_id once stopped), hist_out its source's tokens plus that token at `step`,
+ *              anc_out its source's ancestry plus the source beam at step - 1.  step == 0: vals / idx [n][B], logZ [n]; beam j
+ *              takes the j-th pair (the *_in tables may be NULL).  stop_id -1: none.  0 <= step < T.
+ * decode_attn_beam: decode_attn with indirect keys / values: positions j < P from the caption's prefix cache pk / pv
+ *              [rows/B][P][heads*64], P <= j < L-1 from the generated cache gk / gv [rows][Tg][heads*64] at row
+ *              (r / B) * B + anc[r * ldanc + j - P], position j - P; position L-1 from qkv, written to gk / gv at row r, position
+ *              L-1-P.  P + 1 <= L <= min(P + Tg, 1024).  The summation orders are decode_attn's. */
 int cddmsl_skinny_gemm_workspace(int M, int N, int K);
 int cddmsl_skinny_gemm(const void* x, const void* w, const float* bias, const float* residual, void* y, float* ws, long ws_bytes, int M,
                        int N, int K, int epi, void* stream);
@@ -256,6 +273,15 @@ int cddmsl_decode_attn(const void* qkv, void* kc, void* vc, void* o, int nseq, i
 int cddmsl_pos_embed(const long* ids, int ld_ids, const void* tab, const float* src, const float* wpe, float* x, long rows, int t, int pos0,
                      int W, int vocab, int npos, int dtype, void* stream);
 int cddmsl_gelu_new(void* x, long numel, int dtype, void* stream);
+int cddmsl_lm_head_topk_workspace(int M, int V);
+int cddmsl_lm_head_topk(const void* h, const void* wte, float* vals, int* idx, float* logZ, float* logits, void* ws, long ws_bytes, int M,
+                        int V, int K, int B, void* stream);
+int cddmsl_beam_step(const float* vals, const int* idx, const float* logZ, const float* sum_in, const int* len_in,
+                     const unsigned char* stop_in, const int* hist_in, const unsigned char* anc_in, float* sum_out, int* len_out,
+                     unsigned char* stop_out, int* hist_out, unsigned char* anc_out, int* src, long* next_tok, int n, int B, int T, int step,
+                     int stop_id, void* stream);
+int cddmsl_decode_attn_beam(const void* qkv, const void* pk, const void* pv, void* gk, void* gv, const unsigned char* anc, void* o, int rows,
+                            int B, int heads, int dh, int P, int L, int Tg, int ldanc, int ldqkv, float scale, int dtype, void* stream);
 
 /* ---- fp32 heads: cosine-logit classifier (modeling/roi_heads/fast_rcnn.py:546-572) and the contrastive loss over
  * the cosine-similarity matrix (modeling/meta_arch/rcnn.py:308-317,458-468) ------------------------------------ */

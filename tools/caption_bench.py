@@ -5,8 +5,10 @@ captions/s at N = 1 / 16 / 64 captions of ``--tokens`` tokens (no stop token) af
   (b) the same decode with its linears on the conv/GEMM kernel (hip.linear_fwd),
   (c) the reference's algorithm: the full sequence recomputed every step on torch f32 ops (torch_greedy);
 and the achieved weight bandwidth of the skinny GEMM at GPT-2's four shapes and of the LM head.  Prints a table and one JSON line.
+``--beam-size K`` (K > 1) instead times beam search: ``generate_beam`` with K beams on N captions against greedy ``generate`` at the
+same row count N x K, alternated in one process, and ``torch_beam`` (f32, full recompute).
 
-    python tools/caption_bench.py [--tokens 67] [--ns 1,16,64] [--skip-torch]
+    python tools/caption_bench.py [--tokens 67] [--ns 1,16,64] [--skip-torch] [--beam-size 5 --ns 1,12]
 """
 import argparse
 import json
@@ -51,6 +53,33 @@ def kernel_rates(dec, reps=200):
     return rows
 
 
+def beam_rows(dec, dec32, n, K, T, reps, skip_torch, dev):
+    """generate_beam (n captions, K beams) and greedy generate (n * K captions: the same decode-step rows), alternated ``reps`` times"""
+    from cddmsl_amd.modeling.gpt2 import torch_beam
+    rs = np.random.RandomState(n)
+    p = torch.from_numpy((rs.standard_normal((n * K, 40, 768)) * 0.1).astype(np.float32)).to(dev)
+    runs = {"beam": lambda t: dec.generate_beam(p[:n], beam_size=K, max_tokens=t), "greedy": lambda t: dec.generate(p, max_tokens=t)}
+    acc = {k: [[], []] for k in runs}
+    for k, fn in runs.items():                                # warm every shape
+        fn(1), fn(T)
+    for _ in range(reps):
+        for k, fn in runs.items():
+            acc[k][0].append(timed(lambda: fn(1), 1))
+            acc[k][1].append(timed(lambda: fn(T), 1))
+    rows = []
+    for k, caps in (("beam", n), ("greedy", n * K)):
+        pre, tot = float(np.median(acc[k][0])), float(np.median(acc[k][1]))
+        rows.append({"N": caps, "rows": n * K, "route": f"{k} K={K}" if k == "beam" else "greedy", "ms_per_step": (tot - pre) / (T - 1) * 1e3,
+                     "prefill_ms": pre * 1e3, "captions_per_s": caps / tot})
+    if not skip_torch:
+        with torch.no_grad():
+            pre = timed(lambda: torch_beam(dec32, p[:n], K, 1), 1)
+            tot = timed(lambda: torch_beam(dec32, p[:n], K, T), 1)
+        rows.append({"N": n, "rows": n * K, "route": f"torch_beam f32 K={K}", "ms_per_step": (tot - pre) / (T - 1) * 1e3,
+                     "prefill_ms": pre * 1e3, "captions_per_s": n / tot})
+    return rows
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--tokens", type=int, default=67)
@@ -58,6 +87,7 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--skip-torch", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
+    ap.add_argument("--beam-size", type=int, default=1, help="K > 1: time generate_beam with K beams against greedy generate at N x K rows")
     args = ap.parse_args(argv)
     from cddmsl_amd.modeling.gpt2 import GPT2Decoder, torch_greedy
     from cddmsl_amd.synthetic import make_gpt2_state_dict
@@ -68,6 +98,13 @@ def main(argv=None):
     T = args.tokens
     out = {"tokens": T, "rows": []}
     print(f"{'N':>3} {'route':<28} {'ms/step':>9} {'prefill ms':>10} {'captions/s':>11}")
+    if args.beam_size > 1:
+        for n in [int(v) for v in args.ns.split(",")]:
+            for row in beam_rows(dec, dec32, n, args.beam_size, T, args.reps, args.skip_torch, dev):
+                out["rows"].append(row)
+                print(f"{row['N']:>3} {row['route']:<28} {row['ms_per_step']:>9.3f} {row['prefill_ms']:>10.2f} {row['captions_per_s']:>11.1f}")
+        print(json.dumps(out))
+        return
     for n in [int(v) for v in args.ns.split(",")]:
         p = torch.from_numpy((np.random.RandomState(n).standard_normal((n, 40, 768)) * 0.1).astype(np.float32)).to(dev)
         routes = [("a bf16 skinny", dec, "skinny"), ("b bf16 linear_fwd", dec, "gemm")]

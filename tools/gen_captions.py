@@ -10,6 +10,9 @@ Every image of INPUT_DIR (.jpg / .jpeg / .png) is captioned; with ``--regions`` 
 ``clip_project.*``) unless ``--gpt2-weights`` names another file.  GPT-2's vocabulary (``encoder.json`` / ``vocab.json``) does not
 ship, so it is required.  Writes ``OUTPUT_DIR/captions.json``: per image file name {"caption", "tokens"[, "regions": [{"box",
 "class", "score", "caption", "tokens"}]]}.  Greedy decoding stops at ``--stop-token`` (kept) or after ``--max-tokens``.
+``--beam-size K`` with K > 1 decodes by length-normalised beam search of width K (ClipCap's other mode; upstream uses 5) and
+reports the best beam: each image entry gains "score", the mean log-probability of the caption's tokens, and each region entry the
+same as "caption_score" (a region's "score" is its detection score).  K = 1, the default, is the greedy path and its output.
 Images are preprocessed as in training (test-loader resize, then the 224x224 image-level path), not with OpenAI CLIP's PIL
 preprocessing; captions are not claimed to match the reference's.
 """
@@ -36,6 +39,7 @@ def parse(argv=None):
     ap.add_argument("--max-regions", type=int, default=10)
     ap.add_argument("--max-tokens", type=int, default=67)
     ap.add_argument("--stop-token", default=".")
+    ap.add_argument("--beam-size", type=int, default=1, help="beam width 1..8; 1 = greedy decoding")
     ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16", help="bf16 throughput path or exact-f32 parity path")
     ap.add_argument("--batch", type=int, default=32, help="images per embedding batch")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE config overrides (MODEL.WEIGHTS, INPUT_DIR, OUTPUT_DIR, ...)")
@@ -53,6 +57,8 @@ def main(argv=None):
     cfg = get_cfg()
     cfg.merge_from_file(args.config_file)
     cfg.merge_from_list(args.opts)
+    if not 1 <= args.beam_size <= 8:
+        raise SystemExit(f"--beam-size {args.beam_size} outside 1..8")
     _need_file(args.gpt2_vocab, "--gpt2-vocab")
     _need_file(cfg.MODEL.WEIGHTS, "MODEL.WEIGHTS")
     _need_file(cfg.MODEL.get("VISION_TO_LANG_PATH", ""), "MODEL.VISION_TO_LANG_PATH")
@@ -90,10 +96,12 @@ def main(argv=None):
     names = sorted(f for f in os.listdir(cfg.INPUT_DIR) if f.lower().endswith(EXTS))
     images = [read_image(os.path.join(cfg.INPUT_DIR, f), cfg.INPUT.FORMAT) for f in names]
     t0 = time.perf_counter()
-    caps = caption_images(model, mapper, decoder, images, cfg, vocab, args.max_tokens, stop_id, args.batch)
+    beam = args.beam_size if args.beam_size > 1 else None
+    caps = caption_images(model, mapper, decoder, images, cfg, vocab, args.max_tokens, stop_id, args.batch, beam_size=beam)
     result = {n: c for n, c in zip(names, caps)}
     if args.regions:
-        for n, regs in zip(names, caption_regions(model, mapper, decoder, images, cfg, vocab, args.max_regions, args.max_tokens, stop_id)):
+        regions = caption_regions(model, mapper, decoder, images, cfg, vocab, args.max_regions, args.max_tokens, stop_id, beam_size=beam)
+        for n, regs in zip(names, regions):
             result[n]["regions"] = regs
     os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
     path = os.path.join(cfg.OUTPUT_DIR, "captions.json")
