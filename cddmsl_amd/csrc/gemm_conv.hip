@@ -2086,8 +2086,6 @@ __global__ __launch_bounds__(256) void k_conv3x3_small(ConvArgs p) {
 
 static thread_local int g_last_kernel = 0;   // which kernel the last conv/GEMM entry point of this thread launched (cddmsl_last_kernel)
 static thread_local int g_plan_only = 0;     // cddmsl_plan_only(1): entry points choose their kernel (g_last_kernel) and return without launching
-static thread_local int g_batch = 1;   // set by the batched entry point around its launch
-static inline int g_batch_peek() { return g_batch; }
 
 // ------------------------------------------------------------------------------------------------
 // 256x256 tile, 8 waves (2 x 4; 128x64 per wave), two wave groups ping-ponging on each SIMD.
@@ -2831,6 +2829,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_fwd2(ConvArgs p) {
 #endif
 }
 
+// ================================================================================================
+// Host side.  Every entry point below is three steps:
+//   fill    fill_conv / fill_wgrad validate the C arguments and build the kernel arguments;
+//   plan    plan_fwd / plan_wgrad / plan_gemm_tn choose the kernel (the ids of cddmsl_last_kernel), its grid and its split from the
+//           filled arguments, the operand type and the batch count: no HIP call, nothing global touched but the A/B knobs read;
+//   launch  run_fwd / run_wgrad record the choice, stop there in plan-only mode, and launch what the plan says.
+// What needs the device (CU count, registered workspace) is decided in the launchers: the persistent form and the K-split
+// tail of the 256x256 kernel, and whether a split reduction goes through the workspace.
+// ================================================================================================
+
 // Shapes the 256x256 kernel takes: whole 256-column tiles, K-tiles inside one filter tap, vector epilogue, <= 32 taps,
 // and enough tiles to fill the chip.  Environment CDDMSL_GEMM256 (read per launch, so one process can A/B): 0 = always the
 // 128x128 kernel, 2 = the 256x256 kernel wherever it is legal, unset/1 = the heuristic below.
@@ -2840,15 +2848,84 @@ static bool gemm256_legal(const ConvArgs& a) {
   if (2 * a.pad > a.KH - 1 || 2 * a.pad > a.KW - 1) return false;   // rows of a tile must ascend in memory (per-block buffer base)
   return true;
 }
-static bool use_gemm256(const ConvArgs& a) {
-  const char* e = getenv("CDDMSL_GEMM256");
-  const int mode = e ? atoi(e) : 1;
+
+// The A/B knobs are integer environment variables, read where they are used -- per launch, so one process can A/B -- unless the
+// caller keeps the value (CDDMSL_NT_MIN_MB).  `set`: whether the variable exists at all.
+static long env_int(const char* name, long dflt, bool* set = nullptr) {
+  const char* e = getenv(name);
+  if (set) *set = e != nullptr;
+  return e ? atol(e) : dflt;
+}
+
+// operand type of a launch: the C ABI's dtype (0 = bf16, 1 = f32), or OCP e4m3 bytes (the fp8 entry points)
+enum Operand { OP_BF16 = 0, OP_F32 = 1, OP_FP8 = 2 };
+static int elem_size(Operand op) { return op == OP_BF16 ? 2 : op == OP_F32 ? 4 : 1; }
+
+static bool use_gemm256(const ConvArgs& a, int batch) {
+  const long mode = env_int("CDDMSL_GEMM256", 1);
   if (mode == 0) return false;
   if (!gemm256_legal(a)) return false;
   if (mode == 2) return true;                                   // forced (tests)
   // (per-shape A/B inside the training step: 196 tiles (M 25088, N 512) run 1.3-1.5x faster here, 100 tiles and fewer slower)
-  const long tiles = (long)((a.M + 255) / 256) * (a.Cout / 256) * g_batch_peek();
+  const long tiles = (long)((a.M + 255) / 256) * (a.Cout / 256) * batch;
   return tiles >= 160;
+}
+
+// The 256x128 two-workgroup kernel: whole 128-column tiles, K-tiles of 4 chunks inside one filter tap, vector epilogue.
+// CDDMSL_FWD2 (read per launch): 0 = never, 2 = wherever legal (tests, A/B), unset / 1 = the heuristic.
+static bool fwd2_legal(const ConvArgs& a) {
+  const bool vec_ok = (a.ldy % 8 == 0) && (!a.residual || a.ldr % 8 == 0) && (!a.relu_mask || a.ldm % 8 == 0);
+  if (a.pool || a.res_pool || (a.cpp & 3) || (a.Cout & 127) || !vec_ok || a.KH * a.KW > 31) return false;
+  if (2 * a.pad > a.KH - 1 || 2 * a.pad > a.KW - 1) return false;
+  return true;
+}
+static bool use_fwd2(const ConvArgs& a, int batch) {
+  const long mode = env_int("CDDMSL_FWD2", 1);
+  if (mode == 0 || !fwd2_legal(a)) return false;
+  if (mode == 2) return true;
+  // What the 256x256 kernel does not take (Cout = 128, 384, ...; too few 256x256 tiles), when there are enough 256x128 tiles to
+  // give every CU work: per shape (two dispatches in one process) 1.14-1.31x the 128x128 kernel on the 128-channel 3x3 layers,
+  // 1.04-1.23x on their 1x1 layers; against the 256x256 kernel it loses (x0.72-0.99) on everything but K = 128.
+  if (use_gemm256(a, batch) || batch != 1) return false;
+  return (long)(a.Cout / 128) * ((a.M + 255) / 256) >= env_int("CDDMSL_FWD2_MIN", 256);      // (A/B knob)
+}
+
+// ---- plan: what the planners return (members a planner does not set are 0)
+struct Plan {
+  int kernel;              // id of cddmsl_last_kernel (hip.py _CONV_KERNEL); 0 = no kernel takes the launch (CDDMSL_ERR_ARG)
+  unsigned gx, gy;         // grid
+  int splits;              // weight gradient: blocks along the reduction (m) per output tile ...
+  int mtiles_per_split;    // ... and reduction tiles of WM rows per block
+  int bpb;                 // batched TN GEMM, kernels 9 and 7: batches per block
+};
+
+static Plan plan_fwd(const ConvArgs& a, Operand op, int batch) {
+  const long tiles256 = (long)(a.Cout / 256) * ((a.M + 255) / 256);
+  if (op == OP_FP8) {                                           // e4m3 operands: the 256x256 kernel or nothing -- there is no fallback
+    if (!gemm256_legal(a) || tiles256 > 0x7fffffffL) return {};
+    return {10, (unsigned)tiles256, 1};
+  }
+  if (a.y8 && !use_gemm256(a, batch)) return {};               // e4m3 second output: only launches the 256x256 kernel takes (its epilogue writes it)
+  const long tiles128 = (long)((a.Cout + BN - 1) / BN) * ((a.M + BM - 1) / BM);
+  if (tiles128 > 0x7fffffffL) return {};
+  const bool packed = batch == 1 && a.xrs == a.cpp && a.wrs == a.Kc;
+  // few-channel 3x3 layers (the CLIP stem): streaming register-weight kernel
+  // (8 chunks per pixel = the 64 -> 64 layers of res2 in bf16, forward and -- with the ReLU mask -- input gradient)
+  if (!a.pool && a.KH == 3 && a.KW == 3 && a.pad == 1 && (a.cpp == 1 || a.cpp == 4 || (a.cpp == 8 && a.Cout == 64)) &&
+      (a.Cout == 32 || a.Cout == 64) && !a.residual && !a.out_f32 && packed) {
+    // grid-stride over 32-pixel tiles.  Register weights (one chunk per pixel): 8 blocks of 4 waves per CU.  LDS weights (up to
+    // 72 KiB per block, two blocks fit a CU): exactly the resident blocks, so that the weight image is filled once per CU slot
+    // (2048 blocks refilled it every 4 tiles: 2.9 -> 2.7 ms/step)
+    return {8, a.cpp > 1 ? 256u * 2 : 256u * 8, 1};
+  }
+  // ... and the 1x1 layers of res2 with 64 output channels (64 -> 64, 256 -> 64: one 128-column tile of the GEMM kernels would be half
+  // empty): the same kernel with one tap, bf16.  CDDMSL_SMALL_1X1=0: the 128x128 GEMM kernel (A/B)
+  if (op == OP_BF16 && !a.pool && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.stride == 1 && a.Cout == 64 && (a.cpp == 8 || a.cpp == 32) &&
+      !a.residual && !a.out_f32 && !a.y8 && packed && a.ldy == 64 && env_int("CDDMSL_SMALL_1X1", 1) != 0) return {8, 512, 1};
+  if (use_fwd2(a, batch)) return {11, (unsigned)((long)(a.Cout / 128) * ((a.M + 255) / 256)), (unsigned)batch};
+  if (use_gemm256(a, batch)) return {3, (unsigned)tiles256, (unsigned)batch};
+  if (a.pool) return {2, (unsigned)tiles128, 1};           // AvgPool2d(2) fused into the loader: the register-staged kernel
+  return {1, (unsigned)tiles128, (unsigned)batch};
 }
 
 
@@ -2892,159 +2969,131 @@ static int persistent_blocks_raw() {
   }
   return ncu;
 }
-static int persistent_blocks() {
-  const char* e = getenv("CDDMSL_PERSIST");
-  return (e ? atoi(e) : 1) ? persistent_blocks_raw() : 0;
+static int persistent_blocks() { return env_int("CDDMSL_PERSIST", 1) ? persistent_blocks_raw() : 0; }
+
+// ---- launch, forward
+// The epilogue variant (template parameter EPI) of k_conv_fwd256 and k_conv_fwd2: for bf16 outputs the operand set (bit 0 residual,
+// bit 1 ReLU mask) at compile time, otherwise -1 = run-time flags.  with_epi turns the run-time set into the template argument.
+static int epi_of(const ConvArgs& a) { return (a.out_f32 || a.res_f32 || a.y8) ? -1 : (a.residual ? 1 : 0) | (a.relu_mask ? 2 : 0); }
+template <typename F> void with_epi(int epi, F&& launch) {
+  switch (epi) {
+    case 0: launch(std::integral_constant<int, 0>()); break;
+    case 1: launch(std::integral_constant<int, 1>()); break;
+    case 2: launch(std::integral_constant<int, 2>()); break;
+    default: launch(std::integral_constant<int, 3>()); break;
+  }
 }
 
-// The 256x128 two-workgroup kernel: whole 128-column tiles, K-tiles of 4 chunks inside one filter tap, vector epilogue.
-// CDDMSL_FWD2 (read per launch): 0 = never, 2 = wherever legal (tests, A/B), unset / 1 = the heuristic.
-static bool fwd2_legal(const ConvArgs& a) {
-  const bool vec_ok = (a.ldy % 8 == 0) && (!a.residual || a.ldr % 8 == 0) && (!a.relu_mask || a.ldm % 8 == 0);
-  if (a.pool || a.res_pool || (a.cpp & 3) || (a.Cout & 127) || !vec_ok || a.KH * a.KW > 31) return false;
-  if (2 * a.pad > a.KH - 1 || 2 * a.pad > a.KW - 1) return false;
-  return true;
+template <typename T> void launch_small(const ConvArgs& a, unsigned nb, hipStream_t st) {
+  if (a.KH == 1 && a.cpp == 8) hipLaunchKernelGGL((k_conv3x3_small<T, 8, 2, 1>), dim3(nb), dim3(256), 0, st, a);
+  else if (a.KH == 1) hipLaunchKernelGGL((k_conv3x3_small<T, 32, 2, 1>), dim3(nb), dim3(256), 0, st, a);
+  else if (a.cpp == 1 && a.Cout == 32) hipLaunchKernelGGL((k_conv3x3_small<T, 1, 1>), dim3(nb), dim3(256), 0, st, a);
+  else if (a.cpp == 1) hipLaunchKernelGGL((k_conv3x3_small<T, 1, 2>), dim3(nb), dim3(256), 0, st, a);
+  else if (a.cpp == 8) hipLaunchKernelGGL((k_conv3x3_small<T, 8, 2>), dim3(nb), dim3(256), 0, st, a);
+  else if (a.Cout == 32) hipLaunchKernelGGL((k_conv3x3_small<T, 4, 1>), dim3(nb), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_conv3x3_small<T, 4, 2>), dim3(nb), dim3(256), 0, st, a);
 }
-static bool use_fwd2(const ConvArgs& a) {
-  const char* e = getenv("CDDMSL_FWD2");
-  const int mode = e ? atoi(e) : 1;
-  if (mode == 0 || !fwd2_legal(a)) return false;
-  if (mode == 2) return true;
-  // What the 256x256 kernel does not take (Cout = 128, 384, ...; too few 256x256 tiles), when there are enough 256x128 tiles to
-  // give every CU work: per shape (two dispatches in one process) 1.14-1.31x the 128x128 kernel on the 128-channel 3x3 layers,
-  // 1.04-1.23x on their 1x1 layers; against the 256x256 kernel it loses (x0.72-0.99) on everything but K = 128.
-  if (use_gemm256(a) || g_batch_peek() != 1) return false;
-  const char* et = getenv("CDDMSL_FWD2_MIN");                   // (A/B knob)
-  return (long)(a.Cout / 128) * ((a.M + 255) / 256) >= (et ? atol(et) : 256);
-}
-template <typename T> void launch_fwd2(const ConvArgs& a, dim3 grid, hipStream_t st) {
-  const bool taps = !(a.KH == 1 && a.KW == 1 && a.pad == 0);
-  if (sizeof(T) == 4 || a.out_f32 || a.res_f32 || a.y8) {
-    if (taps) hipLaunchKernelGGL((k_conv_fwd2<T, true, -1>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_conv_fwd2<T, false, -1>), grid, dim3(256), 0, st, a);
-    return;
-  }
+
+template <typename T, bool TAPS> void launch_fwd2(const ConvArgs& a, dim3 grid, hipStream_t st) {
+  const int epi = epi_of(a);
   if constexpr (sizeof(T) == 2) {
-    const int epi = (a.residual ? 1 : 0) | (a.relu_mask ? 2 : 0);
-#define CDDMSL_L2(TP, E) hipLaunchKernelGGL((k_conv_fwd2<T, TP, E>), grid, dim3(256), 0, st, a)
-    if (taps) { switch (epi) { case 0: CDDMSL_L2(true, 0); break; case 1: CDDMSL_L2(true, 1); break; case 2: CDDMSL_L2(true, 2); break; default: CDDMSL_L2(true, 3); } }
-    else { switch (epi) { case 0: CDDMSL_L2(false, 0); break; case 1: CDDMSL_L2(false, 1); break; case 2: CDDMSL_L2(false, 2); break; default: CDDMSL_L2(false, 3); } }
-#undef CDDMSL_L2
-  }
-}
-
-template <typename T, bool TAPS> void launch256_main(const ConvArgs& a, dim3 grid, hipStream_t st, int epi);
-// the 256x256 kernel's epilogue variant (template parameter EPI): compile-time operand set for bf16 outputs, run-time flags otherwise
-constexpr int TAIL_FRAC_DEFAULT = 8;
-template <typename T, bool TAPS> void launch256(const ConvArgs& a, dim3 grid, hipStream_t st) {
-  if (sizeof(T) == 4 || a.out_f32 || a.res_f32 || a.y8) { hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, -1>), grid, dim3(512), 0, st, a); return; }
-  const int epi = (a.residual ? 1 : 0) | (a.relu_mask ? 2 : 0);
-  // Tail of a badly quantised launch.  16 x 50 x 83 pixels are 260 row panels: a 256-column layer of res4 is 260 tiles for 256 CUs --
-  // two rounds of workgroups, the second with 4 of them (15 + 16 such launches per step, ~55 and ~30 us each wasted).  When the last
-  // round would be less than an eighth full, the main launch stops at the last full round and the leftover tiles are computed
-  // split along K (every CU takes a slice; raw accumulators to the workspace) and finished by k_conv_split_reduce.
-  if constexpr (std::is_same<T, __bf16>::value) {
-    const int ncu = persistent_blocks_raw();
-    const int tiles = (int)grid.x, rem = ncu > 0 ? tiles % ncu : 0, nktot = a.Kc >> 3;
-    const char* et = getenv("CDDMSL_TAIL_SPLIT");
-    const char* ef = getenv("CDDMSL_TAIL_FRAC");                 // the last round counts as "nearly empty" below 1 / FRAC of the CUs
-    const int frac = ef ? (atoi(ef) > 0 ? atoi(ef) : 8) : TAIL_FRAC_DEFAULT;
-    if (!(et && atoi(et) == 0) && grid.y == 1 && tiles > ncu && rem > 0 && rem * frac <= ncu && nktot >= 16 && g_ws) {
-      int S = ncu / rem;
-      if (S > nktot / 2) S = nktot / 2;
-      { const char* es = getenv("CDDMSL_TAIL_MAXS"); if (es && S > atoi(es)) S = atoi(es); }      // (A/B knob)
-      const int kper = (nktot + S - 1) / S;
-      S = (nktot + kper - 1) / kper;
-      if (S >= 2 && (long)rem * S * 65536 * 4 <= g_ws_bytes) {
-        ConvArgs m = a, t = a;
-        m.tile_limit = tiles - rem;
-        launch256_main<T, TAPS>(m, dim3((unsigned)(tiles - rem), 1), st, epi);
-        t.partial = (float*)g_ws; t.tile0 = tiles - rem; t.ksplits = S; t.kper = kper;
-        hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, -1, false, true>), dim3((unsigned)(rem * S)), dim3(512), 0, st, t);
-        hipLaunchKernelGGL(k_conv_split_reduce, dim3((unsigned)(rem * 64)), dim3(256), 0, st, t);
-        return;
-      }
+    if (epi >= 0) {
+      with_epi(epi, [&](auto e) { hipLaunchKernelGGL((k_conv_fwd2<T, TAPS, decltype(e)::value>), grid, dim3(256), 0, st, a); });
+      return;
     }
   }
-  launch256_main<T, TAPS>(a, grid, st, epi);
+  hipLaunchKernelGGL((k_conv_fwd2<T, TAPS, -1>), grid, dim3(256), 0, st, a);
 }
+
+// Tail of a badly quantised launch.  16 x 50 x 83 pixels are 260 row panels: a 256-column layer of res4 is 260 tiles for 256 CUs --
+// two rounds of workgroups, the second with 4 of them (15 + 16 such launches per step, ~55 and ~30 us each wasted).  When the last
+// round would be less than an eighth full, the main launch stops at the last full round and the leftover tiles are computed
+// split along K (every CU takes a slice; raw accumulators to the workspace) and finished by k_conv_split_reduce.
+// -> the `rem` leftover tiles in `splits` slices of `kper` K-tiles each; splits = 0: no tail split.
+struct TailSplit { int rem, splits, kper; };
+constexpr int TAIL_FRAC_DEFAULT = 8;
+static TailSplit plan_tail_split(int tiles, int ncu, int nktot, long ws_bytes) {
+  const int rem = ncu > 0 ? tiles % ncu : 0;
+  long frac = env_int("CDDMSL_TAIL_FRAC", TAIL_FRAC_DEFAULT);  // the last round counts as "nearly empty" below 1 / FRAC of the CUs
+  if (frac <= 0) frac = 8;
+  if (env_int("CDDMSL_TAIL_SPLIT", 1) == 0 || tiles <= ncu || rem <= 0 || rem * frac > ncu || nktot < 16) return {};
+  long S = ncu / rem;
+  if (S > nktot / 2) S = nktot / 2;
+  const long maxs = env_int("CDDMSL_TAIL_MAXS", S);             // (A/B knob)
+  if (S > maxs) S = maxs;
+  const int kper = (int)((nktot + S - 1) / S);
+  S = (nktot + kper - 1) / kper;
+  if (S < 2 || rem * S * 65536 * 4 > ws_bytes) return {};
+  return {rem, (int)S, kper};
+}
+
 template <typename T, bool TAPS> void launch256_main(const ConvArgs& a, dim3 grid, hipStream_t st, int epi) {
   // Persistent form (bf16, no taps) for SHORT reductions only: per shape, two builds in one process, K <= 512 layers gain 4-6 %
   // (the ~2.4 us between workgroups is 10-20 % of such a tile), K >= 2048 layers lose 2-4 % against the hardware's dynamic
   // dispatch; in the step k_conv_fwd256 50.9 -> 50.4 ms.
   if constexpr (std::is_same<T, __bf16>::value && !TAPS) {
     const int nb = persistent_blocks();
-    const char* emk = getenv("CDDMSL_PERSIST_MAXKT");             // (A/B knob) longest reduction, in K-tiles, that takes the persistent form
-    if (nb > 0 && grid.y == 1 && (int)grid.x > nb && (a.Kc >> 3) <= (emk ? atoi(emk) : 8)) {
-      switch (epi) {
-        case 0: hipLaunchKernelGGL((k_conv_fwd256<T, false, false, 0, true>), dim3(nb), dim3(512), 0, st, a); break;
-        case 1: hipLaunchKernelGGL((k_conv_fwd256<T, false, false, 1, true>), dim3(nb), dim3(512), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_conv_fwd256<T, false, false, 2, true>), dim3(nb), dim3(512), 0, st, a); break;
-        default: hipLaunchKernelGGL((k_conv_fwd256<T, false, false, 3, true>), dim3(nb), dim3(512), 0, st, a); break;
-      }
+    // (A/B knob) CDDMSL_PERSIST_MAXKT: longest reduction, in K-tiles, that takes the persistent form
+    if (nb > 0 && grid.y == 1 && (int)grid.x > nb && (a.Kc >> 3) <= env_int("CDDMSL_PERSIST_MAXKT", 8)) {
+      with_epi(epi, [&](auto e) { hipLaunchKernelGGL((k_conv_fwd256<T, false, false, decltype(e)::value, true>), dim3(nb), dim3(512), 0, st, a); });
       return;
     }
   }
-  switch (epi) {
-    case 0: hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, 0>), grid, dim3(512), 0, st, a); break;
-    case 1: hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, 1>), grid, dim3(512), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, 2>), grid, dim3(512), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, 3>), grid, dim3(512), 0, st, a); break;
+  with_epi(epi, [&](auto e) { hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, decltype(e)::value>), grid, dim3(512), 0, st, a); });
+}
+
+template <typename T, bool TAPS> void launch256(const ConvArgs& a, dim3 grid, hipStream_t st) {
+  const int epi = epi_of(a);
+  if (sizeof(T) == 4 || epi < 0) { hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, -1>), grid, dim3(512), 0, st, a); return; }
+  if constexpr (sizeof(T) != 4) {
+    if constexpr (std::is_same<T, __bf16>::value) {
+      const int tiles = (int)grid.x;
+      const TailSplit ts = grid.y == 1 ? plan_tail_split(tiles, persistent_blocks_raw(), a.Kc >> 3, g_ws ? g_ws_bytes : 0) : TailSplit{};
+      if (ts.splits) {
+        ConvArgs m = a, t = a;
+        m.tile_limit = tiles - ts.rem;
+        launch256_main<T, TAPS>(m, dim3((unsigned)(tiles - ts.rem), 1), st, epi);
+        t.partial = (float*)g_ws; t.tile0 = tiles - ts.rem; t.ksplits = ts.splits; t.kper = ts.kper;
+        hipLaunchKernelGGL((k_conv_fwd256<T, TAPS, false, -1, false, true>), dim3((unsigned)(ts.rem * ts.splits)), dim3(512), 0, st, t);
+        hipLaunchKernelGGL(k_conv_split_reduce, dim3((unsigned)(ts.rem * 64)), dim3(256), 0, st, t);
+        return;
+      }
+    }
+    launch256_main<T, TAPS>(a, grid, st, epi);
   }
 }
-template <> void launch256<float, false>(const ConvArgs& a, dim3 grid, hipStream_t st) { hipLaunchKernelGGL((k_conv_fwd256<float, false, false, -1>), grid, dim3(512), 0, st, a); }
-template <> void launch256<float, true>(const ConvArgs& a, dim3 grid, hipStream_t st) { hipLaunchKernelGGL((k_conv_fwd256<float, true, false, -1>), grid, dim3(512), 0, st, a); }
 
-template <typename T> int conv_fwd_launch(ConvArgs& a, hipStream_t st) {
-  int ntn = (a.Cout + BN - 1) / BN, ntm = (a.M + BM - 1) / BM;
-  long grid = (long)ntn * ntm;
-  if (grid <= 0) return CDDMSL_OK;
-  if (grid > 0x7fffffffL) return CDDMSL_ERR_ARG;
-  // few-channel 3x3 layers (the CLIP stem): streaming register-weight kernel
-  // (8 chunks per pixel = the 64 -> 64 layers of res2 in bf16, forward and -- with the ReLU mask -- input gradient)
-  if (!a.pool && a.KH == 3 && a.KW == 3 && a.pad == 1 && (a.cpp == 1 || a.cpp == 4 || (a.cpp == 8 && a.Cout == 64)) &&
-      (a.Cout == 32 || a.Cout == 64) && !a.residual && !a.out_f32 && g_batch == 1 && a.xrs == a.cpp && a.wrs == a.Kc) {
-    g_last_kernel = 8;
-    if (g_plan_only) return CDDMSL_OK;
-    // grid-stride over 32-pixel tiles.  Register weights (one chunk per pixel): 8 blocks of 4 waves per CU.  LDS weights (up to
-    // 72 KiB per block, two blocks fit a CU): exactly the resident blocks, so that the weight image is filled once per CU slot
-    // (2048 blocks refilled it every 4 tiles: 2.9 -> 2.7 ms/step)
-    const int nb = a.cpp > 1 ? 256 * 2 : 256 * 8;
-    if (a.cpp == 1 && a.Cout == 32) hipLaunchKernelGGL((k_conv3x3_small<T, 1, 1>), dim3(nb), dim3(256), 0, st, a);
-    else if (a.cpp == 1) hipLaunchKernelGGL((k_conv3x3_small<T, 1, 2>), dim3(nb), dim3(256), 0, st, a);
-    else if (a.cpp == 8) hipLaunchKernelGGL((k_conv3x3_small<T, 8, 2>), dim3(nb), dim3(256), 0, st, a);
-    else if (a.Cout == 32) hipLaunchKernelGGL((k_conv3x3_small<T, 4, 1>), dim3(nb), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_conv3x3_small<T, 4, 2>), dim3(nb), dim3(256), 0, st, a);
-    return launch_status();
+template <typename T> void launch_fwd(const ConvArgs& a, const Plan& p, hipStream_t st) {
+  const dim3 grid(p.gx, p.gy);
+  const bool taps = !(a.KH == 1 && a.KW == 1 && a.pad == 0);
+  if constexpr (std::is_same<T, fp8e4>::value) {                // (kernel 10: the only one with e4m3 operands)
+    if (taps) launch256<T, true>(a, grid, st);
+    else launch256<T, false>(a, grid, st);
+  } else {
+    switch (p.kernel) {
+      case 8: launch_small<T>(a, p.gx, st); break;
+      case 11:
+        if (taps) launch_fwd2<T, true>(a, grid, st);
+        else launch_fwd2<T, false>(a, grid, st);
+        break;
+      case 3:
+        if (a.res_pool) hipLaunchKernelGGL((k_conv_fwd256<T, false, true>), grid, dim3(512), 0, st, a);
+        else if (taps) launch256<T, true>(a, grid, st);
+        else launch256<T, false>(a, grid, st);
+        break;
+      case 2: hipLaunchKernelGGL(k_conv_fwd_reg<T>, grid, dim3(256), 0, st, a); break;
+      default: hipLaunchKernelGGL(k_conv_fwd<T>, grid, dim3(256), 0, st, a); break;
+    }
   }
-  // ... and the 1x1 layers of res2 with 64 output channels (64 -> 64, 256 -> 64: one 128-column tile of the GEMM kernels would be half
-  // empty): the same kernel with one tap, bf16.  CDDMSL_SMALL_1X1=0: the 128x128 GEMM kernel (A/B)
-  if (sizeof(T) == 2 && !a.pool && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.stride == 1 && a.Cout == 64 && (a.cpp == 8 || a.cpp == 32) &&
-      !a.residual && !a.out_f32 && !a.y8 && g_batch == 1 && a.xrs == a.cpp && a.wrs == a.Kc && a.ldy == 64 &&
-      !(getenv("CDDMSL_SMALL_1X1") && atoi(getenv("CDDMSL_SMALL_1X1")) == 0)) {
-    g_last_kernel = 8;
-    if (g_plan_only) return CDDMSL_OK;
-    if (a.cpp == 8) hipLaunchKernelGGL((k_conv3x3_small<T, 8, 2, 1>), dim3(512), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_conv3x3_small<T, 32, 2, 1>), dim3(512), dim3(256), 0, st, a);
-    return launch_status();
-  }
-  if (use_fwd2(a)) {
-    grid = (long)(a.Cout / 128) * ((a.M + 255) / 256);
-    g_last_kernel = 11;
-    if (g_plan_only) return CDDMSL_OK;
-    launch_fwd2<T>(a, dim3((unsigned)grid, (unsigned)g_batch), st);
-    return launch_status();
-  }
-  if (use_gemm256(a)) {
-    grid = (long)(a.Cout / 256) * ((a.M + 255) / 256);
-    g_last_kernel = 3;
-    if (g_plan_only) return CDDMSL_OK;
-    const dim3 g256((unsigned)grid, (unsigned)g_batch);
-    if (a.res_pool) hipLaunchKernelGGL((k_conv_fwd256<T, false, true>), g256, dim3(512), 0, st, a);
-    else if (a.KH == 1 && a.KW == 1 && a.pad == 0) launch256<T, false>(a, g256, st);
-    else launch256<T, true>(a, g256, st);
-  } else if (a.pool) { g_last_kernel = 2; if (g_plan_only) return CDDMSL_OK; hipLaunchKernelGGL(k_conv_fwd_reg<T>, dim3((unsigned)grid), dim3(256), 0, st, a); }
-  else { g_last_kernel = 1; if (g_plan_only) return CDDMSL_OK; hipLaunchKernelGGL(k_conv_fwd<T>, dim3((unsigned)grid, (unsigned)g_batch), dim3(256), 0, st, a); }
+}
+
+static int run_fwd(const ConvArgs& a, Operand op, const Plan& p, void* stream) {
+  if (p.kernel == 0) return CDDMSL_ERR_ARG;
+  g_last_kernel = p.kernel;
+  if (g_plan_only) return CDDMSL_OK;
+  if (op == OP_BF16) launch_fwd<__bf16>(a, p, (hipStream_t)stream);
+  else if (op == OP_F32) launch_fwd<float>(a, p, (hipStream_t)stream);
+  else launch_fwd<fp8e4>(a, p, (hipStream_t)stream);
   return launch_status();
 }
 
@@ -3061,20 +3110,21 @@ extern "C" int cddmsl_plan_only(int on) { const int was = g_plan_only; g_plan_on
 // ones non-temporal (same-box A/B of the training step, 3 runs each: never 102.38 ms, always 101.60, above 128 MiB 101.66; on another box 100 MiB was
 // 0.4 ms ahead of always)
 static int nt_out_for(long out_bytes) {
-  static const long nt_min_mb = getenv("CDDMSL_NT_MIN_MB") ? atol(getenv("CDDMSL_NT_MIN_MB")) : 128;
+  static const long nt_min_mb = env_int("CDDMSL_NT_MIN_MB", 128);
   return out_bytes > (nt_min_mb << 20) ? 1 : 0;
 }
 
-static int conv_fwd_impl(const void* x, const void* w, void* y, const float* scale, const float* bias,
-                         const void* residual, const void* relu_mask, int Nimg, int Hi, int Wi, int Cin,
-                         int Cout, int KH, int KW, int stride, int pad, int pool, int ldy, int ldr, int ldm,
-                         int relu, int out_f32, int dtype, void* y8, const float* q8, float* amax8, void* stream) {
-  int es = dtype == 0 ? 2 : 4;
-  if (dtype != 0 && dtype != 1) return CDDMSL_ERR_ARG;
+// ---- fill, forward: validates the arguments of the convolution entry points and builds the kernel arguments (a.M == 0 with
+// CDDMSL_OK: nothing to do).  x / w are `op`; with e4m3 operands everything else is as for bf16.  out_f32: bit 0 = f32 output, and
+// for cddmsl_conv_fwd bits 1 and 2 (below).  y8 / q8 / amax8 (nullable): the e4m3 second output.
+static int fill_conv(ConvArgs& a, Operand op, const void* x, const void* w, void* y, const float* scale, const float* bias,
+                     const void* residual, const void* relu_mask, int Nimg, int Hi, int Wi, int Cin, int Cout, int KH, int KW,
+                     int stride, int pad, int pool, int ldy, int ldr, int ldm, int relu, int out_f32, void* y8, const float* q8,
+                     float* amax8) {
+  const int es = elem_size(op);
   if (Nimg < 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0) return CDDMSL_ERR_ARG;
   if ((Cin * es) % 16 != 0) return CDDMSL_ERR_ARG;            // channel rows must be whole 16-B chunks
   if (pool && (KH != 1 || KW != 1 || pad != 0 || stride != 1)) return CDDMSL_ERR_ARG;
-  ConvArgs a;
   a.x = (const char*)x; a.w = (const char*)w; a.y = (char*)y; a.scale = scale; a.bias = bias;
   a.residual = (const char*)residual; a.relu_mask = (const char*)relu_mask;
   a.Nimg = Nimg; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
@@ -3084,7 +3134,7 @@ static int conv_fwd_impl(const void* x, const void* w, void* y, const float* sca
   // out_f32 bit 1: the residual rows are f32 (bf16 kernels, f32 output, no ReLU mask) -- the mapper's f32 residual stream
   if ((out_f32 & 2) && (!(out_f32 & 1) || !residual || relu_mask || pool)) return CDDMSL_ERR_ARG;
   a.ldy = ldy; a.ldr = ldr; a.ldm = ldm; a.relu = relu; a.out_f32 = out_f32 & 1; a.pool = pool;
-  a.res_f32 = (dtype == 0 && (out_f32 & 2)) ? 1 : 0;
+  a.res_f32 = (op == OP_BF16 && (out_f32 & 2)) ? 1 : 0;
   // out_f32 bit 2: the residual is a 2x2-average-pooled gradient (the downsample path's input gradient at pooled resolution);
   // buffer-addressed from the tensor base, so the pooled tensor must stay below 2 GiB
   a.res_pool = (out_f32 & 4) ? 1 : 0;
@@ -3102,19 +3152,32 @@ static int conv_fwd_impl(const void* x, const void* w, void* y, const float* sca
 #endif
   if (a.M == 0) return CDDMSL_OK;
   a.nt_out = nt_out_for((long)a.M * Cout * 2);
-  if (y8) {       // e4m3 second output: bf16 launches of the 256x256 kernel only (its epilogue writes it)
-    if (dtype != 0 || (out_f32 & 1) || ldy != Cout || !use_gemm256(a)) return CDDMSL_ERR_ARG;
+  if (y8) {       // e4m3 second output: bf16 output of bf16 or e4m3 operands, dense rows
+    if (op == OP_F32 || (out_f32 & 1) || ldy != Cout) return CDDMSL_ERR_ARG;
     a.y8 = (char*)y8; a.q8 = q8; a.amax8 = (unsigned*)amax8;
   }
-  return dtype == 0 ? conv_fwd_launch<__bf16>(a, (hipStream_t)stream) : conv_fwd_launch<float>(a, (hipStream_t)stream);
+  return CDDMSL_OK;
+}
+
+// fill, plan, launch of the three convolution entry points
+static int conv_fwd_any(Operand op, const void* x, const void* w, void* y, const float* scale, const float* bias,
+                        const void* residual, const void* relu_mask, int Nimg, int Hi, int Wi, int Cin,
+                        int Cout, int KH, int KW, int stride, int pad, int pool, int ldy, int ldr, int ldm,
+                        int relu, int out_f32, void* y8, const float* q8, float* amax8, void* stream) {
+  ConvArgs a;
+  const int st = fill_conv(a, op, x, w, y, scale, bias, residual, relu_mask, Nimg, Hi, Wi, Cin, Cout, KH, KW, stride, pad, pool, ldy, ldr, ldm,
+                           relu, out_f32, y8, q8, amax8);
+  if (st != CDDMSL_OK || a.M == 0) return st;
+  return run_fwd(a, op, plan_fwd(a, op, 1), stream);
 }
 
 extern "C" int cddmsl_conv_fwd(const void* x, const void* w, void* y, const float* scale, const float* bias,
                                const void* residual, const void* relu_mask, int Nimg, int Hi, int Wi, int Cin,
                                int Cout, int KH, int KW, int stride, int pad, int pool, int ldy, int ldr, int ldm,
                                int relu, int out_f32, int dtype, void* stream) {
-  return conv_fwd_impl(x, w, y, scale, bias, residual, relu_mask, Nimg, Hi, Wi, Cin, Cout, KH, KW, stride, pad, pool, ldy, ldr, ldm,
-                       relu, out_f32, dtype, nullptr, nullptr, nullptr, stream);
+  if (dtype != 0 && dtype != 1) return CDDMSL_ERR_ARG;
+  return conv_fwd_any((Operand)dtype, x, w, y, scale, bias, residual, relu_mask, Nimg, Hi, Wi, Cin, Cout, KH, KW, stride, pad, pool, ldy, ldr, ldm,
+                      relu, out_f32, nullptr, nullptr, nullptr, stream);
 }
 
 // cddmsl_conv_fwd (bf16) that ALSO writes y8 [M][Cout] = OCP e4m3 of sat(y * q8[0]) and max-es |y| into amax8[0..63] (64 floats,
@@ -3126,8 +3189,8 @@ extern "C" int cddmsl_conv_fwd_q8(const void* x, const void* w, void* y, const f
                                   int Cout, int KH, int KW, int stride, int pad, int relu, void* y8, const float* q8, float* amax8,
                                   void* stream) {
   if (!y8) return CDDMSL_ERR_ARG;
-  return conv_fwd_impl(x, w, y, scale, bias, residual, relu_mask, Nimg, Hi, Wi, Cin, Cout, KH, KW, stride, pad, 0, Cout, Cout, Cout,
-                       relu, 0, 0, y8, q8, amax8, stream);
+  return conv_fwd_any(OP_BF16, x, w, y, scale, bias, residual, relu_mask, Nimg, Hi, Wi, Cin, Cout, KH, KW, stride, pad, 0, Cout, Cout, Cout,
+                      relu, 0, y8, q8, amax8, stream);
 }
 
 // e4m3 x e4m3 -> bf16 (or f32) on the 256x256 kernel: x [Nimg][Hi][Wi][Cin] and w [Cout][KH][KW][Cin] hold OCP e4m3 bytes (Cin a
@@ -3137,55 +3200,113 @@ extern "C" int cddmsl_conv_fwd_q8(const void* x, const void* w, void* y, const f
 extern "C" int cddmsl_conv_fwd_fp8(const void* x, const void* w, void* y, const float* scale, const float* bias,
                                    const void* residual, const void* relu_mask, int Nimg, int Hi, int Wi, int Cin, int Cout, int KH,
                                    int KW, int pad, int relu, int out_f32, void* y8, const float* q8, float* amax8, void* stream) {
-  if (Nimg < 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || (Cin % 128) != 0 || (out_f32 & ~1)) return CDDMSL_ERR_ARG;
-  ConvArgs a;
-  a.x = (const char*)x; a.w = (const char*)w; a.y = (char*)y; a.scale = scale; a.bias = bias;
-  a.residual = (const char*)residual; a.relu_mask = (const char*)relu_mask;
-  a.Nimg = Nimg; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = 1; a.pad = pad;
-  a.Ho = Hi + 2 * pad - KH + 1; a.Wo = Wi + 2 * pad - KW + 1;
-  if (a.Ho <= 0 || a.Wo <= 0) return CDDMSL_ERR_ARG;
-  a.ldy = a.ldr = a.ldm = Cout; a.relu = relu; a.out_f32 = out_f32; a.pool = 0; a.res_f32 = 0; a.res_pool = 0;
-  long M = (long)Nimg * a.Ho * a.Wo;
-  if (M > 0x7fffff00L) return CDDMSL_ERR_ARG;
-  a.M = (int)M; a.cpp = Cin / 16; a.Kc = KH * KW * a.cpp;
-  a.nt_out = nt_out_for(M * Cout * 2);
-  a.dWo = make_fastdiv((unsigned)a.Wo); a.dHo = make_fastdiv((unsigned)a.Ho);
-  a.dcpp = make_fastdiv((unsigned)a.cpp); a.dKW = make_fastdiv((unsigned)KW);
-  a.xrs = a.cpp; a.wrs = a.Kc; a.bx = a.bw = a.by = 0;
-  if (a.M == 0) return CDDMSL_OK;
-  if (!gemm256_legal(a)) return CDDMSL_ERR_ARG;
-  if (y8) {
-    if (out_f32) return CDDMSL_ERR_ARG;
-    a.y8 = (char*)y8; a.q8 = q8; a.amax8 = (unsigned*)amax8;
-  }
-  const long grid = (long)(a.Cout / 256) * ((a.M + 255) / 256);
-  if (grid > 0x7fffffffL) return CDDMSL_ERR_ARG;
-  g_last_kernel = 10;
-  if (g_plan_only) return CDDMSL_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (KH == 1 && KW == 1 && pad == 0) launch256<fp8e4, false>(a, dim3((unsigned)grid, 1), st);
-  else launch256<fp8e4, true>(a, dim3((unsigned)grid, 1), st);
-  return launch_status();
+  if (Cin % 128 != 0 || (out_f32 & ~1)) return CDDMSL_ERR_ARG;
+  return conv_fwd_any(OP_FP8, x, w, y, scale, bias, residual, relu_mask, Nimg, Hi, Wi, Cin, Cout, KH, KW, 1, pad, 0, Cout, Cout, Cout,
+                      relu, out_f32, y8, q8, amax8, stream);
 }
 
 // The 256x256 wgrad kernel takes bf16 "same" problems with whole 256-wide output tiles and 8-chunk-aligned pixels
 // (so the two X halves of a lane share one filter tap).  CDDMSL_GEMM256 as for the forward kernel (0 = never, 2 = always).
 static bool wgrad256_ok(const WgradArgs& a, int batch) {
-  const char* e = getenv("CDDMSL_GEMM256");
-  const int mode = e ? atoi(e) : 1;
+  const long mode = env_int("CDDMSL_GEMM256", 1);
   if (mode == 0) return false;
   if ((a.Cout & 255) || (a.K & 255) || (a.cpp & 7) || (a.ldd & 7)) return false;
   if (mode == 2) return true;
   // long reductions only: each block ends with 64 Ki scalar atomics, which a short m range cannot amortise
   // (threshold from per-shape A/B inside the training step: 9342 (M 66400, 256 x 2304) and 14112 (M 25088, 512 x 4608) run
   // 1.6x faster here than on the 128x128 kernel, 8300 (M 265600, 512 x 256) and everything below run slower)
-  const char* et = getenv("CDDMSL_WGRAD256_MIN");               // (A/B knob)
-  return (long)(a.Cout / 256) * (a.K / 256) * batch * ((a.M + WM - 1) / WM) >= (et ? atol(et) : 4000);
+  return (long)(a.Cout / 256) * (a.K / 256) * batch * ((a.M + WM - 1) / WM) >= env_int("CDDMSL_WGRAD256_MIN", 4000);      // (A/B knob)
 }
-// buffer addressing: lane offset + soffset must stay below 2 GiB inside one block's reduction range
-static bool wgrad256_span_ok(const WgradArgs& a) {
-  const long rowb = (long)(a.ldd * 2 > a.xrs * 16 ? a.ldd * 2 : a.xrs * 16);
-  return ((long)a.mtiles_per_split * WM + WM + 2L * a.Wi + 2) * rowb + (1L << 20) < (1L << 31);
+// buffer addressing of the 256x256 wgrad kernels: lane offset + soffset must stay below 2 GiB inside one block's reduction range
+// (row_bytes: the longer of a dy row and an x pixel row)
+static bool wgrad256_span_ok(int mtiles_per_split, int Wi, long row_bytes) {
+  return ((long)mtiles_per_split * WM + WM + 2L * Wi + 2) * row_bytes + (1L << 20) < (1L << 31);
+}
+
+// ---- plan, weight gradient
+// `*splits` blocks over total_mt reduction tiles -> tiles per block; *splits becomes the number of blocks that then have work
+static int even_split(int total_mt, long* splits) {
+  const int mps = (int)((total_mt + *splits - 1) / *splits);
+  *splits = (total_mt + mps - 1) / mps;
+  return mps;
+}
+
+// Split count of the 128x128 kernels: one round of blocks (2 per CU) for 1x1 layers, two for filters with taps, and at least 8 m-tiles
+// per block.  Every block ends with 16 Ki f32 atomics; with 2048+ blocks the atomic traffic at L2, not the reduction, set the
+// time of the short backbone layers (measured: 150 -> 67 us at M = 66 400, N = 1024, K = 256).
+// ... and a WHOLE number of 512-block rounds (two resident blocks per CU): with 9 output tiles (128 x 1152) a target of 1024
+// gave 114 splits = 1026 blocks, i.e. a third round for two blocks.  Candidates: the largest split count that stays inside
+// r rounds, r = the target's rounds and one more; the one whose last round is fullest wins (fewer rounds on ties).
+// (Not the search of split_256_rounds: the candidates are clamped to 1 instead of skipped, and the fill is that of the blocks
+// left after even_split.)
+static long split_512_rounds(long tiles, int total_mt, bool taps) {
+  bool forced;
+  const long target = env_int("CDDMSL_WGRAD_BLOCKS", taps ? 1024 : 512, &forced);   // tuning knob (A/B runs): target number of blocks
+  const long maxs = (total_mt + 7) / 8;
+  long splits = 1;
+  const long r0 = (target + 511) / 512;
+  double best = -1.0;
+  for (long r = r0; r <= r0 + 1; ++r) {
+    long c = (512 * r) / tiles;
+    if (c < 1) c = 1;
+    if (c > maxs) c = maxs;
+    long real = c;
+    even_split(total_mt, &real);
+    const long blocks = tiles * real, rounds = (blocks + 511) / 512;
+    const double eff = (double)blocks / (512.0 * rounds);
+    if (eff > best + 0.03) { best = eff; splits = c; }
+    if (c == maxs) break;
+  }
+  if (forced) { splits = (target + tiles - 1) / tiles; if (splits > maxs) splits = maxs; }
+  return splits < 1 ? 1 : splits;
+}
+
+// Split count of the 256x256 ping-pong kernels: ONE block per CU, so the grid should be a whole number of 256-block rounds: take
+// the split count whose grid fills its last round best (fewest rounds on ties: every block ends with 64 Ki atomics), with at
+// least 16 reduction tiles per block.  Measured on N = 2048, K = 512: 256 blocks 683 us vs 640 blocks 894 us.
+static long split_256_rounds(long tiles, int total_mt) {
+  const long maxs = (total_mt + 15) / 16;
+  long sp = 1;
+  double best = -1.0;
+  for (int r = 1; r <= 6; ++r) {
+    long c = (256L * r) / tiles;
+    if (c < 1) continue;
+    if (c > maxs) c = maxs;
+    const long blocks = tiles * c, rounds = (blocks + 255) / 256;
+    const double eff = (double)blocks / (256.0 * rounds);
+    if (eff > best + 0.02) { best = eff; sp = c; }
+    if (c == maxs) break;
+  }
+  return sp;
+}
+
+static Plan plan_wgrad(const WgradArgs& a, Operand op, int batch) {
+  const int es = elem_size(op), total_mt = (a.M + WM - 1) / WM;
+  const long tiles256 = (long)(a.Cout / 256) * (a.K / 256);
+  const long row_bytes = (long)a.ldd * es > a.xrs * 16L ? (long)a.ldd * es : a.xrs * 16L;
+  if (op == OP_FP8) {                                           // k_wgrad256_f8 or nothing (the entry point has checked the shape)
+    long sp = split_256_rounds(tiles256, total_mt);
+    const int mps = even_split(total_mt, &sp);
+    if (!wgrad256_span_ok(mps, a.Wi, row_bytes)) return {};
+    return {12, (unsigned)(tiles256 * sp), 1, (int)sp, mps};
+  }
+  const int cols = 256 / es;
+  const long tiles = (long)((a.Cout + cols - 1) / cols) * ((a.K + cols - 1) / cols);
+  long splits = split_512_rounds(tiles, total_mt, !(a.KH == 1 && a.KW == 1));
+  const int mps = even_split(total_mt, &splits);
+  if (tiles * splits > 0x7fffffffL) return {};
+  const bool same = !a.pool && a.stride == 1 && a.Ho == a.Hi && a.Wo == a.Wi;   // LDS-DMA kernel: output pixel == input pixel
+  if (same && op == OP_BF16 && wgrad256_ok(a, batch)) {
+    bool forced;
+    const long want = env_int("CDDMSL_WGRAD256_BLOCKS", 0, &forced);            // tuning knob (A/B runs): force ~this many blocks
+    const long maxs = (total_mt + 15) / 16;
+    long sp = forced ? (want + tiles256 - 1) / tiles256 : split_256_rounds(tiles256, total_mt);
+    if (sp > maxs) sp = maxs;
+    if (sp < 1) sp = 1;
+    const int mps256 = even_split(total_mt, &sp);
+    if (wgrad256_span_ok(mps256, a.Wi, row_bytes)) return {6, (unsigned)(tiles256 * sp), 1, (int)sp, mps256};
+  }
+  return {same ? 5 : 4, (unsigned)(tiles * splits), 1, (int)splits, mps};
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3230,20 +3351,52 @@ extern "C" int cddmsl_set_workspace(void* ptr, long bytes) {
 }
 // whether a split reduction of `blocks` tiles of `tile_floats` goes through the workspace (CDDMSL_WGRAD_WS=0: atomics, for A/B)
 static bool use_workspace(long blocks, long tile_floats) {
-  const char* e = getenv("CDDMSL_WGRAD_WS");
-  if (e && atoi(e) == 0) return false;
+  if (env_int("CDDMSL_WGRAD_WS", 1) == 0) return false;
   return g_ws != nullptr && blocks * tile_floats * 4 <= g_ws_bytes;
 }
 
-extern "C" int cddmsl_conv_wgrad(const void* x, const void* dy, float* dw, const float* scale, int Nimg, int Hi,
-                                 int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad, int pool, int ldd,
-                                 int dtype, void* stream) {
-  int es = dtype == 0 ? 2 : 4;
-  if (dtype != 0 && dtype != 1) return CDDMSL_ERR_ARG;
+// ---- launch, weight gradient
+// One of the split kernels, then -- if there is more than one split and the workspace holds every block's accumulators -- the
+// reduction of the splits into dw (otherwise the blocks add to dw with atomics).  WAVES x FR as for k_wgrad_reduce.
+template <int WAVES, int FR>
+static void launch_wgrad_split(void (*kernel)(WgradArgs), WgradArgs& a, const Plan& p, hipStream_t st) {
+  constexpr int TN = WAVES == 8 ? 256 : 128, SLOTS = WAVES * FR * 64;
+  const int ntn = (a.Cout + TN - 1) / TN, ntk = (a.K + TN - 1) / TN;
+  const bool ws = p.splits > 1 && use_workspace((long)p.gx, SLOTS * 4);
+  if (ws) a.ws = (float*)g_ws;
+  hipLaunchKernelGGL(kernel, dim3(p.gx), dim3(WAVES * 64), 0, st, a);
+  if (ws) hipLaunchKernelGGL((k_wgrad_reduce<WAVES, FR>), dim3((unsigned)(ntn * ntk * (SLOTS / 256))), dim3(256), 0, st, (const f32x4*)g_ws, a.dw, a.scale,
+                             ntn, ntk, p.splits, a.Cout, a.K, a.ldo);
+}
+
+static int run_wgrad(WgradArgs& a, Operand op, const Plan& p, void* stream) {
+  if (p.kernel == 0) return CDDMSL_ERR_ARG;
+  g_last_kernel = p.kernel;
+  if (g_plan_only) return CDDMSL_OK;
+  hipStream_t st = (hipStream_t)stream;
+  a.mtiles_per_split = p.mtiles_per_split;
+  switch (p.kernel) {
+    case 12: launch_wgrad_split<8, 32>(k_wgrad256_f8, a, p, st); break;
+    case 6: launch_wgrad_split<8, 32>(k_wgrad256, a, p, st); break;
+    case 5:
+      if (op == OP_BF16) launch_wgrad_split<4, 16>(k_conv_wgrad_dma<__bf16>, a, p, st);
+      else hipLaunchKernelGGL(k_conv_wgrad_dma<float>, dim3(p.gx), dim3(256), 0, st, a);
+      break;
+    default:
+      if (op == OP_BF16) hipLaunchKernelGGL(k_conv_wgrad<__bf16>, dim3(p.gx), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(k_conv_wgrad<float>, dim3(p.gx), dim3(256), 0, st, a);
+  }
+  return launch_status();
+}
+
+// ---- fill, weight gradient: validates the arguments and builds the kernel arguments of a convolution's weight gradient (a.M == 0
+// with CDDMSL_OK: nothing to do); x / dy are `op`.  The split (mtiles_per_split) is the plan's.
+static int fill_wgrad(WgradArgs& a, Operand op, const void* x, const void* dy, float* dw, const float* scale, int Nimg, int Hi,
+                      int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad, int pool, int ldd) {
+  const int es = elem_size(op);
   if (Nimg < 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0) return CDDMSL_ERR_ARG;
   if ((Cin * es) % 16 != 0 || (Cout * es) % 16 != 0 || (ldd * es) % 16 != 0) return CDDMSL_ERR_ARG;
   if (pool && (KH != 1 || KW != 1 || pad != 0 || stride != 1)) return CDDMSL_ERR_ARG;
-  WgradArgs a;
   a.x = (const char*)x; a.dy = (const char*)dy; a.dw = dw; a.scale = scale;
   a.Nimg = Nimg; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
   a.ldd = ldd; a.pool = pool;
@@ -3253,99 +3406,23 @@ extern "C" int cddmsl_conv_wgrad(const void* x, const void* dy, float* dw, const
   long M = (long)Nimg * a.Ho * a.Wo;
   if (M > 0x7fffff00L) return CDDMSL_ERR_ARG;
   a.M = (int)M; a.cpp = Cin * es / 16; a.Kc = KH * KW * a.cpp; a.K = KH * KW * Cin; a.ncc = Cout * es / 16;
+  a.mtiles_per_split = 0;
   a.dWo = make_fastdiv((unsigned)a.Wo); a.dHo = make_fastdiv((unsigned)a.Ho);
   a.xrs = a.cpp; a.ldo = a.K; a.direct = 0; a.bx = a.bd = a.bo = 0;
 #ifdef CDDMSL_TILE_STAMPS
   a.tstamps = g_tile_stamps;
 #endif
-  if (a.M == 0) return CDDMSL_OK;
-  int cols = 256 / es;
-  long tiles = (long)((Cout + cols - 1) / cols) * ((a.K + cols - 1) / cols);
-  int total_mt = (a.M + WM - 1) / WM;
-  // Split count: one round of blocks (2 per CU) for 1x1 layers, two for filters with taps, and at least 8 m-tiles per block.
-  // Every block ends with 16 Ki f32 atomics; with 2048+ blocks the atomic traffic at L2, not the reduction, set the
-  // time of the short backbone layers (measured: 150 -> 67 us at M = 66 400, N = 1024, K = 256).
-  const char* eb = getenv("CDDMSL_WGRAD_BLOCKS");                  // tuning knob (A/B runs): target number of blocks
-  const long target = eb ? atol(eb) : ((KH == 1 && KW == 1) ? 512 : 1024);
-  long maxs = (total_mt + 7) / 8;
-  // ... and a WHOLE number of 512-block rounds (two resident blocks per CU): with 9 output tiles (128 x 1152) a target of 1024
-  // gave 114 splits = 1026 blocks, i.e. a third round for two blocks.  Candidates: the largest split count that stays inside
-  // r rounds, r = the target's rounds and one more; the one whose last round is fullest wins (fewer rounds on ties).
-  long splits = 1;
-  {
-    const long r0 = (target + 511) / 512;
-    double best = -1.0;
-    for (long r = r0; r <= r0 + 1; ++r) {
-      long c = (512 * r) / tiles;
-      if (c < 1) c = 1;
-      if (c > maxs) c = maxs;
-      const int mps = (int)((total_mt + c - 1) / c);
-      const long real = (total_mt + mps - 1) / mps, blocks = tiles * real, rounds = (blocks + 511) / 512;
-      const double eff = (double)blocks / (512.0 * rounds);
-      if (eff > best + 0.03) { best = eff; splits = c; }
-      if (c == maxs) break;
-    }
-    if (eb) { splits = (target + tiles - 1) / tiles; if (splits > maxs) splits = maxs; }
-  }
-  if (splits < 1) splits = 1;
-  a.mtiles_per_split = (int)((total_mt + splits - 1) / splits);
-  splits = (total_mt + a.mtiles_per_split - 1) / a.mtiles_per_split;
-  long grid = tiles * splits;
-  if (grid > 0x7fffffffL) return CDDMSL_ERR_ARG;
-  const bool same = !pool && stride == 1 && a.Ho == Hi && a.Wo == Wi;   // LDS-DMA kernel: output pixel == input pixel
-  if (same && dtype == 0 && wgrad256_ok(a, 1)) {
-    // 256x256 ping-pong kernel: ONE block per CU, so the grid should be a whole number of 256-block rounds: take the split
-    // count whose grid fills its last round best (fewest rounds on ties: every block ends with 64 Ki atomics), with at
-    // least 16 reduction tiles per block.  Measured on N = 2048, K = 512: 256 blocks 683 us vs 640 blocks 894 us.
-    long tiles2 = (long)(Cout / 256) * (a.K / 256);
-    long maxs2 = (total_mt + 15) / 16;
-    long sp = 1;
-    double best = -1.0;
-    const char* eb2 = getenv("CDDMSL_WGRAD256_BLOCKS");            // tuning knob (A/B runs): force ~this many blocks
-    for (int r = 1; r <= 6 && !eb2; ++r) {
-      long c = (256L * r) / tiles2;
-      if (c < 1) continue;
-      if (c > maxs2) c = maxs2;
-      const long blocks = tiles2 * c, rounds = (blocks + 255) / 256;
-      const double eff = (double)blocks / (256.0 * rounds);
-      if (eff > best + 0.02) { best = eff; sp = c; }
-      if (c == maxs2) break;
-    }
-    if (eb2) { sp = (atol(eb2) + tiles2 - 1) / tiles2; if (sp > maxs2) sp = maxs2; }
-    if (sp < 1) sp = 1;
-    int keep = a.mtiles_per_split;
-    a.mtiles_per_split = (int)((total_mt + sp - 1) / sp);
-    sp = (total_mt + a.mtiles_per_split - 1) / a.mtiles_per_split;
-    if (wgrad256_span_ok(a)) {
-      g_last_kernel = 6;
-      if (g_plan_only) return CDDMSL_OK;
-      if (sp > 1 && use_workspace(tiles2 * sp, 65536)) {
-        a.ws = (float*)g_ws;
-        hipLaunchKernelGGL(k_wgrad256, dim3((unsigned)(tiles2 * sp)), dim3(512), 0, (hipStream_t)stream, a);
-        hipLaunchKernelGGL((k_wgrad_reduce<8, 32>), dim3((unsigned)(tiles2 * 64)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)g_ws, dw, scale,
-                           Cout / 256, a.K / 256, (int)sp, Cout, a.K, a.ldo);
-        return launch_status();
-      }
-      hipLaunchKernelGGL(k_wgrad256, dim3((unsigned)(tiles2 * sp)), dim3(512), 0, (hipStream_t)stream, a);
-      return launch_status();
-    }
-    a.mtiles_per_split = keep;
-  }
-  g_last_kernel = same ? 5 : 4;
-  if (g_plan_only) return CDDMSL_OK;
-  if (same && dtype == 0 && splits > 1 && use_workspace(grid, 16384)) {
-    a.ws = (float*)g_ws;
-    hipLaunchKernelGGL(k_conv_wgrad_dma<__bf16>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL((k_wgrad_reduce<4, 16>), dim3((unsigned)(tiles * 16)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)g_ws, dw, scale,
-                       (Cout + 127) / 128, (a.K + 127) / 128, (int)splits, Cout, a.K, a.ldo);
-  } else if (same) {
-    if (dtype == 0) hipLaunchKernelGGL(k_conv_wgrad_dma<__bf16>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_conv_wgrad_dma<float>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-  } else {
-    if (dtype == 0) hipLaunchKernelGGL(k_conv_wgrad<__bf16>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_conv_wgrad<float>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-  }
-  return launch_status();
+  return CDDMSL_OK;
+}
+
+extern "C" int cddmsl_conv_wgrad(const void* x, const void* dy, float* dw, const float* scale, int Nimg, int Hi,
+                                 int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad, int pool, int ldd,
+                                 int dtype, void* stream) {
+  if (dtype != 0 && dtype != 1) return CDDMSL_ERR_ARG;
+  WgradArgs a;
+  const int st = fill_wgrad(a, (Operand)dtype, x, dy, dw, scale, Nimg, Hi, Wi, Cin, Cout, KH, KW, stride, pad, pool, ldd);
+  if (st != CDDMSL_OK || a.M == 0) return st;
+  return run_wgrad(a, (Operand)dtype, plan_wgrad(a, (Operand)dtype, 1), stream);
 }
 
 // fp8 configuration: dW[Cout][KH*KW*Cin] (f32) += scale[n] * sum_m dy8[m][n] * im2col(x8)[m][k], both operands OCP e4m3 bytes (NHWC, dy
@@ -3356,47 +3433,11 @@ extern "C" int cddmsl_conv_wgrad_fp8_ok(int Cin, int Cout, int KH, int KW, int p
 }
 extern "C" int cddmsl_conv_wgrad_fp8(const void* x8, const void* dy8, float* dw, const float* scale, int Nimg, int Hi, int Wi, int Cin,
                                      int Cout, int KH, int KW, int pad, int ldd, void* stream) {
-  if (Nimg < 0 || Hi <= 0 || Wi <= 0 || !cddmsl_conv_wgrad_fp8_ok(Cin, Cout, KH, KW, pad, ldd) || ldd < Cout) return CDDMSL_ERR_ARG;
+  if (!cddmsl_conv_wgrad_fp8_ok(Cin, Cout, KH, KW, pad, ldd) || ldd < Cout) return CDDMSL_ERR_ARG;
   WgradArgs a;
-  a.x = (const char*)x8; a.dy = (const char*)dy8; a.dw = dw; a.scale = scale;
-  a.Nimg = Nimg; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = 1; a.pad = pad;
-  a.ldd = ldd; a.pool = 0; a.Ho = Hi; a.Wo = Wi;
-  const long M = (long)Nimg * Hi * Wi;
-  if (M > 0x7fffff00L) return CDDMSL_ERR_ARG;
-  a.M = (int)M; a.cpp = Cin / 16; a.Kc = KH * KW * a.cpp; a.K = KH * KW * Cin; a.ncc = Cout / 16;
-  a.dWo = make_fastdiv((unsigned)a.Wo); a.dHo = make_fastdiv((unsigned)a.Ho);
-  a.xrs = a.cpp; a.ldo = a.K; a.direct = 0; a.bx = a.bd = a.bo = 0;
-  if (a.M == 0) return CDDMSL_OK;
-  const int total_mt = (a.M + WM - 1) / WM;
-  // one block per CU: the split count whose grid fills its last 256-block round best, at least 16 reduction tiles per block
-  const long tiles = (long)(Cout / 256) * (a.K / 256), maxs = (total_mt + 15) / 16;
-  long sp = 1;
-  double best = -1.0;
-  for (int r = 1; r <= 6; ++r) {
-    long c = (256L * r) / tiles;
-    if (c < 1) continue;
-    if (c > maxs) c = maxs;
-    const long blocks = tiles * c, rounds = (blocks + 255) / 256;
-    const double eff = (double)blocks / (256.0 * rounds);
-    if (eff > best + 0.02) { best = eff; sp = c; }
-    if (c == maxs) break;
-  }
-  a.mtiles_per_split = (int)((total_mt + sp - 1) / sp);
-  sp = (total_mt + a.mtiles_per_split - 1) / a.mtiles_per_split;
-  // buffer addressing: lane offset + soffset stay below 2 GiB inside one block's reduction range
-  const long rowb = ldd > a.xrs * 16 ? ldd : a.xrs * 16;
-  if (((long)a.mtiles_per_split * WM + WM + 2L * Wi + 2) * rowb + (1L << 20) >= (1L << 31)) return CDDMSL_ERR_ARG;
-  g_last_kernel = 12;
-  if (g_plan_only) return CDDMSL_OK;
-  if (sp > 1 && use_workspace(tiles * sp, 65536)) {
-    a.ws = (float*)g_ws;
-    hipLaunchKernelGGL(k_wgrad256_f8, dim3((unsigned)(tiles * sp)), dim3(512), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL((k_wgrad_reduce<8, 32>), dim3((unsigned)(tiles * 64)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)g_ws, dw, scale,
-                       Cout / 256, a.K / 256, (int)sp, Cout, a.K, a.ldo);
-    return launch_status();
-  }
-  hipLaunchKernelGGL(k_wgrad256_f8, dim3((unsigned)(tiles * sp)), dim3(512), 0, (hipStream_t)stream, a);
-  return launch_status();
+  const int st = fill_wgrad(a, OP_FP8, x8, dy8, dw, scale, Nimg, Hi, Wi, Cin, Cout, KH, KW, 1, pad, 0, ldd);
+  if (st != CDDMSL_OK || a.M == 0) return st;
+  return run_wgrad(a, OP_FP8, plan_wgrad(a, OP_FP8, 1), stream);
 }
 
 // Batched "NT" GEMM on the conv kernel: for b in [0,batch): C_b[m][n] = sum_k A_b[m][k] * B_b[n][k] (+ bias[n]),
@@ -3409,18 +3450,75 @@ extern "C" int cddmsl_gemm_nt_batched(const void* a, const void* w, void* c, con
   if (M < 0 || N <= 0 || K <= 0 || batch < 0 || batch > 65535) return CDDMSL_ERR_ARG;
   if ((K * es) % 16 || (lda * es) % 16 || (ldb * es) % 16 || (sa * es) % 16 || (sw * es) % 16) return CDDMSL_ERR_ARG;
   if (M == 0 || batch == 0) return CDDMSL_OK;
+  // a 1x1 convolution of one 1 x M image, K -> N channels, with the operand rows and the batches at the caller's strides.  Shares
+  // fill_conv; what a convolution never has is set here.  (nt_out: batched outputs keep the default store policy.)
+  const Operand op = (Operand)dtype;
   ConvArgs p;
-  p.x = (const char*)a; p.w = (const char*)w; p.y = (char*)c; p.scale = nullptr; p.bias = bias; p.residual = nullptr; p.relu_mask = nullptr;
-  p.Nimg = 1; p.Hi = 1; p.Wi = M; p.Cin = K; p.Ho = 1; p.Wo = M; p.Cout = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-  p.ldy = ldc; p.ldr = 0; p.ldm = 0; p.relu = 0; p.out_f32 = out_f32; p.pool = 0; p.res_f32 = 0; p.res_pool = 0;
-  p.M = M; p.cpp = K * es / 16; p.Kc = p.cpp;
-  p.dWo = make_fastdiv((unsigned)M); p.dHo = make_fastdiv(1u); p.dcpp = make_fastdiv((unsigned)p.cpp); p.dKW = make_fastdiv(1u);
+  const int st = fill_conv(p, op, a, w, c, nullptr, bias, nullptr, nullptr, 1, 1, M, K, N, 1, 1, 1, 0, 0, ldc, 0, 0, 0, out_f32 ? 1 : 0,
+                           nullptr, nullptr, nullptr);
+  if (st != CDDMSL_OK) return st;
   p.xrs = lda * es / 16; p.wrs = ldb * es / 16;
   p.bx = sa * es; p.bw = sw * es; p.by = sc * (out_f32 ? 4 : es);
-  g_batch = batch;
-  int st = dtype == 0 ? conv_fwd_launch<__bf16>(p, (hipStream_t)stream) : conv_fwd_launch<float>(p, (hipStream_t)stream);
-  g_batch = 1;
-  return st;
+  p.nt_out = 1;
+  return run_fwd(p, op, plan_fwd(p, op, batch), stream);
+}
+
+// ---- the batched TN GEMM: its own plan (kernels 9, 7, 5) and launch
+// k_gemm_tn_small's grid over kt 128-column K-tiles and `batch` batches: -> gridDim.y, *bpb = batches per block
+static unsigned tn_small_grid(long kt, long batch, int* bpb) {
+  long b = (kt * batch + 4095) / 4096;
+  if (b < 8) b = 8;
+  if (b > batch) b = batch;
+  *bpb = (int)b;
+  return (unsigned)((batch + b - 1) / b);
+}
+
+static Plan plan_gemm_tn(const WgradArgs& p, Operand op, int batch, int mode) {
+  const int cols = 256 / elem_size(op), M = p.M, N = p.Cout, K = p.K;
+  const long tiles = (long)((N + cols - 1) / cols) * ((K + cols - 1) / cols);
+  const int total_mt = (M + WM - 1) / WM;
+  if (op == OP_BF16 && total_mt == 1 && N <= 64 && batch >= 64 && K % 128 == 0 && N % 8 == 0) {
+    // one reduction tile, narrow output (the attention pool's per-region products): compact three-stage ring
+    Plan p = {9, (unsigned)(K / 128), 0};
+    p.gy = tn_small_grid(K / 128, batch, &p.bpb);
+    return p;
+  }
+  if (total_mt <= 4 && batch >= 64) {
+    // short reductions over many batches: stream runs of batches through one block (k_gemm_tn_stream)
+    long bpb = (tiles * batch + 4095) / 4096, minb = (8 + total_mt - 1) / total_mt;
+    if (bpb < minb) bpb = minb;
+    if (bpb > batch) bpb = batch;
+    return {7, (unsigned)tiles, (unsigned)((batch + bpb - 1) / bpb), 0, 0, (int)bpb};
+  }
+  long splits = 1;
+  if (mode == 0) {                                              // (the stores of modes 1 / 2 need one block per tile)
+    const long want = (2048 + tiles * batch - 1) / (tiles * batch), maxs = (total_mt + 7) / 8;
+    splits = want < 1 ? 1 : (want > maxs ? maxs : want);
+    if (splits < 1) splits = 1;
+  }
+  const int mps = even_split(total_mt, &splits);
+  if (tiles * splits > 0x7fffffffL) return {};
+  return {5, (unsigned)(tiles * splits), (unsigned)batch, (int)splits, mps};
+}
+
+static void launch_gemm_tn(const WgradArgs& p, Operand op, const Plan& pl, int batch, int mode, hipStream_t st) {
+  const dim3 grid(pl.gx, pl.gy);
+  if (pl.kernel == 9) {
+#define CDDMSL_TNS(NG)                                                                                              \
+  case NG:                                                                                                          \
+    if (mode == 0) hipLaunchKernelGGL((k_gemm_tn_small<NG, 0>), grid, dim3(256), 0, st, p, batch, pl.bpb);      \
+    else if (mode == 1) hipLaunchKernelGGL((k_gemm_tn_small<NG, 1>), grid, dim3(256), 0, st, p, batch, pl.bpb); \
+    else hipLaunchKernelGGL((k_gemm_tn_small<NG, 2>), grid, dim3(256), 0, st, p, batch, pl.bpb);                \
+    break;
+    switch (p.Cout / 8) { CDDMSL_TNS(1) CDDMSL_TNS(2) CDDMSL_TNS(3) CDDMSL_TNS(4) CDDMSL_TNS(5) CDDMSL_TNS(6) CDDMSL_TNS(7) CDDMSL_TNS(8) }
+#undef CDDMSL_TNS
+  } else if (pl.kernel == 7) {
+    if (op == OP_BF16) hipLaunchKernelGGL(k_gemm_tn_stream<__bf16>, grid, dim3(256), 0, st, p, batch, pl.bpb);
+    else hipLaunchKernelGGL(k_gemm_tn_stream<float>, grid, dim3(256), 0, st, p, batch, pl.bpb);
+  } else {
+    if (op == OP_BF16) hipLaunchKernelGGL(k_conv_wgrad_dma<__bf16>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_conv_wgrad_dma<float>, grid, dim3(256), 0, st, p);
+  }
 }
 
 // Batched "TN" GEMM on the LDS-DMA wgrad kernel: out_b[n][k] (+)= sum_m A_b[m][n] * B_b[m][k]; A rows lda apart (n contiguous),
@@ -3432,62 +3530,20 @@ extern "C" int cddmsl_gemm_tn_batched(const void* a, const void* b, void* out, i
   if (dtype != 0 && dtype != 1) return CDDMSL_ERR_ARG;
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch > 65535 || mode < 0 || mode > 2) return CDDMSL_ERR_ARG;
   if ((K * es) % 16 || (N * es) % 16 || (lda * es) % 16 || (ldb * es) % 16 || (sa * es) % 16 || (sb * es) % 16) return CDDMSL_ERR_ARG;
+  // the weight gradient of a 1x1 convolution of one 1 x M image (x = B, dy = A), with rows, batches and output at the caller's
+  // strides.  Shares fill_wgrad; what a convolution never has is set here.
+  const Operand op = (Operand)dtype;
   WgradArgs p;
-  p.x = (const char*)b; p.dy = (const char*)a; p.dw = (float*)out; p.scale = nullptr;
-  p.Nimg = 1; p.Hi = 1; p.Wi = M; p.Cin = K; p.Ho = 1; p.Wo = M; p.Cout = N; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-  p.ldd = lda; p.pool = 0; p.M = M; p.cpp = K * es / 16; p.Kc = p.cpp; p.K = K; p.ncc = N * es / 16;
-  p.dWo = make_fastdiv((unsigned)M); p.dHo = make_fastdiv(1u);
+  const int fs = fill_wgrad(p, op, b, a, (float*)out, nullptr, 1, 1, M, K, N, 1, 1, 1, 0, 0, lda);
+  if (fs != CDDMSL_OK) return fs;
   p.xrs = ldb * es / 16; p.ldo = ldo; p.direct = mode;
   p.bx = sb * es; p.bd = sa * es; p.bo = so * (mode == 2 ? es : 4);
-  int cols = 256 / es;
-  long tiles = (long)((N + cols - 1) / cols) * ((K + cols - 1) / cols);
-  int total_mt = (M + WM - 1) / WM;
-  long splits = 1;
-  if (mode == 0) {
-    long want = (2048 + tiles * batch - 1) / (tiles * batch);
-    long maxs = (total_mt + 7) / 8;
-    splits = want < 1 ? 1 : (want > maxs ? maxs : want);
-    if (splits < 1) splits = 1;
-  }
-  if (dtype == 0 && total_mt == 1 && N <= 64 && batch >= 64 && K % 128 == 0 && N % 8 == 0) {
-    // one reduction tile, narrow output (the attention pool's per-region products): compact three-stage ring
-    const long kt = K / 128;
-    long bpb = (kt * batch + 4095) / 4096;
-    if (bpb < 8) bpb = 8;
-    if (bpb > batch) bpb = batch;
-    const unsigned gy = (unsigned)((batch + bpb - 1) / bpb);
-    g_last_kernel = 9;
-    if (g_plan_only) return CDDMSL_OK;
-#define CDDMSL_TNS(NG)                                                                                                               \
-  case NG:                                                                                                                           \
-    if (mode == 0) hipLaunchKernelGGL((k_gemm_tn_small<NG, 0>), dim3((unsigned)kt, gy), dim3(256), 0, (hipStream_t)stream, p, batch, (int)bpb);      \
-    else if (mode == 1) hipLaunchKernelGGL((k_gemm_tn_small<NG, 1>), dim3((unsigned)kt, gy), dim3(256), 0, (hipStream_t)stream, p, batch, (int)bpb); \
-    else hipLaunchKernelGGL((k_gemm_tn_small<NG, 2>), dim3((unsigned)kt, gy), dim3(256), 0, (hipStream_t)stream, p, batch, (int)bpb);                \
-    break;
-    switch (N / 8) { CDDMSL_TNS(1) CDDMSL_TNS(2) CDDMSL_TNS(3) CDDMSL_TNS(4) CDDMSL_TNS(5) CDDMSL_TNS(6) CDDMSL_TNS(7) CDDMSL_TNS(8) }
-#undef CDDMSL_TNS
-    return launch_status();
-  }
-  if (total_mt <= 4 && batch >= 64) {
-    // short reductions over many batches: stream runs of batches through one block (k_gemm_tn_stream)
-    long bpb = (tiles * batch + 4095) / 4096, minb = (8 + total_mt - 1) / total_mt;
-    if (bpb < minb) bpb = minb;
-    if (bpb > batch) bpb = batch;
-    const unsigned gy = (unsigned)((batch + bpb - 1) / bpb);
-    g_last_kernel = 7;
-    if (g_plan_only) return CDDMSL_OK;
-    if (dtype == 0) hipLaunchKernelGGL(k_gemm_tn_stream<__bf16>, dim3((unsigned)tiles, gy), dim3(256), 0, (hipStream_t)stream, p, batch, (int)bpb);
-    else hipLaunchKernelGGL(k_gemm_tn_stream<float>, dim3((unsigned)tiles, gy), dim3(256), 0, (hipStream_t)stream, p, batch, (int)bpb);
-    return launch_status();
-  }
-  p.mtiles_per_split = (int)((total_mt + splits - 1) / splits);
-  splits = (total_mt + p.mtiles_per_split - 1) / p.mtiles_per_split;
-  long grid = tiles * splits;
-  if (grid > 0x7fffffffL) return CDDMSL_ERR_ARG;
-  g_last_kernel = 5;
+  const Plan pl = plan_gemm_tn(p, op, batch, mode);
+  if (pl.kernel == 0) return CDDMSL_ERR_ARG;
+  g_last_kernel = pl.kernel;
   if (g_plan_only) return CDDMSL_OK;
-  if (dtype == 0) hipLaunchKernelGGL(k_conv_wgrad_dma<__bf16>, dim3((unsigned)grid, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(k_conv_wgrad_dma<float>, dim3((unsigned)grid, (unsigned)batch), dim3(256), 0, (hipStream_t)stream, p);
+  p.mtiles_per_split = pl.mtiles_per_split;
+  launch_gemm_tn(p, op, pl, batch, mode, (hipStream_t)stream);
   return launch_status();
 }
 
@@ -3500,20 +3556,16 @@ extern "C" int cddmsl_attnpool_dx(const void* pds, const void* zu, const float* 
   if (dtype != 0 || K < 0 || P != 49 || TP != 56 || H2 <= 0 || H2 > 64 || (H2 & 7) || C <= 0 || (C & 127) || !g0 || !mbits || !dx) return CDDMSL_ERR_ARG;
   if (K == 0) return CDDMSL_OK;
   if (K > 65535 * 8) return CDDMSL_ERR_ARG;
+  // the batched TN product of cddmsl_gemm_tn_batched's kernel 9 (M = H2, N = TP, K = C, dense operands) with the MODE 3 epilogue
   WgradArgs p;
-  p.x = (const char*)zu; p.dy = (const char*)pds; p.dw = (float*)dx; p.scale = nullptr;
-  p.Nimg = 1; p.Hi = 1; p.Wi = H2; p.Cin = C; p.Ho = 1; p.Wo = H2; p.Cout = TP; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-  p.ldd = TP; p.pool = 0; p.M = H2; p.cpp = C * 2 / 16; p.Kc = p.cpp; p.K = C; p.ncc = TP * 2 / 16;
-  p.dWo = make_fastdiv((unsigned)H2); p.dHo = make_fastdiv(1u);
-  p.xrs = C * 2 / 16; p.ldo = C; p.direct = 3;
+  const int fs = fill_wgrad(p, OP_BF16, zu, pds, (float*)dx, nullptr, 1, 1, H2, C, TP, 1, 1, 1, 0, 0, TP);
+  if (fs != CDDMSL_OK) return fs;
+  p.direct = 3;
   p.bx = (long)H2 * C * 2; p.bd = (long)H2 * TP * 2; p.bo = (long)P * C * 2;
   p.g0 = g0; p.mbits = mbits; p.gpos = gpos;
-  const long kt = C / 128;
-  long bpb = (kt * K + 4095) / 4096;
-  if (bpb < 8) bpb = 8;
-  if (bpb > K) bpb = K;
-  const unsigned gy = (unsigned)((K + bpb - 1) / bpb);
-  hipLaunchKernelGGL((k_gemm_tn_small<7, 3, 49>), dim3((unsigned)kt, gy), dim3(256), 0, (hipStream_t)stream, p, K, (int)bpb);
+  int bpb;
+  const unsigned gy = tn_small_grid(C / 128, K, &bpb);
+  hipLaunchKernelGGL((k_gemm_tn_small<7, 3, 49>), dim3((unsigned)(C / 128), gy), dim3(256), 0, (hipStream_t)stream, p, K, bpb);
   return launch_status();
 }
 

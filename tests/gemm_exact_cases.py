@@ -3,7 +3,8 @@ tests/golden/bench_gemm_launches.json and every kernel instantiation has a Tier 
 
 A case: entry point, the kernel id dispatch must pick (cddmsl_last_kernel; hip.py _CONV_KERNEL), the per-call switches that force
 it, the geometry (the keys tools/record_gemm_launches.py writes), the epilogue flags, the tiers it runs in, the variants it covers
-and -- ``why`` -- which variant it targets and which line of the dispatch in cddmsl_amd/csrc/gemm_conv.hip selects it.
+and -- ``why`` -- which variant it targets and which function of the dispatch in cddmsl_amd/csrc/gemm_conv.hip selects it (plan_* choose the
+kernel, launch_* its instantiation).
 Tier A: small-integer operands, every partial sum exact in f32, output bit-equal to the exact value rounded once.
 Tier B: Gaussian operands, held to exact_gemm.check_bound and exact_gemm.rounding_bias."""
 
@@ -38,134 +39,135 @@ _FWD_SETS_1X1 = {
 }
 
 CASES = []
-# ---- k_conv_fwd (id 1): the 128x128 kernel, conv_fwd_launch's last branch (gemm_conv.hip:3047) when neither k_conv_fwd256
-# (use_gemm256, :3038) nor k_conv_fwd2 (use_fwd2, :3031) is taken.  Ragged M (666 rows) and N (136 columns).
+# ---- k_conv_fwd (id 1): the 128x128 kernel, plan_fwd's default (gemm_conv.hip) when neither k_conv_fwd256
+# (use_gemm256) nor k_conv_fwd2 (use_fwd2) is taken.  Ragged M (666 rows) and N (136 columns).
 for k, e in _FWD_SETS_1X1.items():
-    CASES.append(case(f"fwd_1x1_{k}", "conv_fwd", 1, conv(2, 9, 37, 64, 136), e, F128, "k_conv_fwd 1x1, :3047", ["fwd"]))
+    CASES.append(case(f"fwd_1x1_{k}", "conv_fwd", 1, conv(2, 9, 37, 64, 136), e, F128, "k_conv_fwd 1x1, plan_fwd's default", ["fwd"]))
 CASES += [
-    case("fwd_3x3_bn_relu", "conv_fwd", 1, conv(2, 9, 13, 64, 96, 3, 1, 1), fwd(True, True, relu=True), F128, "k_conv_fwd taps, :3047", ["fwd"]),
-    case("fwd_3x3_mask", "conv_fwd", 1, conv(2, 9, 13, 64, 96, 3, 1, 1), fwd(relu_mask=True), F128, "k_conv_fwd taps, ReLU-mask input gradient, :3047", ["fwd", "relu_mask"]),
+    case("fwd_3x3_bn_relu", "conv_fwd", 1, conv(2, 9, 13, 64, 96, 3, 1, 1), fwd(True, True, relu=True), F128, "k_conv_fwd taps, plan_fwd's default", ["fwd"]),
+    case("fwd_3x3_mask", "conv_fwd", 1, conv(2, 9, 13, 64, 96, 3, 1, 1), fwd(relu_mask=True), F128,
+         "k_conv_fwd taps, ReLU-mask input gradient, plan_fwd's default", ["fwd", "relu_mask"]),
     case("fwd_s56_bias", "conv_fwd", 1, conv(37, 1, 56, 128, 136, 1, 56), fwd(bias=True), F128,
-         "k_conv_fwd, the attention pool's strided query projection (one row of every 56), :3047", ["fwd"]),
+         "k_conv_fwd, the attention pool's strided query projection (one row of every 56), plan_fwd's default", ["fwd"]),
     case("fwd_reg_pool", "conv_fwd", 2, conv(2, 15, 21, 64, 160, pool=True), fwd(), F128,
-         "k_conv_fwd_reg: AvgPool2d(2) fused into the loader, odd sizes floor, :3046", ["fwd_reg_pool"]),
+         "k_conv_fwd_reg: AvgPool2d(2) fused into the loader, odd sizes floor, plan_fwd (pool)", ["fwd_reg_pool"]),
     case("fwd_reg_pool_bn_relu", "conv_fwd", 2, conv(3, 14, 14, 128, 256, pool=True), fwd(True, True, relu=True), {},
-         "k_conv_fwd_reg (pool is never legal on the 256 kernels: gemm256_legal :2839), :3046", ["fwd_reg_pool"]),
+         "k_conv_fwd_reg (pool is never legal on the 256 kernels: gemm256_legal), plan_fwd (pool)", ["fwd_reg_pool"]),
     case("fwd_full_m_rpn_1x1", "conv_fwd", 1, conv(32, 14, 14, 1024, 256), fwd(True, True, relu=True), {},
-         "k_conv_fwd at a bench launch (res5 head, 6272 rows; too few 256x256 tiles, :2851), :3047", ["fwd", "full_m"]),
+         "k_conv_fwd at a bench launch (res5 head, 6272 rows; too few 256x256 tiles for use_gemm256), plan_fwd's default", ["fwd", "full_m"]),
 ]
 CASES += [
     case("fwd_f32_1x1", "conv_fwd", 1, dict(conv(1, 1, 300, 256, 136), dtype="f32"), fwd(), {},
-         "k_conv_fwd<float> (the step's f32 1x1 launches: too few 256x256 tiles, Cout 136 not a fwd2 width), :3047", ["fwd_f32"]),
+         "k_conv_fwd<float> (the step's f32 1x1 launches: too few 256x256 tiles, Cout 136 not a fwd2 width), plan_fwd's default", ["fwd_f32"]),
     case("fwd_f32_1x1_narrow", "conv_fwd", 1, dict(conv(1, 1, 16, 256, 16), dtype="f32"), fwd(), {},
-         "k_conv_fwd<float> at the step's 16 x 256 -> 16 launch, :3047", ["fwd_f32"]),
+         "k_conv_fwd<float> at the step's 16 x 256 -> 16 launch, plan_fwd's default", ["fwd_f32"]),
 ]
-# ---- k_conv_fwd2 (id 11): the 256x128 two-workgroup kernel, use_fwd2 (:2908) -> :3031; launch_fwd2 (:2920) picks TAPS / EPI
+# ---- k_conv_fwd2 (id 11): the 256x128 two-workgroup kernel, use_fwd2 in plan_fwd; launch_fwd / launch_fwd2 pick TAPS / EPI
 for k in ("plain", "bn_relu", "mask", "bias_f32"):
     CASES.append(case(f"fwd2_1x1_{k}", "conv_fwd", 11, conv(2, 19, 23, 96, 384), _FWD_SETS_1X1[k], FWD2,
-                      "k_conv_fwd2<bf16, false, EPI> (EPI -1 for f32 output), :2931 / :2924", ["fwd2_1x1"]))
+                      "k_conv_fwd2<bf16, false, EPI> (EPI -1 for f32 output), launch_fwd2", ["fwd2_1x1"]))
 for k in ("bn_relu", "mask"):
     CASES.append(case(f"fwd2_3x3_{k}", "conv_fwd", 11, conv(2, 19, 23, 32, 128, 3, 1, 1), _FWD_SETS_1X1[k], FWD2,
-                      "k_conv_fwd2<bf16, true, EPI>, :2930", ["fwd2_taps"]))
+                      "k_conv_fwd2<bf16, true, EPI>, launch_fwd2", ["fwd2_taps"]))
 CASES += [
     case("fwd2_full_m_res2_3x3", "conv_fwd", 11, conv(16, 200, 333, 128, 128, 3, 1, 1), fwd(True, True, relu=True), {},
-         "k_conv_fwd2 at the bench's (1065600, 128, 1152) launch, heuristic :2918", ["fwd2_taps", "full_m"]),
+         "k_conv_fwd2 at the bench's (1065600, 128, 1152) launch, use_fwd2's heuristic", ["fwd2_taps", "full_m"]),
     case("fwd2_full_m_res2_3x3_mask", "conv_fwd", 11, conv(16, 200, 333, 128, 128, 3, 1, 1), fwd(relu_mask=True), {},
-         "k_conv_fwd2 input-gradient form at the bench's (1065600, 128, 1152) launch, :2918", ["fwd2_taps", "full_m", "relu_mask"]),
+         "k_conv_fwd2 input-gradient form at the bench's (1065600, 128, 1152) launch, use_fwd2's heuristic", ["fwd2_taps", "full_m", "relu_mask"]),
 ]
-# ---- k_conv_fwd256 (id 3): use_gemm256 (:2843) -> :3038; launch256 (:2939) / launch256_main (:2971) pick the instantiation
+# ---- k_conv_fwd256 (id 3): use_gemm256 in plan_fwd; launch_fwd / launch256 / launch256_main pick the instantiation
 for k, e in _FWD_SETS_1X1.items():
     CASES.append(case(f"fwd256_1x1_{k}", "conv_fwd", 3, conv(2, 19, 23, 128, 512), e, F256,
-                      "k_conv_fwd256<bf16, false, false, EPI> (EPI -1: f32 output / f32 residual, :2940), :2988",
+                      "k_conv_fwd256<bf16, false, false, EPI> (EPI -1: f32 output / f32 residual, launch256), launch256_main",
                       ["fwd256_1x1"] + (["fwd256_out_f32"] if e["out_f32"] else []) + (["fwd256_res_f32"] if e["residual"] == "f32" else [])))
 for k in ("plain", "bias_relu", "bn_relu", "mask"):
     CASES.append(case(f"fwd256_3x3_{k}", "conv_fwd", 3, conv(2, 19, 23, 64, 256, 3, 1, 1), _FWD_SETS_1X1[k], F256,
-                      "k_conv_fwd256<bf16, true, false, EPI>, :2988", ["fwd256_taps"]))
+                      "k_conv_fwd256<bf16, true, false, EPI>, launch256_main", ["fwd256_taps"]))
 CASES += [
     case("fwd256_s56_bias", "conv_fwd", 3, conv(37, 1, 56, 128, 256, 1, 56), fwd(bias=True), F256,
-         "k_conv_fwd256 on the strided query projection (stride is legal on the 256 kernel: gemm256_legal :2837), :2988", ["fwd256_1x1"]),
+         "k_conv_fwd256 on the strided query projection (stride is legal on the 256 kernel: gemm256_legal), launch256_main", ["fwd256_1x1"]),
     case("fwd256_res_pool", "conv_fwd", 3, conv(3, 15, 21, 128, 256), fwd(residual="pooled"), F256,
-         "k_conv_fwd256<bf16, false, true>: AvgPool2d(2)-backward residual, odd sizes, :3043", ["fwd256_res_pool"]),
+         "k_conv_fwd256<bf16, false, true>: AvgPool2d(2)-backward residual, odd sizes, launch_fwd (res_pool)", ["fwd256_res_pool"]),
     case("fwd256_res_pool_mask", "conv_fwd", 3, conv(2, 50, 84, 64, 512), fwd(residual="pooled", relu_mask=True), F256,
-         "k_conv_fwd256<bf16, false, true> with the ReLU mask, :3043", ["fwd256_res_pool", "relu_mask"]),
+         "k_conv_fwd256<bf16, false, true> with the ReLU mask, launch_fwd (res_pool)", ["fwd256_res_pool", "relu_mask"]),
     case("fwd256_persistent", "conv_fwd", 3, conv(1, 83003, 1, 128, 1024), fwd(True, True, "bf16", True), F256,
-         "persistent form (K <= 512, 1 300 tiles > CUs, ragged last panel): launch256_main :2978", ["fwd256_persistent"]),
+         "persistent form (K <= 512, 1 300 tiles > CUs, ragged last panel): launch256_main's persistent form", ["fwd256_persistent"]),
     case("fwd256_persistent_mask", "conv_fwd", 3, conv(1, 83003, 1, 128, 1024), fwd(residual="bf16", relu_mask=True), F256,
-         "persistent form, EPI 3, :2983", ["fwd256_persistent", "relu_mask"]),
+         "persistent form, EPI 3, launch256_main", ["fwd256_persistent", "relu_mask"]),
     case("fwd256_tail_split_3x3", "conv_fwd", 3, conv(13, 64, 80, 320, 256, 3, 1, 1), fwd(True, True, "bf16", True),
          dict(F256, CDDMSL_TAIL_SPLIT="1"),
-         "K-split tail (260 tiles on 256 CUs, K slices starting inside taps) + k_conv_split_reduce epilogue: launch256 :2952", ["fwd256_tail_split"]),
+         "K-split tail (260 tiles on 256 CUs, K slices starting inside taps) + k_conv_split_reduce epilogue: plan_tail_split in launch256", ["fwd256_tail_split"]),
     case("fwd256_tail_split_mask", "conv_fwd", 3, conv(13, 64, 80, 320, 256, 3, 1, 1), fwd(relu_mask=True), dict(F256, CDDMSL_TAIL_SPLIT="1"),
-         "K-split tail, the ReLU-mask form of k_conv_split_reduce, :2952", ["fwd256_tail_split", "relu_mask"]),
+         "K-split tail, the ReLU-mask form of k_conv_split_reduce, plan_tail_split in launch256", ["fwd256_tail_split", "relu_mask"]),
     case("fwd256_dgrad_wd", "conv_fwd", 3, conv(2, 19, 23, 256, 256, 3, 1, 1), fwd(relu_mask=True), F256,
-         "input gradient through weight_prep's flipped / transposed / scaled wd (read back as the operand), :2988", ["dgrad_wd", "relu_mask"]),
+         "input gradient through weight_prep's flipped / transposed / scaled wd (read back as the operand), launch256_main", ["dgrad_wd", "relu_mask"]),
     # bench launch shapes, full M, row-sampled references (16 images)
     case("fwd256_full_m_roi_3x3", "conv_fwd", 3, conv(8192, 14, 14, 512, 512, 3, 1, 1), fwd(True, True, relu=True), {},
-         "the bench's (1605632, 512, 4608) RoI-head 3x3, heuristic :2851, non-temporal stores (1.5 GiB out)", ["fwd256_taps", "full_m"]),
+         "the bench's (1605632, 512, 4608) RoI-head 3x3, use_gemm256's heuristic, non-temporal stores (1.5 GiB out)", ["fwd256_taps", "full_m"]),
     case("fwd256_full_m_roi_3x3_mask", "conv_fwd", 3, conv(8192, 14, 14, 512, 512, 3, 1, 1), fwd(relu_mask=True), {},
-         "its input gradient at full M, :2851", ["fwd256_taps", "full_m", "relu_mask"]),
+         "its input gradient at full M, use_gemm256's heuristic", ["fwd256_taps", "full_m", "relu_mask"]),
     case("fwd256_full_m_roi_expand", "conv_fwd", 3, conv(8192, 7, 7, 512, 2048), fwd(True, True, "bf16", True), {},
-         "the bench's (401408, 2048, 512) res5 expand with residual: persistent form, :2978", ["fwd256_persistent", "full_m"]),
+         "the bench's (401408, 2048, 512) res5 expand with residual: persistent form, launch256_main", ["fwd256_persistent", "full_m"]),
     case("fwd256_full_m_res2_expand", "conv_fwd", 3, conv(16, 200, 333, 64, 256), fwd(True, True, "bf16", True), {},
-         "the bench's (1065600, 256, 64) res2 expand with residual: persistent, one K-tile, :2978", ["fwd256_persistent", "full_m"]),
+         "the bench's (1065600, 256, 64) res2 expand with residual: persistent, one K-tile, launch256_main", ["fwd256_persistent", "full_m"]),
     case("fwd256_full_m_res4_3x3", "conv_fwd", 3, conv(16, 50, 83, 1024, 1024, 3, 1, 1), fwd(bias=True, relu=True), {},
-         "the bench's (66400, 1024, 9216) 3x3: 1 040 tiles, K-split tail, :2952", ["fwd256_tail_split", "full_m"]),
-    # 32-image geometry: input and output 3.06 GiB, sampled rows past byte 2^31 (per-block buffer bases, :2160 / :2583)
+         "the bench's (66400, 1024, 9216) 3x3: 1 040 tiles, K-split tail, plan_tail_split in launch256", ["fwd256_tail_split", "full_m"]),
+    # 32-image geometry: input and output 3.06 GiB, sampled rows past byte 2^31 (per-block buffer bases of tile_epilogue and k_conv_fwd256)
     case("fwd256_over_2gib_roi_3x3", "conv_fwd", 3, conv(16384, 14, 14, 512, 512, 3, 1, 1), fwd(True, True, relu=True), {},
-         "32 images' RoI-head 3x3: operands over 2 GiB, :2851", ["fwd256_taps", "full_m", "over_2gib"]),
+         "32 images' RoI-head 3x3: operands over 2 GiB, use_gemm256's heuristic", ["fwd256_taps", "full_m", "over_2gib"]),
 ]
-# ---- k_conv3x3_small (id 8): conv_fwd_launch :3005 (3x3) and :3022 (1x1, 64 outputs); instantiation by chunks per pixel / Cout
+# ---- k_conv3x3_small (id 8): plan_fwd's two small-layer branches (3x3; 1x1, 64 outputs); launch_small picks the instantiation by chunks per pixel / Cout
 CASES += [
     case("small_1_1", "conv_fwd", 8, conv(2, 37, 53, 8, 32, 3, 2, 1), fwd(True, True, relu=True), {},
-         "k_conv3x3_small<bf16, 1, 1>: the stem's padded 3-channel pixel, 32 outputs, stride 2, :3013", ["small<1,1>"]),
+         "k_conv3x3_small<bf16, 1, 1>: the stem's padded 3-channel pixel, 32 outputs, stride 2, launch_small", ["small<1,1>"]),
     case("small_1_2", "conv_fwd", 8, conv(1, 40, 61, 8, 64, 3, 1, 1), fwd(True, True, relu=True), {},
-         "k_conv3x3_small<bf16, 1, 2>, :3014", ["small<1,2>"]),
+         "k_conv3x3_small<bf16, 1, 2>, launch_small", ["small<1,2>"]),
     case("small_8_2", "conv_fwd", 8, conv(2, 37, 53, 64, 64, 3, 1, 1), fwd(True, True, relu=True), {},
-         "k_conv3x3_small<bf16, 8, 2>: res2's 64 -> 64 3x3, :3015", ["small<8,2>"]),
+         "k_conv3x3_small<bf16, 8, 2>: res2's 64 -> 64 3x3, launch_small", ["small<8,2>"]),
     case("small_8_2_mask", "conv_fwd", 8, conv(1, 50, 83, 64, 64, 3, 1, 1), fwd(relu_mask=True), {},
-         "k_conv3x3_small<bf16, 8, 2> input-gradient form, :3015", ["small<8,2>", "relu_mask"]),
+         "k_conv3x3_small<bf16, 8, 2> input-gradient form, launch_small", ["small<8,2>", "relu_mask"]),
     case("small_4_1", "conv_fwd", 8, conv(3, 21, 30, 32, 32, 3, 1, 1), fwd(True, True, relu=True), {},
-         "k_conv3x3_small<bf16, 4, 1>, :3016", ["small<4,1>"]),
+         "k_conv3x3_small<bf16, 4, 1>, launch_small", ["small<4,1>"]),
     case("small_4_2", "conv_fwd", 8, conv(3, 21, 30, 32, 64, 3, 1, 1), fwd(True, True, relu=True), {},
-         "k_conv3x3_small<bf16, 4, 2>, :3017", ["small<4,2>"]),
+         "k_conv3x3_small<bf16, 4, 2>, launch_small", ["small<4,2>"]),
     case("small_8_2_1", "conv_fwd", 8, conv(2, 37, 53, 64, 64), fwd(True, True, relu=True), {},
-         "k_conv3x3_small<bf16, 8, 2, 1>: 1x1 64 -> 64, :3027", ["small<8,2,1>"]),
+         "k_conv3x3_small<bf16, 8, 2, 1>: 1x1 64 -> 64, plan_fwd's one-tap branch, launch_small", ["small<8,2,1>"]),
     case("small_32_2_1", "conv_fwd", 8, conv(3, 5, 7, 256, 64), fwd(True, True, relu=True), {},
-         "k_conv3x3_small<bf16, 32, 2, 1>: 1x1 256 -> 64, :3028", ["small<32,2,1>"]),
+         "k_conv3x3_small<bf16, 32, 2, 1>: 1x1 256 -> 64, plan_fwd's one-tap branch, launch_small", ["small<32,2,1>"]),
     case("small_full_m_stem2", "conv_fwd", 8, conv(16, 400, 667, 32, 64, 3, 1, 1), fwd(True, True, relu=True), {},
-         "the bench's (4268800, 64, 288) stem conv, :3017", ["small<4,2>", "full_m"]),
+         "the bench's (4268800, 64, 288) stem conv, launch_small", ["small<4,2>", "full_m"]),
 ]
-# ---- weight gradients: cddmsl_conv_wgrad (:3238)
+# ---- weight gradients: cddmsl_conv_wgrad (plan_wgrad chooses kernel and split, run_wgrad / launch_wgrad_split launch)
 CASES += [
     case("wgrad256_3x3_ws", "conv_wgrad", 6, conv(9, 14, 14, 256, 256, 3, 1, 1), wg(True, True), F256,
-         "k_wgrad256 + k_wgrad_reduce<8, 32>: M = 1764 is 28 reduction tiles, two splits through the workspace, into a non-zero dW, :3322",
+         "k_wgrad256 + k_wgrad_reduce<8, 32>: M = 1764 is 28 reduction tiles, two splits through the workspace, into a non-zero dW, launch_wgrad_split",
          ["wgrad256_ws"]),
     case("wgrad256_3x3_atomics", "conv_wgrad", 6, conv(9, 14, 14, 512, 512, 3, 1, 1), wg(False, True), dict(F256, CDDMSL_WGRAD_WS="0"),
-         "k_wgrad256 with f32 atomics (CDDMSL_WGRAD_WS=0), :3329", ["wgrad256_atomics"]),
-    case("wgrad256_1x1_ws", "conv_wgrad", 6, conv(4, 40, 37, 256, 512), wg(True, True), F256, "k_wgrad256 1x1, :3322", ["wgrad256_ws"]),
+         "k_wgrad256 with f32 atomics (CDDMSL_WGRAD_WS=0: use_workspace), launch_wgrad_split", ["wgrad256_atomics"]),
+    case("wgrad256_1x1_ws", "conv_wgrad", 6, conv(4, 40, 37, 256, 512), wg(True, True), F256, "k_wgrad256 1x1, launch_wgrad_split", ["wgrad256_ws"]),
     case("wgrad256_1x1_atomics", "conv_wgrad", 6, conv(2, 9, 11, 256, 512), wg(False, True), dict(F256, CDDMSL_WGRAD_WS="0"),
-         "k_wgrad256 1x1, atomics, :3329", ["wgrad256_atomics"]),
+         "k_wgrad256 1x1, atomics, launch_wgrad_split", ["wgrad256_atomics"]),
     case("wgrad_dma_1x1_ws", "conv_wgrad", 5, conv(4, 40, 37, 128, 192), wg(True, True), F128,
-         "k_conv_wgrad_dma<bf16> + k_wgrad_reduce<4, 16>, :3336", ["wgrad_dma"]),
+         "k_conv_wgrad_dma<bf16> + k_wgrad_reduce<4, 16>, launch_wgrad_split", ["wgrad_dma"]),
     case("wgrad_dma_1x1_acc", "conv_wgrad", 5, conv(4, 40, 37, 128, 192), wg(False, True), dict(F128, CDDMSL_WGRAD_WS="0"),
-         "k_conv_wgrad_dma<bf16> with atomics, :3342", ["wgrad_dma"]),
+         "k_conv_wgrad_dma<bf16> with atomics, launch_wgrad_split", ["wgrad_dma"]),
     case("wgrad_dma_1x1_new", "conv_wgrad", 5, conv(1, 1, 300, 128, 64), wg(), F128,
-         "k_conv_wgrad_dma<bf16> into a fresh dW (the mapper's linear layers), :3336", ["wgrad_dma"]),
-    case("wgrad_dma_3x3", "conv_wgrad", 5, conv(3, 14, 14, 64, 128, 3, 1, 1), wg(True, True), F128, "k_conv_wgrad_dma<bf16> taps, :3336", ["wgrad_dma"]),
+         "k_conv_wgrad_dma<bf16> into a fresh dW (the mapper's linear layers), launch_wgrad_split", ["wgrad_dma"]),
+    case("wgrad_dma_3x3", "conv_wgrad", 5, conv(3, 14, 14, 64, 128, 3, 1, 1), wg(True, True), F128, "k_conv_wgrad_dma<bf16> taps, launch_wgrad_split", ["wgrad_dma"]),
     case("wgrad_s56", "conv_wgrad", 4, conv(37, 1, 56, 128, 136, 1, 56), wg(False, True), {},
-         "k_conv_wgrad: the stride-56 1x1 query projection (not 'same': :3295), :3345", ["wgrad_s56"]),
+         "k_conv_wgrad: the stride-56 1x1 query projection (not 'same' in plan_wgrad), run_wgrad", ["wgrad_s56"]),
     case("wgrad_full_m_s56", "conv_wgrad", 4, conv(8192, 1, 56, 2048, 2048, 1, 56), wg(False, True), {},
-         "k_conv_wgrad at the bench's (8192, 2048, 2048) stride-56 launch, :3345", ["wgrad_s56", "full_m"]),
+         "k_conv_wgrad at the bench's (8192, 2048, 2048) stride-56 launch, plan_wgrad (not 'same')", ["wgrad_s56", "full_m"]),
     case("wgrad256_full_m_roi_3x3", "conv_wgrad", 6, conv(8192, 14, 14, 512, 512, 3, 1, 1), wg(True, True), {},
-         "k_wgrad256 at the bench's (1605632, 512, 4608) launch, heuristic :3183", ["wgrad256_ws", "full_m"]),
+         "k_wgrad256 at the bench's (1605632, 512, 4608) launch, wgrad256_ok's heuristic", ["wgrad256_ws", "full_m"]),
     case("wgrad256_full_m_res4_3x3", "conv_wgrad", 6, conv(16, 50, 83, 1024, 1024, 3, 1, 1), wg(False, True), {},
-         "k_wgrad256 at the bench's (66400, 1024, 9216) launch, :3183", ["wgrad256_ws", "full_m"]),
+         "k_wgrad256 at the bench's (66400, 1024, 9216) launch, wgrad256_ok's heuristic", ["wgrad256_ws", "full_m"]),
     case("wgrad_dma_full_m_res2_3x3", "conv_wgrad", 5, conv(16, 200, 333, 128, 128, 3, 1, 1), wg(True, True), {},
-         "k_conv_wgrad_dma at the bench's (1065600, 128, 1152) launch, :3336", ["wgrad_dma", "full_m"]),
+         "k_conv_wgrad_dma at the bench's (1065600, 128, 1152) launch, plan_wgrad, launch_wgrad_split", ["wgrad_dma", "full_m"]),
     case("wgrad256_over_2gib_roi_3x3", "conv_wgrad", 6, conv(16384, 14, 14, 512, 512, 3, 1, 1), wg(True, True), {},
-         "32 images' RoI-head 3x3 weight gradient: operands over 2 GiB (wgrad256_span_ok :3186)", ["wgrad256_ws", "full_m", "over_2gib"]),
+         "32 images' RoI-head 3x3 weight gradient: operands over 2 GiB (wgrad256_span_ok in plan_wgrad)", ["wgrad256_ws", "full_m", "over_2gib"]),
 ]
-# ---- batched entry points (the attention pool): cddmsl_gemm_nt_batched (:3405) on conv_fwd_launch, cddmsl_gemm_tn_batched (:3429).
+# ---- batched entry points (the attention pool): cddmsl_gemm_nt_batched on plan_fwd / run_fwd, cddmsl_gemm_tn_batched on plan_gemm_tn.
 # Geometry = the full layout (element strides; a_off / b_off / c_off: element offsets of the operand views, as layers.py passes them).
 def nt(M, N, K, batch, lda=None, ldb=None, ldc=None, sa=None, sw=None, sc=None, a_off=0, b_off=0, c_off=0):
     return dict(M=M, N=N, K=K, batch=batch, lda=lda or K, ldb=ldb or K, ldc=ldc or N, sa=sa or M * K, sw=sw or N * K, sc=sc or M * N,
@@ -180,32 +182,32 @@ def tn(M, N, K, batch, lda=None, ldb=None, ldo=None, sa=None, sb=None, so=None, 
 for out in (False, True):
     s = "_f32" if out else ""
     CASES.append(case(f"nt_128{s}", "gemm_nt_batched", 1, nt(70, 40, 64, 3), dict(bias=False, out_f32=out), F128,
-                      "k_conv_fwd over gridDim.y batches, packed operands, :3047", ["fwd"]))
+                      "k_conv_fwd over gridDim.y batches, packed operands, plan_fwd's default", ["fwd"]))
     CASES.append(case(f"nt_256{s}", "gemm_nt_batched", 3, nt(300, 256, 64, 2), dict(bias=False, out_f32=out), F256,
-                      "k_conv_fwd256 batched (g_batch > 1: no persistent / split forms), packed operands, :3044", ["fwd256_batched"]))
+                      "k_conv_fwd256 batched (batch > 1: no persistent / split forms), packed operands, plan_fwd (use_gemm256 with the batch count)", ["fwd256_batched"]))
 CASES += [
     case("tn_small", "gemm_tn_batched", 9, tn(56, 32, 256, 70), dict(accumulate=False, out="bf16"), {},
-         "k_gemm_tn_small<4, 2> (one reduction tile, N <= 64, >= 64 batches), :3452", ["tn_small"]),
+         "k_gemm_tn_small<4, 2> (one reduction tile, N <= 64, >= 64 batches), plan_gemm_tn", ["tn_small"]),
     case("tn_small_f32", "gemm_tn_batched", 9, tn(33, 24, 128, 90), dict(accumulate=False, out="f32"), {},
-         "k_gemm_tn_small<3, 1> (f32 store, 33-row reduction), :3452", ["tn_small"]),
+         "k_gemm_tn_small<3, 1> (f32 store, 33-row reduction), plan_gemm_tn", ["tn_small"]),
     case("tn_stream", "gemm_tn_batched", 7, tn(100, 32, 256, 77), dict(accumulate=False, out="bf16"), {},
-         "k_gemm_tn_stream<bf16> (two reduction tiles, runs of batches per block), :3471", ["tn_stream"]),
+         "k_gemm_tn_stream<bf16> (two reduction tiles, runs of batches per block), plan_gemm_tn", ["tn_stream"]),
     case("tn_dma_acc", "gemm_tn_batched", 5, tn(1500, 64, 128, 3), dict(accumulate=True, out="f32"), {},
-         "k_conv_wgrad_dma<bf16> batched, f32 atomics into a non-zero out, :3489", ["wgrad_dma"]),
+         "k_conv_wgrad_dma<bf16> batched, f32 atomics into a non-zero out, plan_gemm_tn's last branch", ["wgrad_dma"]),
 ]
 # The attention pool's strided layouts at the bench's sizes (layers.py AttnPoolFn, K regions, H = 32 heads, C = 2048, D = 64, TP = 56):
 # 16 images = 8192 regions, 32 images = 16384 (operand views reaching 2 and 4 GiB through the per-batch bases)
 _ATTN = [  # (id, entry, kid, geometry, epilogue, why)
     ("nt_heads", "gemm_nt_batched", 1, nt(8192, 64, 2048, 32, 65536, 2048, 2048, 2048, 131072, 64), dict(bias=False, out_f32=False),
-     "o = Z @ Wv^T per head: A rows H*C apart, k_conv_fwd (64 columns), :3047"),
+     "o = Z @ Wv^T per head: A rows H*C apart, k_conv_fwd (64 columns), plan_fwd's default"),
     ("nt_regions", "gemm_nt_batched", 1, nt(32, 56, 2048, 8192, 2048, 2048, 56, 131072, 114688, 1792, a_off=65536), dict(bias=False, out_f32=True),
-     "S = U . tok^T per region, U = the second half of zu, f32 out, k_conv_fwd, :3047"),
+     "S = U . tok^T per region, U = the second half of zu, f32 out, k_conv_fwd, plan_fwd's default"),
     ("nt_qk", "gemm_nt_batched", 3, nt(8192, 2048, 64, 32, 2048, 2048, 131072, 64, 64, 2048, c_off=65536), dict(bias=False, out_f32=False),
-     "U = q0 @ Wk per head into the second half of zu (rows 2*H*C apart), k_conv_fwd256, :3044"),
+     "U = q0 @ Wk per head into the second half of zu (rows 2*H*C apart), k_conv_fwd256, plan_fwd (use_gemm256 with the batch count)"),
     ("tn_dwv", "gemm_tn_batched", 5, tn(8192, 64, 2048, 32, 2048, 65536, 2048, 64, 2048, 131072), dict(accumulate=True, out="f32"),
-     "dWv += dO^T Z per head: f32 atomics, B rows H*C apart, k_conv_wgrad_dma, :3489"),
+     "dWv += dO^T Z per head: f32 atomics, B rows H*C apart, k_conv_wgrad_dma, plan_gemm_tn's last branch"),
     ("tn_z", "gemm_tn_batched", 9, tn(56, 32, 2048, 8192, 32, 2048, 2048, 1792, 114688, 65536), dict(accumulate=False, out="bf16"),
-     "Z = P^T tok per region: k_gemm_tn_small<4, 2>, 32 batches per block, :3452"),
+     "Z = P^T tok per region: k_gemm_tn_small<4, 2>, 32 batches per block, plan_gemm_tn"),
 ]
 for id_, entry, kid, geom, epi, why in _ATTN:
     CASES.append(case(id_, entry, kid, geom, epi, {}, why + " (the bench's 16-image launch)",
@@ -214,7 +216,7 @@ for id_, entry, kid, geom, epi, why in _ATTN:
     CASES.append(case(id_ + "_32img", entry, kid, big, epi, {}, why + " (32 images: operands past 2 GiB)",
                       ["full_m", "batched_strided", "over_2gib"]))
 CASES.append(case("nt_mapper", "gemm_nt_batched", 3, nt(544, 1024, 1920, 16, 30720, 30720, 1024, 1920, 1920, 557056),
-                  dict(bias=False, out_f32=True), {}, "the mapper's per-head product (A, B rows 30720 apart), k_conv_fwd256, :3044",
+                  dict(bias=False, out_f32=True), {}, "the mapper's per-head product (A, B rows 30720 apart), k_conv_fwd256, plan_fwd (use_gemm256 with the batch count)",
                   ["batched_strided"]))
 
 REQUIRED_VARIANTS = [

@@ -200,3 +200,68 @@ def test_case_table_covers_every_instantiation_and_bench_shape():
     assert {c["kid"] for c in big} >= {1, 3, 5, 6, 9}
     for c in CASES.CASES:          # every case says what it targets and where dispatch selects it
         assert c.get("why"), c["id"]
+
+
+# ------------------------------------------------------------------------------------------------ the dispatch, replayed on the CPU
+SWITCHES = ("CDDMSL_GEMM256", "CDDMSL_FWD2", "CDDMSL_PERSIST", "CDDMSL_TAIL_SPLIT", "CDDMSL_SMALL_1X1", "CDDMSL_WGRAD_WS")
+_PTR = 1 << 20          # stands for an operand: in plan-only mode the entry points validate, plan and return -- nothing reads it
+
+
+def _plan_raw(L, entry, g, epi):
+    """one entry point of the raw C ABI, with the arguments hip.py's wrapper would pass for this geometry and epilogue
+    -> (status, cddmsl_last_kernel)"""
+    dt = {"bf16": 0, "f32": 1}[g["dtype"]]
+    es = 2 if dt == 0 else 4
+    if entry in ("conv_fwd", "conv_wgrad"):
+        N, H, W, Cin, Cout, KH, KW, s, p, pool = (g[k] for k in ("N", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "pad", "pool"))
+    if entry == "conv_fwd":
+        opt = lambda on: _PTR if on else None
+        if epi["emit8"]:
+            st = L.cddmsl_conv_fwd_q8(_PTR, _PTR, _PTR, opt(epi["scale"]), opt(epi["bias"]), opt(epi["residual"]), opt(epi["relu_mask"]),
+                                      N, H, W, Cin, Cout, KH, KW, s, p, int(epi["relu"]), _PTR, _PTR, _PTR, None)
+        else:
+            bits = int(epi["out_f32"]) | (2 if epi["residual"] == "f32" and dt == 0 else 0) | (4 if epi["residual"] == "pooled" else 0)
+            st = L.cddmsl_conv_fwd(_PTR, _PTR, _PTR, opt(epi["scale"]), opt(epi["bias"]), opt(epi["residual"]), opt(epi["relu_mask"]),
+                                   N, H, W, Cin, Cout, KH, KW, s, p, int(pool), Cout, Cout, Cout, int(epi["relu"]), bits, dt, None)
+    elif entry == "conv_wgrad":
+        st = L.cddmsl_conv_wgrad(_PTR, _PTR, _PTR, _PTR if epi["scale"] else None, N, H, W, Cin, Cout, KH, KW, s, p, int(pool), Cout, dt, None)
+    elif entry == "gemm_nt_batched":
+        off = lambda k: _PTR + g.get(k, 0) * es
+        st = L.cddmsl_gemm_nt_batched(off("a_off"), off("b_off"), off("c_off"), None, g["M"], g["N"], g["K"], g["lda"], g["ldb"], g["ldc"],
+                                      g["batch"], g["sa"], g["sw"], g["sc"], int(epi["out_f32"] and dt == 0), dt, None)
+    elif entry == "gemm_tn_batched":
+        mode = 0 if epi["accumulate"] else 1 if epi["out"] == "f32" else 2
+        st = L.cddmsl_gemm_tn_batched(_PTR, _PTR, _PTR, g["M"], g["N"], g["K"], g["lda"], g["ldb"], g["ldo"], g["batch"], g["sa"], g["sb"],
+                                      g["so"], mode, dt, None)
+    else:
+        raise AssertionError(f"the raw replay has no call for entry point {entry!r}")
+    return st, L.cddmsl_last_kernel()
+
+
+def test_dispatch_replayed_through_the_raw_abi_in_plan_only_mode(monkeypatch):
+    """every launch recorded from the bench step and every case of the GPU table -- under the case's switches, the others cleared --
+    goes through the raw C ABI in plan-only mode (no GPU: validate, plan, return): status CDDMSL_OK and the recorded / expected
+    kernel id.  Every entry point of the two tables has a raw call in _plan_raw (an unknown one fails there, it is not skipped)."""
+    import __graft_entry__ as ge
+    ge.build()
+    from cddmsl_amd import hip
+    L = hip._L()
+    with open(os.path.join(GOLDEN, "bench_gemm_launches.json")) as fh:
+        rec = json.load(fh)["entries"]
+    todo = [(f"recorded launch {i}", e["entry"], e["geometry"], e["epilogue"], {}, e["kernel_id"]) for i, e in enumerate(rec)]
+    todo += [(c["id"], c["entry"], c["geom"], dict({"emit8": False}, **c["epi"]), c["env"], c["kid"]) for c in CASES.CASES]
+    assert len(rec) >= 367 and len(CASES.CASES) >= 100
+    bad = []
+    was = L.cddmsl_plan_only(1)
+    try:
+        for name, entry, g, epi, env, kid in todo:
+            for k in SWITCHES:
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            st, got = _plan_raw(L, entry, g, epi)
+            if (st, got) != (0, kid):
+                bad.append((name, entry, g, epi, env, f"status {st}, kernel {got}, expected {kid}"))
+    finally:
+        L.cddmsl_plan_only(was)
+    assert not bad, bad
