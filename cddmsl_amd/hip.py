@@ -24,6 +24,8 @@ def _L():
         L.cddmsl_last_kernel.argtypes = []
         L.cddmsl_plan_only.argtypes = [ci]
         L.cddmsl_conv_fwd.argtypes = [vp] * 7 + [ci] * 16 + [vp]
+        L.cddmsl_bottleneck64_ok.argtypes = [ci] * 4
+        L.cddmsl_bottleneck64_fwd.argtypes = [vp] * 17 + [ci] * 4 + [vp]
         L.cddmsl_conv_wgrad.argtypes = [vp] * 4 + [ci] * 12 + [vp]
         L.cddmsl_set_workspace.argtypes = [vp, c_long]
         L.cddmsl_weight_prep.argtypes = [vp] * 4 + [ci] * 5 + [vp]
@@ -176,7 +178,8 @@ class _Profiler:
 
 PROFILE = _Profiler()
 # cddmsl_last_kernel() ids -> profiler row names (one row per KERNEL, so the roofline object describes one kernel)
-_CONV_KERNEL = {10: "k_conv_fwd256_fp8", 11: "k_conv_fwd2", 1: "k_conv_fwd", 2: "k_conv_fwd_reg", 3: "k_conv_fwd256", 4: "k_conv_wgrad", 5: "k_conv_wgrad_dma", 6: "k_wgrad256", 7: "k_gemm_tn_stream", 8: "k_conv3x3_small", 9: "k_gemm_tn_small", 12: "k_wgrad256_fp8"}
+_CONV_KERNEL = {10: "k_conv_fwd256_fp8", 11: "k_conv_fwd2", 1: "k_conv_fwd", 2: "k_conv_fwd_reg", 3: "k_conv_fwd256", 4: "k_conv_wgrad", 5: "k_conv_wgrad_dma", 6: "k_wgrad256", 7: "k_gemm_tn_stream", 8: "k_conv3x3_small", 9: "k_gemm_tn_small", 12: "k_wgrad256_fp8",
+                13: "k_bottleneck64"}
 
 
 def _timed(name):
@@ -280,6 +283,47 @@ def conv_fwd(x, w, scale=None, bias=None, residual=None, relu=False, relu_mask=N
     if y8 is not None:
         y._fp8 = (y8, emit8[0].data_ptr())
     return y
+
+
+def bottleneck64_ok(o1, w2, w3, wd=None, w1n=None):
+    """does the fused frozen-bottleneck kernel take this block?  bf16, packed tensors, 64 planes (conv2 64 -> 64 3x3, conv3 64 -> 256,
+    an optional 64 -> 256 downsample convolution and an optional 256 -> 64 conv1 of the next block), every tensor below 2 GiB."""
+    if not (o1.is_cuda and o1.dtype == torch.bfloat16 and o1.dim() == 4 and o1.is_contiguous() and o1.shape[3] == 64):
+        return False
+    want = ((w2, (64, 3, 3, 64)), (w3, (256, 1, 1, 64)), (wd, (256, 1, 1, 64)), (w1n, (64, 1, 1, 256)))
+    if any(w is not None and (tuple(w.shape) != s or w.dtype != torch.bfloat16 or not w.is_contiguous()) for w, s in want):
+        return False
+    N, H, W, _ = o1.shape
+    return N > 0 and bool(_L().cddmsl_bottleneck64_ok(N, H, W, 0))
+
+
+def bottleneck64_fwd(o1, w2, bn2, w3, bn3, residual=None, x0=None, wd=None, bnd=None, w1n=None, bn1n=None):
+    """One frozen 64-plane Bottleneck behind its conv1 in one launch (``bottleneck64_ok``): o1 [N,H,W,64] -> out [N,H,W,256] =
+    relu(bn3(conv3(relu(bn2(conv2(o1))))) + residual), bit-identical to the three ``conv_fwd`` launches.  The residual is given
+    or, with ``wd`` / ``bnd``, computed as bnd(x0 . wd) from the block's input ``x0``.  With ``w1n`` / ``bn1n`` (conv1 of the next
+    block) also returns o1n [N,H,W,64] = relu(bn1n(out . w1n)); else None.  bn* = (scale, bias) f32."""
+    require_cuda(o1, w2, w3, residual, x0, wd, w1n)
+    assert bottleneck64_ok(o1, w2, w3, wd, w1n) and (residual is None) != (wd is None)
+    N, H, W, _ = o1.shape
+    for t, c in ((residual, 256), (x0 if wd is not None else None, 64)):
+        assert t is None or (t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == (N, H, W, c))
+    for bn, c in ((bn2, 64), (bn3, 256), (bnd, 256), (bn1n, 64)):
+        assert bn is None or all(v.dtype == torch.float32 and v.numel() == c and v.is_contiguous() and v.is_cuda for v in bn)
+    assert (wd is None) == (bnd is None) and (w1n is None) == (bn1n is None) and (wd is None or x0 is not None)
+    out = torch.empty((N, H, W, 256), device=o1.device, dtype=o1.dtype)
+    o1n = torch.empty((N, H, W, 64), device=o1.device, dtype=o1.dtype) if w1n is not None else None
+    sd, bd = bnd if bnd is not None else (None, None)
+    s1n, b1n = bn1n if bn1n is not None else (None, None)
+    e0 = PROFILE.begin(name="k_bottleneck64") if PROFILE.on else None
+    check(_L().cddmsl_bottleneck64_fwd(ptr(o1), ptr(w2), ptr(bn2[0]), ptr(bn2[1]), ptr(w3), ptr(bn3[0]), ptr(bn3[1]), ptr(residual),
+                                       ptr(x0 if wd is not None else None), ptr(wd), ptr(sd), ptr(bd), ptr(w1n), ptr(s1n), ptr(b1n),
+                                       ptr(out), ptr(o1n), N, H, W, 0, stream_ptr()), "cddmsl_bottleneck64_fwd")
+    M = N * H * W
+    kn = 576 * 64 + 64 * 256 + (64 * 256 if wd is not None else 0) + (256 * 64 if w1n is not None else 0)
+    # algorithmic HBM bytes: o1, the residual or x0, out, o1n and the weights once each (o2 and the computed residual never exist)
+    PROFILE.end(e0, "k_bottleneck64", 2.0 * M * kn, (M, 256, 576, 3, int(wd is not None), int(w1n is not None)),
+                nbytes=float(2 * M * (64 + (64 if wd is not None else 256) + 256 + (64 if w1n is not None else 0)) + 2 * kn))
+    return out, o1n
 
 
 def conv_emit8_ok(M, Cout, KH, KW, Cin_chunks_ok=True):

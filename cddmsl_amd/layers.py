@@ -656,11 +656,53 @@ class ResStageFn(torch.autograd.Function):
         return gs, None, None, None, None, None
 
 
+def _fused_stage_ok(x, blocks, out_spec):
+    """Can this save-nothing stage run on ``hip.bottleneck64_fwd``?  bf16 without fp8, every block a packed stride-1 Bottleneck of
+    64 planes (conv2 64 -> 64 3x3, expansion to 256), a downsample convolution on the first block only.  CDDMSL_FUSED_BOTTLENECK=0
+    (read per call, so one process can A/B) keeps the separate launches."""
+    if os.environ.get("CDDMSL_FUSED_BOTTLENECK", "1") == "0" or out_spec is not None:
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous()):
+        return False
+    cin = x.shape[3]
+    for bi, bp in enumerate(blocks):
+        if bp.fp8 or bp.stride != 1 or any(v is None for b in bp.bn[:3] for v in b):
+            return False
+        if tuple(_ohwi(bp.w[0]).shape) != (64, 1, 1, cin) or tuple(_ohwi(bp.w[1]).shape) != (64, 3, 3, 64) or tuple(_ohwi(bp.w[2]).shape) != (256, 1, 1, 64):
+            return False
+        if bp.w[3] is not None:
+            if bi > 0 or cin != 64 or tuple(_ohwi(bp.w[3]).shape) != (256, 1, 1, 64) or any(v is None for v in bp.bn[3]):
+                return False
+        elif cin != 256:
+            return False
+        cin = 256
+    return bool(blocks) and bool(hip._L().cddmsl_bottleneck64_ok(x.shape[0], x.shape[1], x.shape[2], 0))
+
+
+def _fused_stage_forward(x, blocks):
+    """The stage as conv1 of its first block plus ONE launch per block: conv2, conv3 with the residual add (the first block's
+    downsample convolution computed in the kernel) and conv1 of the next block; o2 and the downsample result never reach HBM and
+    a block's output is read once.  Bit-identical to ``_block_forward``."""
+    T = x.dtype
+    wf = lambda pw: pw.get(T, need_dgrad=False)[0]
+    o1 = conv_fwd_auto(x, blocks[0].pw[0], blocks[0].bn[0][0], blocks[0].bn[0][1], False, relu=True)
+    cur = x
+    for bi, bp in enumerate(blocks):
+        nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
+        kw = dict(x0=cur, wd=wf(bp.pw[3]), bnd=bp.bn[3]) if bp.pw[3] is not None else dict(residual=cur)
+        if nxt is not None:
+            kw.update(w1n=wf(nxt.pw[0]), bn1n=nxt.bn[0])
+        cur, o1 = hip.bottleneck64_fwd(o1, wf(bp.pw[1]), bp.bn[1], wf(bp.pw[2]), bp.bn[2], **kw)
+    return cur
+
+
 def res_stage(x, blocks, frozen, out_grad_premasked=False, out_spec=None):
     """Runs a residual stage.  Frozen stages (FREEZE_AT) and no-grad calls keep no activations.  ``out_spec`` (hip.OutSpec): the
     stage output is written into one half of a buffer shared with a second pass (no concatenation copy later)."""
     px0 = getattr(x, "_pooled2", None)               # 2x2-pooled copy of x supplied by its producer (roi_align)
     if frozen or not torch.is_grad_enabled():
+        if _fused_stage_ok(x, blocks, out_spec):
+            return _fused_stage_forward(x, blocks)
         cur = x
         for bi, bp in enumerate(blocks):
             cur, _ = _block_forward(cur, bp, False, px0 if bi == 0 else None, blocks[bi + 1].pw[0] if bi + 1 < len(blocks) else None,

@@ -40,6 +40,20 @@ int cddmsl_abi_version(void);
 int cddmsl_conv_fwd(const void* x, const void* w, void* y, const float* scale, const float* bias, const void* residual,
                     const void* relu_mask, int Nimg, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad,
                     int pool, int ldy, int ldr, int ldm, int relu, int out_f32, int dtype, void* stream);
+/* One frozen 64-plane CLIP Bottleneck behind its conv1 as ONE launch (clip_backbone.py:57-70 at stride 1; bf16, forward only):
+ *   o2  = relu(o1 (*) w2 * s2 + b2)                   3x3 pad 1, 64 -> 64, never written to memory
+ *   out = relu(o2 . w3 * s3 + b3 + residual)          [Nimg][H][W][256]
+ *   o1n = relu(out . w1n * s1n + b1n)                 [Nimg][H][W][64]: conv1 of the NEXT block, when w1n is given
+ * The residual is either read (`residual`, [Nimg][H][W][256]) or, when wd is given, computed as x0 . wd * sd + bd from the
+ * block's 64-channel input x0 (the downsample convolution, rounded to bf16 as its own launch would store it): exactly one of
+ * the two.  Weights as cddmsl_conv_fwd takes them ([Cout][KH][KW][Cin] bf16), scale / bias f32 per output channel, required.
+ * Results are bit-identical to the separate cddmsl_conv_fwd launches.  cddmsl_bottleneck64_ok: 1 when the shape / dtype is taken
+ * (dtype 0, every tensor below 2 GiB); anything else is CDDMSL_ERR_ARG -- the caller keeps the separate launches. */
+int cddmsl_bottleneck64_ok(int Nimg, int H, int W, int dtype);
+int cddmsl_bottleneck64_fwd(const void* o1, const void* w2, const float* s2, const float* b2, const void* w3, const float* s3,
+                            const float* b3, const void* residual, const void* x0, const void* wd, const float* sd,
+                            const float* bd, const void* w1n, const float* s1n, const float* b1n, void* out, void* o1n,
+                            int Nimg, int H, int W, int dtype, void* stream);
 /* Device scratch for the weight-gradient kernels' split reductions (no counterpart in the reference: ATen's conv backward owns its
  * workspace, aten/src/ATen/native/cudnn).  With `bytes` of 16-byte-aligned device memory registered, a split reduction stores its
  * partial tiles there and a second kernel sums them into dW (deterministic; f32 atomics otherwise, and whenever the launch needs more
@@ -57,7 +71,7 @@ int cddmsl_gemm_tn_batched(const void* a, const void* b, void* out, int M, int N
                            long sb, long so, int mode, int dtype, void* stream);
 /* diagnostic: the kernel the calling thread's last conv / GEMM entry point launched -- 1 k_conv_fwd (128x128 LDS-DMA),
  * 2 k_conv_fwd_reg (fused avg-pool loader), 3 k_conv_fwd256 (256x256 ping-pong), 4 k_conv_wgrad, 5 k_conv_wgrad_dma,
- * 6 k_wgrad256, 7 k_gemm_tn_stream, 8 k_conv3x3_small (few-channel 3x3 layers: the CLIP stem), 9 k_gemm_tn_small.  bench.py uses it to attribute HIP-event times to kernels. */
+ * 6 k_wgrad256, 7 k_gemm_tn_stream, 8 k_conv3x3_small (few-channel 3x3 layers: the CLIP stem), 9 k_gemm_tn_small, 13 k_bottleneck64 (cddmsl_bottleneck64_fwd).  bench.py uses it to attribute HIP-event times to kernels. */
 int cddmsl_last_kernel(void);
 /* diagnostic: while on (per thread), the conv / GEMM entry points above choose their kernel (cddmsl_last_kernel) and return
  * without launching; bench.py asks this way BEFORE a launch whether it is the kernel whose launches it is timing, so only those
