@@ -5,7 +5,7 @@
 //                   FastRCNNOutputLayers.forward (detectron2/modeling/roi_heads/fast_rcnn.py:546-572) on e4m3 operands,
 //                   v_mfma_scale_f32_32x32x64_f8f6f4 with f32 accumulation, operands straight from global memory (each byte is
 //                   read once: nothing to stage)
-// The convolutions themselves run on k_conv_fwd256<fp8e4> (gemm_conv.hip).
+// The convolutions themselves run on k_conv_fwd256<fp8e4> (conv_fwd256.hip).
 #include "common.h"
 
 namespace {

@@ -5,7 +5,7 @@
 //   FastRCNNOutputLayers.forward  modeling/roi_heads/fast_rcnn.py:546-572   x/||x|| . w_c/||w_c|| / T, bg logit 0
 //   v2l_contrastive               modeling/meta_arch/rcnn.py:308-317,458-468 rows / norm, S = A B^T,
 //                                 0.5 * (CE(S, arange) + CE(S^T, arange))
-// The S = A B^T contraction itself runs on the exact-f32 MFMA GEMM (gemm_conv.hip); these kernels are the
+// The S = A B^T contraction itself runs on the exact-f32 MFMA GEMM (conv_fwd.hip / conv_fwd256.hip, dispatched by gemm_conv.hip); these kernels are the
 // row-wise pieces around it.  Everything is f32: T = 0.01 multiplies logits by 100, so no bf16 here.
 #include "common.h"
 

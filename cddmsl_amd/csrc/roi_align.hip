@@ -191,7 +191,7 @@ __global__ void k_roi_align_fwd(const char* x, const float* rois, char* y, char*
 #pragma unroll
       for (int q = 0; q < VEC; ++q) {
         const float sq = esc[c * VEC + q], bq = ebi[c * VEC + q];
-        acc[q] = sizeof(T) == 2 ? __builtin_fmaf(acc[q], sq, bq) : acc[q] * sq + bq;       // (as the conv epilogues: gemm_conv.hip affine<T>)
+        acc[q] = sizeof(T) == 2 ? __builtin_fmaf(acc[q], sq, bq) : acc[q] * sq + bq;       // (as the conv epilogues: gemm_common.h affine<T>)
         if (relu) acc[q] = fmaxf(acc[q], 0.f);
       }
     }

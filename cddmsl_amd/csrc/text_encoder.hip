@@ -1,5 +1,5 @@
 // CLIP text encoder (RegionCLIP's language tower: detectron2/modeling/backbone/clip_backbone.py:273-317,732-877), forward only --
-// the reference freezes it (clip_rcnn.py:438-439).  The linears run on the conv/GEMM kernels (gemm_conv.hip) and the two per-layer
+// the reference freezes it (clip_rcnn.py:438-439).  The linears run on the conv/GEMM kernels (gemm_conv.hip and the kernel files it dispatches to) and the two per-layer
 // LayerNorms on the mapper's LayerNorm kernel (losses.hip), and the token + positional embedding (encode_text's first two lines) on
 // pos_embed (gpt2.hip); this file holds what those do not cover:
 //   attn_causal   o = softmax(q k^T dh^-0.5 + mask) v per (sequence, head), keys j <= query i (build_attention_mask), dh = 64

@@ -1,7 +1,7 @@
 """Exact references and per-element error bounds for the attention kernels (imported by the attention tests; not a conftest).
 
 Every reference takes the operands a kernel was given, as stored (bf16 or f32), and computes in float64.  Every bound follows the
-kernel's own rounding points (cddmsl_amd/csrc/attn_small.hip, elementwise.hip, gemm_conv.hip k_gemm_tn_small MODE 3).  Units:
+kernel's own rounding points (cddmsl_amd/csrc/attn_small.hip, elementwise.hip, conv_wgrad.hip k_gemm_tn_small MODE 3).  Units:
 u = 2^-24 (f32), u_b = 2^-8 (the unit roundoff of a round-to-nearest-even bf16 store), C_ACC the f32 accumulation constant of
 tests/exact_gemm.py (a sum of products is off by at most C_ACC u sum|a b|).
 

@@ -1,6 +1,6 @@
 """Exact references and an error bound for the bf16 convolution / GEMM kernels (imported by the exact-product tests; not a conftest).
 
-Every kernel of cddmsl_amd/csrc/gemm_conv.hip multiplies bf16 operands exactly and sums the products in f32, so its result can be
+Every kernel behind the dispatch of cddmsl_amd/csrc/gemm_conv.hip (conv_fwd.hip, conv_fwd256.hip, conv_wgrad.hip, bottleneck64.hip) multiplies bf16 operands exactly and sums the products in f32, so its result can be
 held to the float64 product of the operands it was given -- not to another library's f32 convolution:
 
   |got - exact| <= u_out * |exact| + C_ACC * 2^-24 * |scale| * sum|a*b| + 2^-24 * (|bias| + |residual| + |dW before|)

@@ -3,8 +3,8 @@ tests/golden/bench_gemm_launches.json and every kernel instantiation has a Tier 
 
 A case: entry point, the kernel id dispatch must pick (cddmsl_last_kernel; hip.py _CONV_KERNEL), the per-call switches that force
 it, the geometry (the keys tools/record_gemm_launches.py writes), the epilogue flags, the tiers it runs in, the variants it covers
-and -- ``why`` -- which variant it targets and which function of the dispatch in cddmsl_amd/csrc/gemm_conv.hip selects it (plan_* choose the
-kernel, launch_* its instantiation).
+and -- ``why`` -- which variant it targets and which function of the dispatch selects it (plan_* in cddmsl_amd/csrc/gemm_conv.hip choose the
+kernel, launch_* in the kernel's own file -- conv_fwd.hip, conv_fwd256.hip, conv_wgrad.hip -- its instantiation).
 Tier A: small-integer operands, every partial sum exact in f32, output bit-equal to the exact value rounded once.
 Tier B: Gaussian operands, held to exact_gemm.check_bound and exact_gemm.rounding_bias."""
 

@@ -1,12 +1,13 @@
 #!/bin/bash
 # usage (GPU box, from the repo root): [SRC=roi_align] [OUT=ab_out] bash tools/ab_rebuild.sh "<extra hipcc flags>" <tag>  -- bench, rebuild one object with the flags, relinks the library, runs the bench
+# SRC: the unit to rebuild, default conv_fwd256 (k_conv_fwd256, the kernel row the summary prints)
 set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 OUT=${OUT:-ab_out}; mkdir -p $OUT
 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-forward-roofline > $OUT/ab_base1.json 2> $OUT/ab.err
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -ffp-contract=off $1 -I include -c cddmsl_amd/csrc/${SRC:-gemm_conv}.hip -o /tmp/gemm_conv_ab.o
-mkdir -p /tmp/objs && cp build/obj/*.o /tmp/objs/ && cp /tmp/gemm_conv_ab.o /tmp/objs/${SRC:-gemm_conv}.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -ffp-contract=off $1 -I include -c cddmsl_amd/csrc/${SRC:-conv_fwd256}.hip -o /tmp/gemm_conv_ab.o
+mkdir -p /tmp/objs && cp build/obj/*.o /tmp/objs/ && cp /tmp/gemm_conv_ab.o /tmp/objs/${SRC:-conv_fwd256}.o
 cp cddmsl_amd/libcddmsl_hip.so /tmp/lib_base.so
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC /tmp/objs/*.o -o cddmsl_amd/libcddmsl_hip.so
 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-forward-roofline > $OUT/ab_var1.json 2>> $OUT/ab.err

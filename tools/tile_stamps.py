@@ -1,9 +1,9 @@
 """Where a 256x256 tile of k_conv_fwd256 spends its time: per wave, s_memrealtime stamps (the constant 100 MHz reference) at kernel entry,
-main-loop start, main-loop end and exit (after the wave's stores have left), from a DIAGNOSTIC build of the library (-DCDDMSL_TILE_STAMPS on gemm_conv.hip;
+main-loop start, main-loop end and exit (after the wave's stores have left), from a DIAGNOSTIC build of the library (-DCDDMSL_TILE_STAMPS on every unit that includes gemm_common.h -- it adds a member to ConvArgs / WgradArgs, which they share;
 the shipped library carries no stamps).  Reports, per shape, the medians over all waves of prologue / main loop / epilogue in
 microseconds and the launch's event time.
 
-  build:  for f in cddmsl_amd/csrc/*.hip: hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off [-DCDDMSL_TILE_STAMPS for gemm_conv] -c ...
+  build:  for f in cddmsl_amd/csrc/*.hip: hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off [-DCDDMSL_TILE_STAMPS for gemm_conv, conv_fwd, conv_fwd256, conv_wgrad, bottleneck64] -c ...
           hipcc -shared -fPIC *.o -o scratch/libstamps.so
   run:    python tools/tile_stamps.py scratch/libstamps.so
 """
