@@ -32,7 +32,8 @@ __global__ void k_rpn_decode(const int* order, const float* deltas, const float*
   const float* d = deltas + ((long)n * total + a) * 4;
   float w = ax1 - ax0, h = ay1 - ay0;
   float cx = ax0 + 0.5f * w, cy = ay0 + 0.5f * h;
-  float dx = d[0] / wx, dy = d[1] / wy, dw = fminf(d[2] / ww, clampv), dh = fminf(d[3] / wh, clampv);
+  float dx = d[0] / wx, dy = d[1] / wy, dw = d[2] / ww, dh = d[3] / wh;
+  dw = dw > clampv ? clampv : dw; dh = dh > clampv ? clampv : dh;   // torch.clamp(max=): a NaN stays a NaN (fminf would return the clamp)
   float pcx = dx * w + cx, pcy = dy * h + cy;
   float pw = expf(dw) * w, phh = expf(dh) * h;
   float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * phh, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * phh;
@@ -331,11 +332,14 @@ extern "C" int cddmsl_anchors(const float* cell, float* out, int Hf, int Wf, int
 // pattern in the low word; radix sort is stable, so equal scores keep the lower index first) instead of rocPRIM's segmented
 // sort, which handles 16 long segments with little parallelism (1.4 ms for 16 x 62 250 keys; this: ~0.2 ms).  Only the
 // 32 + ceil(log2 N) significant key bits are sorted.  Call with temp == NULL to get the workspace size in *temp_bytes.
+// Signed zeros are equal scores (as for torch.sort): -0.0 is sorted as +0.0 and comes back as +0.0 in keys_out; every other key
+// comes back bit for bit.  NaN keys have no defined order.
 __global__ void k_sort_make_keys(const float* keys, unsigned long long* k64, int* idx, int N, int total) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)N * total) return;
   const unsigned img = (unsigned)(i / total);
-  const unsigned f = __float_as_uint(keys[i]);
+  unsigned f = __float_as_uint(keys[i]);
+  if (f == 0x80000000u) f = 0u;                                            // -0.0 == +0.0: one key, so the lower index stays first
   const unsigned asc = f ^ ((f >> 31) ? 0xffffffffu : 0x80000000u);      // unsigned order == float order
   k64[i] = ((unsigned long long)img << 32) | (unsigned)(~asc);              // ascending composite == (image, descending score)
   idx[i] = (int)(i - (long)img * total);

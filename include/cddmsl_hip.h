@@ -160,7 +160,8 @@ int cddmsl_roi_align_backward_nchw_anyorder(const void* grad, const float* rois,
 int cddmsl_anchors(const float* cell, float* out, int Hf, int Wf, int A, float stride, float offset, void* stream);
 /* stable descending sort of every row of keys_in [N][total] (torch.sort(descending=True, stable=True) per image,
  * proposal_utils.py:66-70): one device-wide radix sort over (image, score) composite keys; `offsets` is unused (dense rows);
- * temp == NULL returns the workspace size in *temp_bytes */
+ * temp == NULL returns the workspace size in *temp_bytes.  +0.0 and -0.0 are equal scores (lower index first); a -0.0 key is
+ * returned as +0.0 in keys_out, every other key bit for bit.  NaN keys have no defined order. */
 int cddmsl_sort_desc(const float* keys_in, float* keys_out, int* idx_scratch, int* order_out, const int* offsets, int N,
                      int total, void* temp, size_t* temp_bytes, void* stream);
 int cddmsl_rpn_decode(const int* order, const float* deltas, const float* cell, const int* img_hw, float* boxes,
