@@ -84,7 +84,9 @@ constexpr int ROI_MAXS = 256;     // samples per axis held in LDS (adaptive samp
 // outputs in avgpool2_fwd's order, so it is bit-identical to pooling the stored map.
 // ``y`` may be absent (RP = 2: only the pooled map is wanted); ``esc`` / ``ebi`` (per channel) and ``relu``: y = relu?(esc * v + ebi)
 // applied to the pooled-over-samples value before it is rounded -- the FrozenBN + ReLU of a 1x1 convolution that was applied to
-// the feature map BEFORE the pooling (both are linear: see cddmsl_roi_align_forward_affine).
+// the feature map BEFORE the pooling (both are linear: see cddmsl_roi_align_forward_affine).  Pooled-only (``y`` absent): the
+// affine follows the 2x2 average instead, yp = esc * avgpool2(bins) + ebi, as in k_roi_align_fwd_rows<2> -- one multiply-add per
+// pooled element instead of four, and the bins stay what they are without an affine (no ReLU there: the host refuses it).
 template <typename T, int RP>
 __global__ void k_roi_align_fwd(const char* x, const float* rois, char* y, char* yp, int* dbg_grid, int N, int H, int W, int cch,
                                 int ph, int pw, float scale, int sampling_ratio, int aligned, const float* esc, const float* ebi,
@@ -187,7 +189,7 @@ __global__ void k_roi_align_fwd(const char* x, const float* rois, char* y, char*
 #pragma unroll
       for (int q = 0; q < VEC; ++q) acc[q] /= count;
     }
-    if (esc) {
+    if (esc && !(RP == 2 && !y)) {
 #pragma unroll
       for (int q = 0; q < VEC; ++q) {
         const float sq = esc[c * VEC + q], bq = ebi[c * VEC + q];
@@ -213,6 +215,13 @@ __global__ void k_roi_align_fwd(const char* x, const float* rois, char* y, char*
       Vec<T>::unpack(outp[RP - 1][0], a2); Vec<T>::unpack(outp[RP - 1][RP - 1], a3);
 #pragma unroll
       for (int q = 0; q < VEC; ++q) o[q] = ((a0[q] + a1[q]) + (a2[q] + a3[q])) * 0.25f;
+      if (esc && !y) {
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) {
+          const float sq = esc[c * VEC + q], bq = ebi[c * VEC + q];
+          o[q] = sizeof(T) == 2 ? __builtin_fmaf(o[q], sq, bq) : o[q] * sq + bq;
+        }
+      }
       ((u32x4*)yp)[(((long)k * (ph / 2) + i0 / 2) * (pw / 2) + j0 / 2) * cch + c] = Vec<T>::pack(o);
     }
   }
@@ -256,8 +265,17 @@ __global__ __launch_bounds__(256) void k_roi_align_fwd_rows(const char* x, const
   __shared__ float s_ywl[ROW_MAXY], s_ywh[ROW_MAXY];
   const int ny = RP * g.gh, nx = pw * g.gw;                    // y samples of this (pooled) row; x samples of the whole row
   const int opw = pw / RP;                                     // outputs per row
-  const int c = threadIdx.x;                                   // channel chunk of this lane
+  const int c = blockIdx.y * blockDim.x + threadIdx.x;        // channel chunk of this lane
   const bool inb = g.b >= 0 && g.b < N;
+  // this lane's scale / bias, requested before anything else: they arrive under the table building (see the wait in front of the walk)
+  float sq[8], bq[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { sq[q] = 1.f; bq[q] = 0.f; }
+  if (esc) {                                                   // (block-uniform; lanes without a chunk read the last one's)
+    const int cl = min(c, cch - 1);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { sq[q] = esc[cl * 8 + q]; bq[q] = ebi[cl * 8 + q]; }
+  }
   // a sampling grid beyond the tables, or an inverted box (x1 < x0: its x samples DESCEND along the row, or its adaptive grid is negative),
   // which the sliding window below cannot walk (block-uniform): bins evaluated tap by tap
   if (nx > ROI_MAXS || 2 * ny > ROW_MAXY || g.bw < 0.f) {
@@ -287,7 +305,7 @@ __global__ __launch_bounds__(256) void k_roi_align_fwd_rows(const char* x, const
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         o[q] = acc[q] * inv;
-        if (esc) { o[q] = __builtin_fmaf(o[q], esc[c * 8 + q], ebi[c * 8 + q]); if (relu) o[q] = fmaxf(o[q], 0.f); }
+        if (esc) { o[q] = __builtin_fmaf(o[q], sq[q], bq[q]); if (relu) o[q] = fmaxf(o[q], 0.f); }
       }
       ((u32x4*)y)[(((long)k * nrb + i0 / RP) * opw + jo) * cch + c] = Vec<__bf16>::pack(o);
     }
@@ -344,9 +362,6 @@ __global__ __launch_bounds__(256) void k_roi_align_fwd_rows(const char* x, const
   const int nrow = __builtin_amdgcn_readfirstlane(s_n[0]);
   const int first = __builtin_amdgcn_readfirstlane(s_n[1]);
   const float inv = 1.0f / ((float)max(g.gh * g.gw, 1) * (float)(RP * RP));
-  float sq[8], bq[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) { sq[q] = esc ? esc[c * 8 + q] : 1.f; bq[q] = ebi ? ebi[c * 8 + q] : 0.f; }
   const u32x4* xb = (const u32x4*)x + (long)(inb ? g.b : 0) * H * W * cch + c;
   auto rload = [&](int px, float* R) {                         // R = sum over the merged rows of wy * x[py][px]   (wave-uniform px)
 #pragma unroll
@@ -391,6 +406,12 @@ __global__ __launch_bounds__(256) void k_roi_align_fwd_rows(const char* x, const
       for (int q = 0; q < 8; ++q) R[q] = __builtin_fmaf(wyr[e], v[q], R[q]);
     }
   };
+  // scale / bias have to BE there before the walk, on every path into it: the compiler tracks outstanding loads per register and
+  // merges paths pessimistically, so with the two still formally in flight on the path around `any` it put s_waitcnt vmcnt(0) in
+  // front of the affine of every output -- which also drains the column requested one slide ahead.  With the affine the 2048-channel
+  // pooled forward ran 1.12 ms against 1.06 ms without (1024 channels: 0.54 against 0.47); an explicit wait here, which the
+  // compiler's bookkeeping sees, leaves the outputs without one.  (vmcnt(0), expcnt and lgkmcnt left alone: gfx9 encoding.)
+  __builtin_amdgcn_s_waitcnt(0x0F70);                          // (unconditional: under `if (esc)` it is one more path to merge)
   if (any) {
     rload(cur, R0); rload(min(cur + 1, W - 1), R1);
     if (ahead) issue(min(cur + 2, W - 1));
@@ -426,10 +447,14 @@ __global__ __launch_bounds__(256) void k_roi_align_fwd_rows(const char* x, const
     if (--left == 0) {
       float o[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        o[q] = acc[q] * inv;
-        if (esc) { o[q] = __builtin_fmaf(o[q], sq[q], bq[q]); if (relu) o[q] = fmaxf(o[q], 0.f); }
-        acc[q] = 0.f;
+      for (int q = 0; q < 8; ++q) { o[q] = acc[q] * inv; acc[q] = 0.f; }
+      if (esc) {                                               // (block-uniform: one branch per output, not one per element)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o[q] = __builtin_fmaf(o[q], sq[q], bq[q]);
+        if (relu) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) o[q] = fmaxf(o[q], 0.f);
+        }
       }
       // (non-temporal: the crops are read by a later launch; stored this way they stop evicting the feature map every RoI re-reads --
       // 1.42 -> 1.36 ms per step and -0.3 ms on the step, same-box A/B)
@@ -606,6 +631,9 @@ static int roi_align_forward_impl(const void* x, const float* rois, void* y, voi
   if ((dtype != 0 && dtype != 1) || (C * es) % 16 || H <= 0 || W <= 0 || ph <= 0 || pw <= 0 || K < 0 || N < 0)
     return CDDMSL_ERR_ARG;
   if ((esc == nullptr) != (ebi == nullptr)) return CDDMSL_ERR_ARG;
+  // pooled-only applies the affine AFTER the 2x2 average (both kernels); a ReLU does not commute with that average, so the two
+  // orders would differ: refused rather than picked
+  if (!y && y_pooled && relu) return CDDMSL_ERR_ARG;
   if (K == 0) return CDDMSL_OK;   // empty inputs return correctly-shaped empties (poolers.py:221-224)
   if (!y && !y_pooled) return CDDMSL_ERR_ARG;
   if (y8 && (dtype != 0 || !y)) return CDDMSL_ERR_ARG;
@@ -615,12 +643,18 @@ static int roi_align_forward_impl(const void* x, const float* rois, void* y, voi
   if (grid > 0x7fffffffL) return CDDMSL_ERR_ARG;
   int threads = cch >= 256 ? 256 : ((cch + 63) / 64) * 64;
   hipStream_t st = (hipStream_t)stream;
-  // throughput path: one output (the crops, or only their 2x2-pooled map), bf16, every channel chunk in one block, tables that fit
+  // throughput path: one output (the crops, or only their 2x2-pooled map), bf16, at most 256 channel chunks, tables that fit
   const char* rows_env = getenv("CDDMSL_ROI_ROWS");            // "0": the tap-by-tap kernel for everything (A/B switch, read per launch)
   const bool rows_off = rows_env && rows_env[0] == '0';
   if (dtype == 0 && !y8 && !dbg_grid && ((y != nullptr) != (y_pooled != nullptr)) && cch <= 256 && !rows_off) {
-    if (y) k_roi_align_fwd_rows<1><<<dim3((unsigned)((long)K * ph)), dim3(threads), 0, st>>>((const char*)x, rois, (char*)y, N, H, W, cch, ph, pw, spatial_scale, sampling_ratio, aligned, esc, ebi, relu);
-    else k_roi_align_fwd_rows<2><<<dim3((unsigned)((long)K * (ph / 2))), dim3(threads), 0, st>>>((const char*)x, rois, (char*)y_pooled, N, H, W, cch, ph, pw, spatial_scale, sampling_ratio, aligned, esc, ebi, relu);
+    // one wave per block, the 64-chunk channel groups in grid.y (the slowest index): the waves of a bin row share nothing but the
+    // tables, and as one 256-thread block they waited for each other at its two barriers and spread one image's map over four
+    // times the cache footprint.  Pooled-only forward of 8192 RoIs on 16 maps of 50 x 83, 256 / 128 / 64 threads per block:
+    // 2048 channels 1.06 / 0.91 / 0.83 ms, 1024 channels 0.47 / 0.47 / 0.41 ms (bit-identical outputs).
+    const int rthreads = 64;
+    const unsigned gy = (unsigned)((cch + rthreads - 1) / rthreads);
+    if (y) k_roi_align_fwd_rows<1><<<dim3((unsigned)((long)K * ph), gy), dim3(rthreads), 0, st>>>((const char*)x, rois, (char*)y, N, H, W, cch, ph, pw, spatial_scale, sampling_ratio, aligned, esc, ebi, relu);
+    else k_roi_align_fwd_rows<2><<<dim3((unsigned)((long)K * (ph / 2)), gy), dim3(rthreads), 0, st>>>((const char*)x, rois, (char*)y_pooled, N, H, W, cch, ph, pw, spatial_scale, sampling_ratio, aligned, esc, ebi, relu);
     return launch_status();
   }
 #define CDDMSL_RAF(TT, RPP) k_roi_align_fwd<TT, RPP><<<dim3((unsigned)grid), dim3(threads), 0, st>>>((const char*)x, rois, (char*)y, (char*)y_pooled, dbg_grid, N, H, W, cch, ph, pw, spatial_scale, sampling_ratio, aligned, esc, ebi, relu, (char*)y8, q8, (unsigned*)amax8)

@@ -809,17 +809,18 @@ def roi_align_forward_affine(x, rois, ph, pw, spatial_scale, sampling_ratio, ali
                              pooled_only=False, extra_rows=0, emit8=None):
     """RoIAlign of a map that already went through a 1x1 convolution (layers.RoIStageFn):
     ``pooled_only=False``: y [K,ph,pw,C] = relu?(scale * roi_align(x) + bias) (per channel, f32 scale / bias);
-    ``pooled_only=True``: only AvgPool2d(2) of the crops, [K,ph/2,pw/2,C] (no affine) -- the full-resolution crops are never written."""
+    ``pooled_only=True``: only AvgPool2d(2) of the crops, [K,ph/2,pw/2,C] = scale * avgpool2(roi_align(x)) + bias (the affine after the
+    average; no ReLU: the library refuses it) -- the full-resolution crops are never written."""
     require_cuda(x, rois)
     assert rois.dim() == 2 and rois.size(1) == 5 and rois.dtype == torch.float32 and rois.is_contiguous()
-    assert (scale is None) == (bias is None) and not (pooled_only and scale is not None)
+    assert (scale is None) == (bias is None)
     N, H, W, C = x.shape
     K = rois.shape[0]
     if pooled_only:
         y, yp = None, torch.empty((K + extra_rows, ph // 2, pw // 2, C), device=x.device, dtype=x.dtype)
     else:
         y, yp = torch.empty((K + extra_rows, ph, pw, C), device=x.device, dtype=x.dtype), None
-        assert scale is None or (scale.dtype == torch.float32 and scale.numel() == C and bias.numel() == C and scale.is_contiguous() and bias.is_contiguous())
+    assert scale is None or (scale.dtype == torch.float32 and scale.numel() == C and bias.numel() == C and scale.is_contiguous() and bias.is_contiguous())
     y8 = None
     if emit8 is not None:     # e4m3 copy of the crops for the convolution that consumes them (fp8 configuration), as y._fp8
         assert not pooled_only and x.dtype == torch.bfloat16

@@ -743,7 +743,21 @@ def res_stage_attnpool(x, blocks, frozen, ap):
 # ------------------------------------------------------------------------------------------------
 # RoIAlign -> CLIP layer4 with the first block's conv1 moved in front of the pooling
 # ------------------------------------------------------------------------------------------------
-def _roi_block0_forward(feat, rois, bp, out_size, scale, sr, extra, next_pw=None):
+def roi_downsample_on_map(K, out_size, N, H, W):
+    """Does layer4.0's downsample conv run on the feature map, in front of the pooling, as conv1 does?  On the map it is an
+    N*H*W-row GEMM, on the pooled crops a K*(out_size/2)^2-row one: commute when the crops have more rows (8192 RoIs on 16 maps
+    of 50 x 83: 401 408 against 66 400 rows; the region branch's 512 crops on 32 maps would lose: 25 088 against 132 800).
+    CDDMSL_ROI_COMMUTE_DOWN=0 / 1 forces never / always (A/B, tests; read per call); CDDMSL_ROI_COMMUTE=0 (the literal order,
+    modeling/roi_heads.py) wins over both."""
+    if os.environ.get("CDDMSL_ROI_COMMUTE", "1") == "0":
+        return False
+    v = os.environ.get("CDDMSL_ROI_COMMUTE_DOWN", "")
+    if v in ("0", "1"):
+        return v == "1"
+    return K * (out_size // 2) ** 2 > N * H * W
+
+
+def _roi_block0_forward(feat, rois, bp, out_size, scale, sr, extra, next_pw=None, on_map=None):
     """First Bottleneck of the RoI head's layer4 (clip_roi_heads.py:113-115 -> clip_backbone.py:57-70) on the pooled crops, WITHOUT
     the crops: RoIAlign is a linear map over pixels and conv1 / the downsample conv are 1x1 (linear over channels), so
 
@@ -751,23 +765,48 @@ def _roi_block0_forward(feat, rois, bp, out_size, scale, sr, extra, next_pw=None
         avgpool2(roi_align(x))  (-> downsample conv)  written directly, pooled           rows instead of 1.6 M crop rows at 8192 RoIs)
 
     The [K,14,14,1024] crop tensor (3.3 GB) is never written or read; the 512-channel o1 (half of it) is what conv2 needs
-    anyway.  Returns (o1, o2, p2, px, out, e4m3 copy of o1 or None)."""
+    anyway.  Where the pooled crops have more rows than the maps have pixels (``roi_downsample_on_map``) the downsample conv
+    crosses the pooling as well:
+
+        bnd(convd(avgpool2(roi_align(x)))) = sd * avgpool2(roi_align(convd(x))) + bd     (the affine AFTER the pooling: samples outside
+                                                                                          the map weigh zero, so a bias cannot be pooled)
+
+    and the pooled crops ``px`` are not formed either (only the appended maps' are: they keep the literal arithmetic).
+    ``on_map``: that decision when the caller took it already (RoIStageFn: its backward follows the same one).
+    Returns (o1, o2, p2, px, out, e4m3 copy of o1 or None); ``px`` = the pooled appended maps (or None) when commuted."""
     T = feat.dtype
     (s1, b1), (s2, b2), (s3, b3), bnd = bp.bn
     w1, _ = bp.pw[0].get(T, False)
     f8 = bp.fp8
     K, E = rois.shape[0], (0 if extra is None else extra.shape[0])
+    N, H, W, _ = feat.shape
     z = hip.conv_fwd(feat, w1)                                                              # conv1 on the feature map, no affine yet
     o1_shape = (K + E, out_size, out_size, z.shape[-1])
     e8 = fp8_emit_for(bp.pw[1], o1_shape, 1, f8) if E == 0 else None                       # (appended maps are copied in afterwards: quantise then)
     o1 = hip.roi_align_forward_affine(z, rois, out_size, out_size, scale, sr, True, s1, b1, relu=True, extra_rows=E, emit8=e8)
-    px = hip.roi_align_forward_affine(feat, rois, out_size, out_size, scale, sr, True, pooled_only=True, extra_rows=E)
+    del z
+    if on_map is None:
+        on_map = roi_downsample_on_map(K, out_size, N, H, W)
+    if on_map:
+        wd, _ = bp.pw[3].get(T, False)
+        zd = hip.conv_fwd(feat, wd)                                                         # the downsample conv on the feature map, bf16 / f32
+        idn = hip.roi_align_forward_affine(zd, rois, out_size, out_size, scale, sr, True, bnd[0], bnd[1], pooled_only=True, extra_rows=E)
+        del zd
+        px = None
+        if E:
+            px = hip.avgpool2_fwd(extra)
+            idn[K:].copy_(hip.conv_fwd(px, wd, bnd[0], bnd[1]))
+    else:
+        px = hip.roi_align_forward_affine(feat, rois, out_size, out_size, scale, sr, True, pooled_only=True, extra_rows=E)
+        idn = None
     if E:                                            # maps of the crops' geometry riding behind them (the 224x224 crops' res4)
         o1[K:].copy_(hip.conv_fwd(extra, w1, s1, b1, relu=True))
-        px[K:].copy_(hip.avgpool2_fwd(extra))
+        if idn is None:
+            px[K:].copy_(hip.avgpool2_fwd(extra))
     o2 = conv_fwd_auto(o1, bp.pw[1], s2, b2, f8, relu=True, pad=1)
     p2 = hip.avgpool2_fwd(o2)
-    idn = conv_fwd_auto(px, bp.pw[3], bnd[0], bnd[1], f8)
+    if idn is None:
+        idn = conv_fwd_auto(px, bp.pw[3], bnd[0], bnd[1], f8)
     out_shape = (p2.shape[0], p2.shape[1], p2.shape[2], _ohwi(bp.w[2]).shape[0])
     out = conv_fwd_auto(p2, bp.pw[2], s3, b3, f8, emit8=fp8_emit_for(next_pw, out_shape, 0, f8), residual=idn, relu=True)
     return o1, o2, p2, px, out, (_fp8_made_for(o1, bp.pw[1]) if f8 else None)
@@ -777,19 +816,22 @@ class RoIStageFn(torch.autograd.Function):
     """pooler (poolers.py:190-229) + ``backbone.layer4`` (clip_roi_heads.py:113-115) as ONE autograd node, first block as in
     ``_roi_block0_forward``.  Backward of that block: the gradient of o1 goes back through the RoIAlign gather at 512 channels
     to the feature-map-level conv1 (its weight gradient is a 66 400-row reduction, its input gradient a 66 400-row GEMM), the
-    downsample path's gradient through the gather on the POOLED 7x7 grid (a quarter of the bytes)."""
+    downsample path's gradient through the gather on the POOLED 7x7 grid (a quarter of the bytes) -- at the downsample conv's
+    input width, or, where that conv ran on the map (``roi_downsample_on_map``), at its output width in front of its two
+    map-level gradient GEMMs."""
 
     @staticmethod
     def forward(ctx, feat, anchor, rois, roi_start, blocks, out_size, scale, sr, out_grad_premasked, extra):
         feat = feat.contiguous()
         nxt = lambda i: blocks[i + 1].pw[0] if i + 1 < len(blocks) else None
-        o1, o2, p2, px, cur, o1_8 = _roi_block0_forward(feat, rois, blocks[0], out_size, scale, sr, extra, nxt(0))
+        on_map = roi_downsample_on_map(rois.shape[0], out_size, feat.shape[0], feat.shape[1], feat.shape[2])
+        o1, o2, p2, px, cur, o1_8 = _roi_block0_forward(feat, rois, blocks[0], out_size, scale, sr, extra, nxt(0), on_map)
         saved, o1_8s = [feat, rois, roi_start, extra, o1, o2, p2, px, cur], [None, o1_8, None]
         for bi, bp in enumerate(blocks[1:], start=1):
             cur, mids = _block_forward(cur, bp, True, None, nxt(bi))
             saved += [mids[0], mids[1], mids[2], mids[3], cur]
             o1_8s += list(mids[4])
-        ctx.blocks, ctx.meta = blocks, (out_size, scale, sr, out_grad_premasked)
+        ctx.blocks, ctx.meta = blocks, (out_size, scale, sr, out_grad_premasked, on_map)
         ctx.save_for_backward(*saved, *o1_8s)         # (fp8 configuration: three e4m3 input copies per block, for the weight gradients)
         return cur
 
@@ -797,7 +839,7 @@ class RoIStageFn(torch.autograd.Function):
     def backward(ctx, g):
         blocks = ctx.blocks
         saved, o1_8s = ctx.saved_tensors[:-3 * len(blocks)], ctx.saved_tensors[-3 * len(blocks):]
-        out_size, scale, sr, premasked = ctx.meta
+        out_size, scale, sr, premasked, on_map = ctx.meta
         feat, rois, roi_start, extra = saved[:4]
         st = saved[4:]                               # per block: o1, o2, p2, px, out
         gs = g.contiguous() if premasked else hip.relu_bwd(g.contiguous(), st[-1])
@@ -819,21 +861,32 @@ class RoIStageFn(torch.autograd.Function):
         dpre2 = hip.avgpool2_bwd(dgrad_auto(gs, bp.pw[2], f8, gs_slot), tuple(o2.shape), mask=o2, emit8=e8)
         dpre1 = dgrad_auto(dpre2, bp.pw[1], f8, d2_slot, pad=1, relu_mask=o1)                # [K+E,14,14,planes] wrt bn1's output
         wgrad_auto(o1, dpre2, bp.pw[1], s2, 1, _ohwi(_grad_buf(w2p)), f8, o1_8s[1], d2_slot)
-        hip.conv_wgrad(px, gs, shp(wdp), bnd[0], out=_ohwi(_grad_buf(wdp)))
-        dxb = dgrad_auto(gs, bp.pw[3], f8, gs_slot)                                          # [K+E,7,7,C] wrt the pooled crops
+        N, H, W, C = feat.shape
+        _, w1d = bp.pw[0].get(T, True)
+        dfeat = dextra = dzd = wdd = None
+        if on_map:
+            # the downsample path back across the pooling FIRST: the pooled gather at the conv's output width, then its two gradients
+            # on the feature map (sd rides in the weight-gradient scale and in the prepared input-gradient weights); the appended maps'
+            # rows keep their own pooled input ``px`` [E,7,7,C]
+            _, wdd = bp.pw[3].get(T, True)
+            dzd = hip.roi_align_backward(gs[:K], rois, roi_start, (N, H, W, gs.shape[-1]), scale, sr, True, pooled=True)
+            hip.conv_wgrad(feat, dzd, shp(wdp), bnd[0], out=_ohwi(_grad_buf(wdp)))
+            if E:
+                hip.conv_wgrad(px, gs[K:], shp(wdp), bnd[0], out=_ohwi(_grad_buf(wdp)))
+        else:
+            hip.conv_wgrad(px, gs, shp(wdp), bnd[0], out=_ohwi(_grad_buf(wdp)))
+            dxb = dgrad_auto(gs, bp.pw[3], f8, gs_slot)                                      # [K+E,7,7,C] wrt the pooled crops
         # back across the pooling: gather at `planes` channels, then conv1's gradients on the feature map (s1 rides in the
         # weight-gradient scale and in the prepared input-gradient weights, as for every conv of a stage)
-        N, H, W, C = feat.shape
         dz = hip.roi_align_backward(dpre1[:K], rois, roi_start, (N, H, W, dpre1.shape[-1]), scale, sr, True)
         hip.conv_wgrad(feat, dz, shp(w1p), s1, out=_ohwi(_grad_buf(w1p)))
-        _, w1d = bp.pw[0].get(T, True)
-        dfeat = dextra = None
         if E:
             hip.conv_wgrad(extra, dpre1[K:], shp(w1p), s1, out=_ohwi(_grad_buf(w1p)))
             if ctx.needs_input_grad[9]:
-                dextra = hip.conv_fwd(dpre1[K:], w1d, residual=hip.avgpool2_bwd(dxb[K:].contiguous(), tuple(extra.shape)))
+                dxe = hip.conv_fwd(gs[K:], wdd) if on_map else dxb[K:].contiguous()
+                dextra = hip.conv_fwd(dpre1[K:], w1d, residual=hip.avgpool2_bwd(dxe, tuple(extra.shape)))
         if ctx.needs_input_grad[0]:
-            r = hip.roi_align_backward(dxb[:K], rois, roi_start, (N, H, W, C), scale, sr, True, pooled=True)
+            r = hip.conv_fwd(dzd, wdd) if on_map else hip.roi_align_backward(dxb[:K], rois, roi_start, (N, H, W, C), scale, sr, True, pooled=True)
             dfeat = hip.conv_fwd(dz, w1d, residual=r)
         return dfeat, None, None, None, None, None, None, None, None, dextra
 

@@ -129,7 +129,11 @@ int cddmsl_roi_align_backward(const void* dy, const float* rois, const int* roi_
  * the pooling -- RoIAlign is linear over pixels, a 1x1 conv over channels: roi_align(x) W = roi_align(x W) -- so the
  * [K][14][14][1024] crop tensor (3.3 GB at 8192 RoIs) is never formed:
  *   _affine:  y = relu?(scale[c] * roi_align(x)[.., c] + bias[c])  (FrozenBN + ReLU of that conv; scale / bias nullable),
- *             y nullable when only y_pooled (the downsample path's AvgPool2d(2) of the crops) is wanted;
+ *             y nullable when only y_pooled (the downsample path's AvgPool2d(2) of the crops) is wanted: then
+ *             y_pooled = scale[c] * avgpool2(roi_align(x))[.., c] + bias[c], the affine AFTER the average (the downsample conv
+ *             moved in front of the pooling too: its FrozenBN bias cannot be pooled, bins at the border do not weigh 1), and
+ *             relu != 0 returns CDDMSL_ERR_ARG (a ReLU does not commute with the average); with y given, y_pooled is
+ *             avgpool2 of the stored y;
  *   _backward_pooled: dy is the gradient of the pooled map [K][ph][pw][C] (RoIAlign grid 2ph x 2pw): roi_align_backward of the
  *             AvgPool2d backward of dy, without forming it;
  *             y8 / q8 / amax8 (nullable, bf16 only): e4m3 copy of y for the consuming convolution, as cddmsl_conv_fwd_q8. */

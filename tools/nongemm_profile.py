@@ -46,11 +46,16 @@ def main():
     def add(name, nbytes, what):
         est[name] = (float(nbytes), what)
 
-    # RoIAlign forward (commuted head): conv1 map (512 ch) -> o1 crops; res4 (1024 ch) -> pooled crops; per pass
-    add("roi_align_forward", sum(k * 196 * 512 * 2 + k * 49 * 1024 * 2 for k in (K, Kr)) + 2 * (B * hf * wf * 512 * 2 + res4) + res4,
-        "o1 crops [K,14,14,512] + pooled crops [K,7,7,1024] written, the two maps read once")
-    add("roi_align_backward", sum(k * 196 * 512 * 2 + k * 49 * 1024 * 2 for k in (K, Kr)) + 2 * (B * hf * wf * 512 * 2) + 3 * res4,
-        "crop gradients read, map gradients written")
+    # RoIAlign (commuted head), per pass: conv1's map (512 ch) <-> o1 crops; the downsample path's pooled crops at the conv's input
+    # width (1024, from res4) or, where that conv runs on the map (layers.roi_downsample_on_map), at its output width (2048)
+    from cddmsl_amd import layers
+    roi_b, wide = 0, []
+    for k, n in ((K, B), (Kr, 2 * B)):
+        cd = 2048 if layers.roi_downsample_on_map(k, 14, n, hf, wf) else 1024
+        wide.append(cd)
+        roi_b += k * 196 * 512 * 2 + k * 49 * cd * 2 + n * hf * wf * (512 + cd) * 2
+    add("roi_align_forward", roi_b, f"o1 crops [K,14,14,512] + pooled crops [K,7,7,{wide[0]} / {wide[1]}] written, the two maps of each pass read once")
+    add("roi_align_backward", roi_b, "crop gradients read, map gradients written (same tensors)")
     tokb = sum(k * (P * C4 * 2 + 56 * C4 * 2 + C4 * 8) for k in Kp)
     add("attn_tokens_fwd", tokb, "map [K,49,2048] read, tokens [K,56,2048] + mask words [K,2048] x 8 B written")
     add("attnpool_dx", sum(k * (64 * C4 * 2 + P * C4 * 2 + C4 * 12 + 64 * 56 * 2) for k in Kp), "[dZ;U] read, dx written, g0 + mask words read")
