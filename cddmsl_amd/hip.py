@@ -774,7 +774,9 @@ def sgd_clip_step(params, grads, moms, norm_ws, lr, momentum, wd, clip, first_st
     n = len(params)
     if n == 0:
         return
-    require_cuda(*params, *grads, *moms)
+    require_cuda(*params, *grads, *moms, norm_ws)
+    assert len(grads) == n and len(moms) == n
+    assert norm_ws.dtype == torch.float32 and norm_ws.is_contiguous() and norm_ws.numel() >= n, "norm_ws holds one f32 per tensor"
     for p, g, m in zip(params, grads, moms):
         assert p.dtype == g.dtype == m.dtype == torch.float32
         assert same_layout(p, g) and same_layout(p, m), "param/grad/momentum must share a memory layout"
@@ -1078,8 +1080,11 @@ def l2norm_fwd(x, eps):
 
 def l2norm_bwd(dy, y, inv):
     require_cuda(dy, y, inv)
+    dy = dy.contiguous()
+    assert y.dim() == 2 and y.dtype == dy.dtype == inv.dtype == torch.float32 and y.is_contiguous() and inv.is_contiguous()
+    assert dy.shape == y.shape and inv.numel() == y.shape[0]
     dx = torch.empty_like(y)
-    check(_L().cddmsl_l2norm_bwd(ptr(dy.contiguous()), ptr(y), ptr(inv), ptr(dx), y.shape[0], y.shape[1], stream_ptr()), "cddmsl_l2norm_bwd")
+    check(_L().cddmsl_l2norm_bwd(ptr(dy), ptr(y), ptr(inv), ptr(dx), y.shape[0], y.shape[1], stream_ptr()), "cddmsl_l2norm_bwd")
     return dx
 
 
@@ -1087,7 +1092,7 @@ def cosine_logits_fwd(x, wn, temperature, eps=1e-12):
     require_cuda(x, wn)
     R, D = x.shape
     Kc = wn.shape[0]
-    assert x.dtype == wn.dtype == torch.float32 and x.is_contiguous() and wn.is_contiguous()
+    assert x.dtype == wn.dtype == torch.float32 and x.is_contiguous() and wn.is_contiguous() and wn.dim() == 2 and wn.shape[1] == D
     scores = torch.empty((R, Kc + 1), device=x.device, dtype=torch.float32)
     inv = torch.empty(R, device=x.device, dtype=torch.float32)
     check(_L().cddmsl_cosine_logits_fwd(ptr(x), ptr(wn), ptr(scores), ptr(inv), R, D, Kc, temperature, eps, stream_ptr()),
@@ -1098,10 +1103,14 @@ def cosine_logits_fwd(x, wn, temperature, eps=1e-12):
 def cosine_logits_bwd(ds, x, wn, inv, temperature, dx=None):
     require_cuda(ds, x, wn, inv, dx)
     R, D = x.shape
+    ds = ds.contiguous()
+    assert x.dtype == wn.dtype == inv.dtype == ds.dtype == torch.float32 and x.is_contiguous() and wn.is_contiguous() and inv.is_contiguous()
+    assert wn.dim() == 2 and wn.shape[1] == D and tuple(ds.shape) == (R, wn.shape[0] + 1) and inv.numel() == R
     acc = dx is not None
     if dx is None:
         dx = torch.empty_like(x)
-    check(_L().cddmsl_cosine_logits_bwd(ptr(ds.contiguous()), ptr(x), ptr(wn), ptr(inv), ptr(dx), R, D, wn.shape[0], temperature, int(acc),
+    assert dx.dtype == torch.float32 and dx.is_contiguous() and dx.shape == x.shape
+    check(_L().cddmsl_cosine_logits_bwd(ptr(ds), ptr(x), ptr(wn), ptr(inv), ptr(dx), R, D, wn.shape[0], temperature, int(acc),
                                          stream_ptr()), "cddmsl_cosine_logits_bwd")
     return dx
 
@@ -1120,6 +1129,8 @@ def contrastive_fwd(S):
 def contrastive_bwd(S, rl, cl, gloss):
     require_cuda(S, rl, cl, gloss)
     n = S.shape[0]
+    assert S.dtype == rl.dtype == cl.dtype == torch.float32 and tuple(S.shape) == (n, n) and S.is_contiguous()
+    assert rl.is_contiguous() and cl.is_contiguous() and rl.numel() == n and cl.numel() == n and gloss.numel() == 1
     dS = torch.empty_like(S)
     check(_L().cddmsl_contrastive_bwd(ptr(S), ptr(rl), ptr(cl), ptr(gloss.reshape(1).float().contiguous()), ptr(dS), n, n, stream_ptr()),
           "cddmsl_contrastive_bwd")
@@ -1131,7 +1142,8 @@ def layernorm_fwd(x, gamma, beta, out_dtype, eps=1e-5):
     """x [R,D] f32 -> (y [R,D] out_dtype, mean [R], rstd [R])"""
     require_cuda(x, gamma, beta)
     R, D = x.shape
-    assert x.dtype == torch.float32 and x.is_contiguous()
+    assert x.dtype == gamma.dtype == beta.dtype == torch.float32 and x.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous()
+    assert gamma.numel() == D and beta.numel() == D
     y = torch.empty((R, D), device=x.device, dtype=out_dtype)
     mean = torch.empty(R, device=x.device, dtype=torch.float32)
     rstd = torch.empty(R, device=x.device, dtype=torch.float32)
@@ -1146,6 +1158,8 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=None):
     require_cuda(dy, x, gamma, mean, rstd, accumulate_into)
     R, D = x.shape
     dy = dy.contiguous()
+    assert x.dtype == gamma.dtype == mean.dtype == rstd.dtype == torch.float32 and x.is_contiguous() and gamma.is_contiguous()
+    assert mean.is_contiguous() and rstd.is_contiguous() and gamma.numel() == D and mean.numel() == R and rstd.numel() == R and dy.shape == x.shape
     if accumulate_into is None:
         dx, acc = torch.empty_like(x), 0
     else:
@@ -1469,7 +1483,7 @@ def attn_small_bwd(q, kv, do, t, heads, scale):
 def focal_ce_fwd(logits, target, gamma, bg_class, bg_weight):
     require_cuda(logits, target)
     R, C = logits.shape
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and target.dtype == torch.int64
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and target.dtype == torch.int64 and target.is_contiguous() and target.numel() == R
     row = torch.empty(R, device=logits.device, dtype=torch.float32)
     probs = torch.empty_like(logits)
     check(_L().cddmsl_focal_ce_fwd(ptr(logits), ptr(target), ptr(row), ptr(probs), R, C, gamma, bg_class, bg_weight, stream_ptr()),
@@ -1479,6 +1493,9 @@ def focal_ce_fwd(logits, target, gamma, bg_class, bg_weight):
 
 def focal_ce_bwd(logits, target, probs, gscale, gamma, bg_class, bg_weight):
     require_cuda(logits, target, probs, gscale)
+    assert logits.dim() == 2 and logits.dtype == probs.dtype == torch.float32 and logits.is_contiguous() and probs.is_contiguous()
+    assert probs.shape == logits.shape and target.dtype == torch.int64 and target.is_contiguous() and target.numel() == logits.shape[0]
+    assert gscale.numel() == 1
     d = torch.empty_like(logits)
     check(_L().cddmsl_focal_ce_bwd(ptr(logits), ptr(target), ptr(probs), ptr(gscale.reshape(1).float().contiguous()), ptr(d), logits.shape[0],
                                    logits.shape[1], gamma, bg_class, bg_weight, stream_ptr()), "cddmsl_focal_ce_bwd")
