@@ -519,8 +519,15 @@ __global__ __launch_bounds__(256, 2) void k_conv_fwd(ConvArgs p) {
 // L1/L2).  All loads of a tile are issued before its MFMAs.  Output: lanes = consecutive channels (64 contiguous bytes
 // per pixel and tile).  Same accumulation order as k_conv_fwd (chunk pairs in K order) -> bit-identical results.
 // ------------------------------------------------------------------------------------------------
-template <typename T, int CPP, int NT, int NTAP = 9>     // NTAP = 1: the same streaming structure for a 1x1 layer with 32 / 64 output channels
+//
+// POOL (bf16, the ost_ok path only): the launch writes AvgPool2d(2) of its result and the full-resolution map never reaches memory.  A
+// tile is then 8 POOLED pixels: tile row r stands for pixel (2 poy + ((r >> 1) & 1), 2 pox + (r & 1)) of pooled pixel tile * 8 + (r >> 2), so
+// accumulator registers 4k .. 4k+3 of a lane are the 2x2 window of pooled pixel 2k + hh in k_avgpool2_fwd's order; the four values are
+// rounded to bf16 as the unfused launch stores them, averaged in that kernel's order and rounded once more: bit-identical to the two
+// launches.  An odd last row / column is never computed.  The pooled tile is 8 rows x NT * 64 bytes (NT = 2: one 1 KiB store).
+template <typename T, int CPP, int NT, int NTAP = 9, bool POOL = false>     // NTAP = 1: the same streaming structure for a 1x1 layer with 32 / 64 output channels
 __global__ __launch_bounds__(256) void k_conv3x3_small(ConvArgs p) {
+  static_assert(!POOL || (Mma<T>::ES == 2 && NT == 2 && NTAP == 9 && CPP > 1), "pooled output: the bf16 3x3 instantiation with 64 output channels");
   constexpr int KC = NTAP * CPP, KS = (KC + 1) / 2;    // 16-byte chunks of a weight row; k-steps of two chunks
   constexpr int PAD = NTAP == 9 ? 1 : 0;
   constexpr int ES = Mma<T>::ES;
@@ -550,7 +557,8 @@ __global__ __launch_bounds__(256) void k_conv3x3_small(ConvArgs p) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) { sc[nt] = p.scale ? p.scale[nt * 32 + r] : 1.f; bi[nt] = p.bias ? p.bias[nt * 32 + r] : 0.f; }
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  const int ntiles = (p.M + 31) >> 5;
+  const int Hp = p.Ho >> 1, Wp = p.Wo >> 1, Mp = POOL ? p.Nimg * Hp * Wp : 0;     // POOL: the pooled map, Mp rows
+  const int ntiles = POOL ? (Mp + 7) >> 3 : (p.M + 31) >> 5;
   // Addressing.  An ablation of this kernel (round 2: loads, MFMAs and stores switched off one at a time) showed 40-50 % of its time
   // to be the per-tile INDEX ARITHMETIC alone -- per k-step a tap select, two range tests and a 64-bit address, per output element a
   // 64-bit address and a row test: ~530 vector-ALU instructions per 32-pixel tile against 36-72 MFMAs.  Now: buffer addressing
@@ -561,18 +569,30 @@ __global__ __launch_bounds__(256) void k_conv3x3_small(ConvArgs p) {
   // (base one row and one pixel BEFORE the tensor: the lane offset of a pixel's tap (0,0) is then never negative -- the range check
   // sees the lane offset alone -- and the bytes in front of the tensor are only ever addressed by taps the mask removes)
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x - (long)(p.Wi + 1) * (CPP * 16)), 0, 0x7fffffff, 0x00020000);
-  const long ybytes = (long)p.M * p.ldy * ES, mbytes = (long)p.M * p.ldm * ES;
+  const long ybytes = (long)(POOL ? Mp : p.M) * p.ldy * ES, mbytes = (long)p.M * p.ldm * ES;
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, (int)(ybytes > 0x7fffffffL ? 0x7fffffffL : ybytes), 0x00020000);
   const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc((void*)p.relu_mask, 0, p.relu_mask ? (int)(mbytes > 0x7fffffffL ? 0x7fffffffL : mbytes) : 0, 0x00020000);
   const float relu_floor = p.relu ? 0.f : -__builtin_inff();
   __shared__ __attribute__((aligned(16))) u32x4 ost[ES == 2 ? 4 * 32 * NT * 4 : 1];    // per wave: one output tile, 32 rows x NT * 64 bytes
   const bool ost_ok = !p.relu_mask && p.ldy == NT * 32 && (long)p.M * NT * 64 < 0x7fffffffL;
   for (int tile = wave; tile < ntiles; tile += nwaves) {
-    const int m = tile * 32 + r;
-    const bool vm = m < p.M;
-    const unsigned mm = vm ? m : 0;
-    const unsigned tq = fdiv(mm, p.dWo), ox = mm - tq * p.Wo;
-    const unsigned img = fdiv(tq, p.dHo), oy = tq - img * p.Ho;
+    bool vm;
+    unsigned ox, oy, img;
+    if (POOL) {
+      const int q = tile * 8 + (r >> 2);
+      vm = q < Mp;
+      const unsigned qq = vm ? q : 0;
+      const unsigned tq = fdiv(qq, p.dWp), pox = qq - tq * Wp;
+      img = fdiv(tq, p.dHp);
+      oy = 2 * (tq - img * Hp) + ((r >> 1) & 1); ox = 2 * pox + (r & 1);
+    } else {
+      const int m = tile * 32 + r;
+      vm = m < p.M;
+      const unsigned mm = vm ? m : 0;
+      const unsigned tq = fdiv(mm, p.dWo);
+      ox = mm - tq * p.Wo;
+      img = fdiv(tq, p.dHo); oy = tq - img * p.Ho;
+    }
     const int iy0 = (int)oy * p.stride - PAD, ix0 = (int)ox * p.stride - PAD;
     // byte offset of tap (0,0), chunk 0 of this lane's pixel (may be "negative": wraps, and is then masked by the tap test)
     const unsigned lbase = (unsigned)((((int)img * p.Hi + iy0 + 1) * p.Wi + ix0 + 1) * (CPP * 16)) + (CPP > 1 ? hh * 16 : 0);
@@ -620,6 +640,26 @@ __global__ __launch_bounds__(256) void k_conv3x3_small(ConvArgs p) {
     // contiguous bytes of y.  It goes through this wave's LDS slot (2-byte writes in the accumulator layout, 16-byte reads in memory
     // order; one wave's DS operations execute in order, no barrier) and leaves as 2 * NT wave-wide 1 KiB stores instead of 16 * NT
     // stores of 2 bytes per lane (two 64-byte pieces per instruction).
+    if (POOL) {
+      char* ob = (char*)ost + (threadIdx.x >> 6) * (32 * NT * 64);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float a4[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float v = affine<T>(acc[nt][4 * k + j], sc[nt], bi[nt]);
+            asm("v_max_f32 %0, %1, %2" : "=v"(v) : "v"(v), "s"(relu_floor));
+            a4[j] = bf2f(f2bf(v));
+          }
+          *(unsigned short*)(ob + (2 * k + hh) * (NT * 64) + (nt * 32 + r) * 2) = f2bf(((a4[0] + a4[1]) + (a4[2] + a4[3])) * 0.25f);
+        }
+      static_assert(!POOL || NT == 2, "one 1 KiB store per pooled tile");
+      const u32x4 o = *(const u32x4*)(ob + lane * 16);
+      __builtin_amdgcn_raw_buffer_store_b128(o, ry, (unsigned)(lane * 16), tile * (8 * NT * 64), 0);   // (rows past Mp: outside num_records)
+      continue;
+    }
     if (ES == 2 && ost_ok) {
       char* ob = (char*)ost + (threadIdx.x >> 6) * (32 * NT * 64);
 #pragma unroll
@@ -666,6 +706,9 @@ template <typename T> void launch_small(const ConvArgs& a, unsigned nb, hipStrea
   else if (a.cpp == 1) hipLaunchKernelGGL((k_conv3x3_small<T, 1, 2>), dim3(nb), dim3(256), 0, st, a);
   else if (a.cpp == 8) hipLaunchKernelGGL((k_conv3x3_small<T, 8, 2>), dim3(nb), dim3(256), 0, st, a);
   else if (a.Cout == 32) hipLaunchKernelGGL((k_conv3x3_small<T, 4, 1>), dim3(nb), dim3(256), 0, st, a);
+  else if (a.pool_out) {                            // (cddmsl_conv3x3_pool_fwd admits bf16 alone)
+    if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((k_conv3x3_small<T, 4, 2, 9, true>), dim3(nb), dim3(256), 0, st, a);
+  }
   else hipLaunchKernelGGL((k_conv3x3_small<T, 4, 2>), dim3(nb), dim3(256), 0, st, a);
 }
 

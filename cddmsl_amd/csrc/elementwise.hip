@@ -188,6 +188,53 @@ __global__ void k_avgpool2_bwd(const char* dy, const char* mask, const char* add
   }
 }
 
+// k_avgpool2_fwd (bf16) that also records the ReLU mask its backward needs: one u32 per OUTPUT chunk, byte (dy * 2 + dx) = the 8 bits
+// x[2oy+dy][2ox+dx][8c + j] > 0 (bit j; the same test k_avgpool2_bwd applies to the full mask, so NaN and -0 give 0) -- 1/16 of x's bytes
+__global__ void k_avgpool2_fwd_bits(const char* x, char* y, unsigned* bits, int N, int H, int W, int cch) {
+  using T = __bf16;
+  int Ho = H / 2, Wo = W / 2;
+  long total = (long)N * Ho * Wo * cch;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    int c = i % cch; long q = i / cch;
+    int ox = q % Wo; q /= Wo;
+    int oy = q % Ho; int n = q / Ho;
+    const u32x4* b = (const u32x4*)x + (((long)n * H + 2 * oy) * W + 2 * ox) * cch + c;
+    float a0[8], a1[8], a2[8], a3[8], o[8];
+    Elt<T>::unpack(b[0], a0); Elt<T>::unpack(b[cch], a1);
+    Elt<T>::unpack(b[(long)W * cch], a2); Elt<T>::unpack(b[(long)W * cch + cch], a3);
+    unsigned m = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      o[j] = ((a0[j] + a1[j]) + (a2[j] + a3[j])) * 0.25f;
+      m |= (a0[j] > 0.f ? 1u : 0u) << j | (a1[j] > 0.f ? 1u : 0u) << (8 + j) | (a2[j] > 0.f ? 1u : 0u) << (16 + j) | (a3[j] > 0.f ? 1u : 0u) << (24 + j);
+    }
+    ((u32x4*)y)[i] = Elt<T>::pack(o);
+    bits[i] = m;
+  }
+}
+// k_avgpool2_bwd (bf16, no add) reading that word of the pooled position instead of the full-resolution mask chunk
+__global__ void k_avgpool2_bwd_bits(const char* dy, const unsigned* bits, char* dx, int N, int H, int W, int cch) {
+  using T = __bf16;
+  int Ho = H / 2, Wo = W / 2;
+  long total = (long)N * H * W * cch;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    int c = i % cch; long q = i / cch;
+    int xx = q % W; q /= W;
+    int yy = q % H; int n = q / H;
+    float g[8], o[8];
+    bool in = (yy >> 1) < Ho && (xx >> 1) < Wo;
+    unsigned m = 0u;
+    if (in) {
+      const long p = (((long)n * Ho + (yy >> 1)) * Wo + (xx >> 1)) * cch + c;
+      Elt<T>::unpack(((const u32x4*)dy)[p], g);
+      m = bits[p] >> (8 * ((yy & 1) * 2 + (xx & 1)));
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (in && ((m >> j) & 1u)) ? g[j] * 0.25f : 0.f;
+    ((u32x4*)dx)[i] = Elt<T>::pack(o);
+  }
+}
+
 // fp8 configuration: the same pass (bf16) also writes the e4m3 copy of dx for the GEMMs that consume it -- y8 = sat(dx * q8[0]), from
 // the f32 value -- and max-es |dx| into amax8[block & 63] (delayed scaling; see fp8.hip)
 __global__ __launch_bounds__(256) void k_avgpool2_bwd_q8(const char* dy, const char* mask, const char* add, char* dx, int N, int H, int W, int cch,
@@ -702,6 +749,24 @@ extern "C" int cddmsl_avgpool2_bwd(const void* dy, const void* mask, const void*
   if (total == 0) return CDDMSL_OK;
   DISPATCH(dtype, k_avgpool2_bwd, <<<dim3(gsz(total)), dim3(256), 0, (hipStream_t)stream>>>(
       (const char*)dy, (const char*)mask, (const char*)add, (char*)dx, N, H, W, cch));
+  return launch_status();
+}
+
+// bf16 only (the mask word holds 8 channels = one 16-byte chunk); bits [N][H/2][W/2][C/8] u32
+extern "C" int cddmsl_avgpool2_fwd_bits(const void* x, void* y, void* bits, int N, int H, int W, int C, int dtype, void* stream) {
+  if (dtype != 0 || C % 8 || H < 2 || W < 2 || !bits) return CDDMSL_ERR_ARG;
+  const int cch = C / 8;
+  const long total = (long)N * (H / 2) * (W / 2) * cch;
+  if (total == 0) return CDDMSL_OK;
+  hipLaunchKernelGGL(k_avgpool2_fwd_bits, dim3(gsz(total)), dim3(256), 0, (hipStream_t)stream, (const char*)x, (char*)y, (unsigned*)bits, N, H, W, cch);
+  return launch_status();
+}
+extern "C" int cddmsl_avgpool2_bwd_bits(const void* dy, const void* bits, void* dx, int N, int H, int W, int C, int dtype, void* stream) {
+  if (dtype != 0 || C % 8 || H < 2 || W < 2 || !bits) return CDDMSL_ERR_ARG;
+  const int cch = C / 8;
+  const long total = (long)N * H * W * cch;
+  if (total == 0) return CDDMSL_OK;
+  hipLaunchKernelGGL(k_avgpool2_bwd_bits, dim3(gsz(total)), dim3(256), 0, (hipStream_t)stream, (const char*)dy, (const unsigned*)bits, (char*)dx, N, H, W, cch);
   return launch_status();
 }
 

@@ -78,6 +78,9 @@ struct ConvArgs {
   // launch stops at this logical tile (persistent form; the one-tile grid is simply shorter).
   float* partial = nullptr;
   int tile0 = 0, ksplits = 1, kper = 0, tile_limit = 0;
+  // cddmsl_conv3x3_pool_fwd: y is AvgPool2d(2) of the result, [Nimg][Ho/2][Wo/2][ldy] (k_conv3x3_small POOL); divisors of the pooled map
+  int pool_out = 0;
+  FastDiv dWp = {}, dHp = {};
   int nt_out = 1;  // bf16 output stored non-temporal (CDDMSL_STORE_AUX): outputs too large to be found in the caches by their consumer
 #ifdef CDDMSL_TILE_STAMPS
   unsigned long long* tstamps = nullptr;  // diagnostic build only (tools/tile_stamps.py): per wave, 100 MHz s_memrealtime stamps at entry / loop start / loop end / exit

@@ -259,6 +259,26 @@ extern "C" int cddmsl_conv_fwd(const void* x, const void* w, void* y, const floa
                       relu, out_f32, nullptr, nullptr, nullptr, stream);
 }
 
+// The stem's third convolution with the AvgPool2d(2) behind it in one launch: y [Nimg][Hi/2][Wi/2][64] = avgpool2(relu(bn(conv3x3(x)))),
+// bit-identical to cddmsl_conv_fwd (pad 1, FrozenBN + ReLU) followed by cddmsl_avgpool2_fwd.  Only what that layer is: bf16, 32 -> 64
+// channels, stride 1, scale and bias given, no mask (stride / relu_mask / dtype are arguments so that anything else is REFUSED here
+// instead of silently computed another way).
+extern "C" int cddmsl_conv3x3_pool_fwd(const void* x, const void* w, void* y, const float* scale, const float* bias, const void* relu_mask,
+                                       int Nimg, int Hi, int Wi, int Cin, int Cout, int stride, int dtype, void* stream) {
+  if (dtype != 0 || Cin != 32 || Cout != 64 || stride != 1 || relu_mask || !scale || !bias || Hi < 2 || Wi < 2) return CDDMSL_ERR_ARG;
+  ConvArgs a;
+  const int st = fill_conv(a, OP_BF16, x, w, y, scale, bias, nullptr, nullptr, Nimg, Hi, Wi, Cin, Cout, 3, 3, 1, 1, 0, Cout, 0, 0, 1, 0,
+                           nullptr, nullptr, nullptr);
+  if (st != CDDMSL_OK || a.M == 0) return st;
+  // (buffer addressing: the input and the pooled output each below 2 GiB)
+  if ((long)Nimg * Hi * Wi * Cin * 2 >= 0x7ffff000L || (long)Nimg * (a.Ho / 2) * (a.Wo / 2) * Cout * 2 >= 0x7fffffffL) return CDDMSL_ERR_ARG;
+  a.pool_out = 1;
+  a.dWp = make_fastdiv((unsigned)(a.Wo / 2)); a.dHp = make_fastdiv((unsigned)(a.Ho / 2));
+  const Plan pl = plan_fwd(a, OP_BF16, 1);
+  if (pl.kernel != 8) return CDDMSL_ERR_ARG;
+  return run_fwd(a, OP_BF16, pl, stream);
+}
+
 // cddmsl_conv_fwd (bf16) that ALSO writes y8 [M][Cout] = OCP e4m3 of sat(y * q8[0]) and max-es |y| into amax8[0..63] (64 floats,
 // spread by block to keep the atomics off one address): the producer side of the fp8 configuration -- the convolution that
 // consumes y reads y8 instead of a separate quantisation pass.  Only launches the 256x256 kernel takes (CDDMSL_ERR_ARG otherwise:

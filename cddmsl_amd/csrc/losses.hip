@@ -251,10 +251,12 @@ __global__ __launch_bounds__(256) void k_layernorm_fwd_v(const float* __restrict
   }
   if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
 }
-template <typename T, int NSEG>
+// EMIT: also stores the bf16 rounding (nearest even) of the final f32 value into dxb -- the copy the next GEMM's operand cast would make
+template <typename T, int NSEG, bool EMIT = false>
 __global__ __launch_bounds__(256) void k_layernorm_bwd_v(const void* __restrict__ dy, const float* __restrict__ x,
                                                          const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                         const float* __restrict__ rstd, float* dx, long R, int accumulate) {
+                                                         const float* __restrict__ rstd, float* dx, long R, int accumulate,
+                                                         void* dxb = nullptr) {
   constexpr int D = NSEG * 256;
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -284,6 +286,7 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd_v(const void* __restrict_
     v.z = rs * (g[s].z - sg - xh[s].z * sgx); v.w = rs * (g[s].w - sg - xh[s].w * sgx);
     if (accumulate) { v.x = o[s].x + v.x; v.y = o[s].y + v.y; v.z = o[s].z + v.z; v.w = o[s].w + v.w; }
     dxr[s * 64 + lane] = v;
+    if (EMIT) st4((__bf16*)nullptr, dxb, r * (D / 4) + s * 64 + lane, v);
   }
 }
 template <typename T> bool layernorm_fwd_v(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
@@ -298,8 +301,17 @@ template <typename T> bool layernorm_fwd_v(const float* x, const float* gamma, c
   return false;
 }
 template <typename T> bool layernorm_bwd_v(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
-                                           float* dx, long R, int D, int accumulate, hipStream_t st) {
+                                           float* dx, long R, int D, int accumulate, hipStream_t st, void* dxb = nullptr) {
   const dim3 grid((unsigned)((R + 3) / 4)), blk(256);
+  if (dxb) {
+    switch (D) {
+      case 256: k_layernorm_bwd_v<T, 1, true><<<grid, blk, 0, st>>>(dy, x, gamma, mean, rstd, dx, R, accumulate, dxb); return true;
+      case 512: k_layernorm_bwd_v<T, 2, true><<<grid, blk, 0, st>>>(dy, x, gamma, mean, rstd, dx, R, accumulate, dxb); return true;
+      case 768: k_layernorm_bwd_v<T, 3, true><<<grid, blk, 0, st>>>(dy, x, gamma, mean, rstd, dx, R, accumulate, dxb); return true;
+      case 1024: k_layernorm_bwd_v<T, 4, true><<<grid, blk, 0, st>>>(dy, x, gamma, mean, rstd, dx, R, accumulate, dxb); return true;
+    }
+    return false;
+  }
   switch (D) {
     case 256: k_layernorm_bwd_v<T, 1><<<grid, blk, 0, st>>>(dy, x, gamma, mean, rstd, dx, R, accumulate); return true;
     case 512: k_layernorm_bwd_v<T, 2><<<grid, blk, 0, st>>>(dy, x, gamma, mean, rstd, dx, R, accumulate); return true;
@@ -421,6 +433,21 @@ extern "C" int cddmsl_layernorm_bwd(const void* dy, const float* x, const float*
   if (dtype == 0) k_layernorm_bwd<__bf16><<<grid, dim3(256), 0, (hipStream_t)stream>>>(dy, x, gamma, mean, rstd, dx, R, D, accumulate);
   else k_layernorm_bwd<float><<<grid, dim3(256), 0, (hipStream_t)stream>>>(dy, x, gamma, mean, rstd, dx, R, D, accumulate);
   return launch_status();
+}
+// cddmsl_layernorm_bwd on the vector kernel, which also writes dx_bf16 = bf16(dx) [R][D].  *emitted = 1 when it did; rows the vector
+// kernel does not take (D not 256/512/768/1024, unaligned pointers) go through the scalar kernel, which writes no copy: *emitted = 0.
+extern "C" int cddmsl_layernorm_bwd_emit(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                         float* dx, void* dx_bf16, long R, int D, int accumulate, int dtype, int* emitted, void* stream) {
+  if (R < 0 || D <= 0 || (dtype != 0 && dtype != 1) || !dx_bf16 || !emitted) return CDDMSL_ERR_ARG;
+  *emitted = 0;
+  if (R == 0) return CDDMSL_OK;
+  if (aligned16(dy, x, gamma, dx, dx_bf16) &&
+      (dtype == 0 ? layernorm_bwd_v<__bf16>(dy, x, gamma, mean, rstd, dx, R, D, accumulate, (hipStream_t)stream, dx_bf16)
+                  : layernorm_bwd_v<float>(dy, x, gamma, mean, rstd, dx, R, D, accumulate, (hipStream_t)stream, dx_bf16))) {
+    *emitted = 1;
+    return launch_status();
+  }
+  return cddmsl_layernorm_bwd(dy, x, gamma, mean, rstd, dx, R, D, accumulate, dtype, stream);
 }
 extern "C" int cddmsl_focal_ce_fwd(const float* logits, const long* target, float* row_loss, float* probs, long R, int C,
                                    float gamma, int bg_class, float bg_weight, void* stream) {

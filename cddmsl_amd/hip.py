@@ -41,6 +41,9 @@ def _L():
         L.cddmsl_avgpool2_fwd.argtypes = [vp, vp] + [ci] * 5 + [vp]
         L.cddmsl_avgpool2_bwd.argtypes = [vp] * 4 + [ci] * 5 + [vp]
         L.cddmsl_avgpool2_bwd_q8.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 4
+        L.cddmsl_avgpool2_fwd_bits.argtypes = [vp] * 3 + [ci] * 5 + [vp]
+        L.cddmsl_avgpool2_bwd_bits.argtypes = [vp] * 3 + [ci] * 5 + [vp]
+        L.cddmsl_conv3x3_pool_fwd.argtypes = [vp] * 6 + [ci] * 7 + [vp]
         L.cddmsl_attn_tokens_fwd.argtypes = [vp] * 3 + [ci] * 5 + [vp]
         L.cddmsl_attn_tokens_bwd.argtypes = [vp] * 4 + [ci] * 5 + [vp]
         L.cddmsl_attnpool_softmax_fwd.argtypes = [vp] * 3 + [c_long, ci, ci, ci, cf, ci, vp]
@@ -75,6 +78,7 @@ def _L():
         L.cddmsl_cosine_logits_bwd.argtypes = [vp] * 5 + [c_long, ci, ci, cf, ci, vp]
         L.cddmsl_layernorm_fwd.argtypes = [vp] * 6 + [c_long, ci, cf, ci, vp]
         L.cddmsl_layernorm_bwd.argtypes = [vp] * 6 + [c_long, ci, ci, ci, vp]
+        L.cddmsl_layernorm_bwd_emit.argtypes = [vp] * 7 + [c_long, ci, ci, ci, ctypes.POINTER(ci), vp]
         L.cddmsl_focal_ce_fwd.argtypes = [vp] * 4 + [c_long, ci, cf, ci, cf, vp]
         L.cddmsl_focal_ce_bwd.argtypes = [vp] * 5 + [c_long, ci, cf, ci, cf, vp]
         L.cddmsl_attn_small_fwd.argtypes = [vp] * 4 + [ci] * 8 + [cf, ci, vp]
@@ -282,6 +286,33 @@ def conv_fwd(x, w, scale=None, bias=None, residual=None, relu=False, relu_mask=N
                              + (relu_mask.numel() * relu_mask.element_size() if relu_mask is not None else 0)))
     if y8 is not None:
         y._fp8 = (y8, emit8[0].data_ptr())
+    return y
+
+
+def conv3x3_pool_fwd(x, w, scale, bias, relu_mask=None, stride=1):
+    """The stem's third convolution and its AvgPool2d(2) in one launch: x [N,H,W,32] bf16, w [64,3,3,32] -> [N,H//2,W//2,64] =
+    avgpool2_fwd(conv_fwd(x, w, scale, bias, relu=True, pad=1)), bit-identical; the full-resolution map is never written.  The library
+    refuses (``HipLibraryError``) anything but that layer: f32, other widths, ``stride`` != 1, a ``relu_mask``."""
+    require_cuda(x, w, scale, bias, relu_mask)
+    assert x.dim() == 4 and w.dim() == 4 and x.is_contiguous() and w.is_contiguous() and x.dtype == w.dtype
+    N, H, W, Cin = x.shape
+    Cout, KH, KW, Cin2 = w.shape
+    assert (KH, KW, Cin2) == (3, 3, Cin), (x.shape, w.shape)
+    for v in (scale, bias):
+        assert v is not None and v.dtype == torch.float32 and v.numel() == Cout and v.is_contiguous()
+    assert relu_mask is None or (relu_mask.dtype == x.dtype and relu_mask.is_contiguous())
+    y = torch.empty((N, H // 2, W // 2, Cout), device=x.device, dtype=x.dtype)
+
+    def launch():
+        return _L().cddmsl_conv3x3_pool_fwd(ptr(x), ptr(w), ptr(y), ptr(scale), ptr(bias), ptr(relu_mask), N, H, W, Cin, Cout, stride,
+                                            _dt(x), stream_ptr())
+    e0 = PROFILE.begin(plan=launch) if PROFILE.on else None
+    check(launch(), "cddmsl_conv3x3_pool_fwd")
+    # booked under the row of the unfused launch (same M, N, K: the convolution is computed at the even rows / columns in full);
+    # algorithmic bytes: x and w once, the POOLED map written
+    Mc = N * (H // 2) * (W // 2) * 4
+    PROFILE.end(e0, "k_conv3x3_small", 2.0 * Mc * Cout * 9 * Cin, (Mc, Cout, 9 * Cin, 3, 2, 1),
+                nbytes=float(x.numel() * x.element_size() + w.numel() * w.element_size() + y.numel() * y.element_size()))
     return y
 
 
@@ -567,6 +598,31 @@ def avgpool2_fwd(x):
     y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=x.dtype)
     check(_L().cddmsl_avgpool2_fwd(ptr(x), ptr(y), N, H, W, C, _dt(x), stream_ptr()), "cddmsl_avgpool2_fwd")
     return y
+
+
+@_timed("avgpool2_fwd")
+def avgpool2_fwd_bits(x):
+    """(avgpool2_fwd(x), bits): bits [N,H//2,W//2,C//8] int32, byte (dy*2+dx) of a word = the 8 bits x[2oy+dy][2ox+dx][8c+j] > 0 (bit j)
+    -- the ReLU mask ``avgpool2_bwd_bits`` needs, at 1/16 of x's bytes.  bf16 only."""
+    require_cuda(x)
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    N, H, W, C = x.shape
+    y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=x.dtype)
+    bits = torch.empty((N, H // 2, W // 2, C // 8), device=x.device, dtype=torch.int32)
+    check(_L().cddmsl_avgpool2_fwd_bits(ptr(x), ptr(y), ptr(bits), N, H, W, C, _dt(x), stream_ptr()), "cddmsl_avgpool2_fwd_bits")
+    return y, bits
+
+
+@_timed("avgpool2_bwd")
+def avgpool2_bwd_bits(dy, in_shape, bits):
+    """avgpool2_bwd(dy, in_shape, mask=x) with the mask given as ``avgpool2_fwd_bits(x)[1]``; bit-identical.  bf16 only."""
+    require_cuda(dy, bits)
+    N, H, W, C = in_shape
+    assert dy.dtype == torch.bfloat16 and dy.is_contiguous() and tuple(dy.shape) == (N, H // 2, W // 2, C)
+    assert bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (N, H // 2, W // 2, C // 8)
+    dx = torch.empty(in_shape, device=dy.device, dtype=dy.dtype)
+    check(_L().cddmsl_avgpool2_bwd_bits(ptr(dy), ptr(bits), ptr(dx), N, H, W, C, _dt(dy), stream_ptr()), "cddmsl_avgpool2_bwd_bits")
+    return dx
 
 
 @_timed("avgpool2_bwd")
@@ -1153,8 +1209,10 @@ def layernorm_fwd(x, gamma, beta, out_dtype, eps=1e-5):
 
 
 @_timed("layernorm")
-def layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=None):
-    """dx = LN'(dy); with ``accumulate_into`` (f32 [R,D], contiguous) the result is ADDED to that tensor in place and it is returned"""
+def layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=None, emit_bf16=False):
+    """dx = LN'(dy); with ``accumulate_into`` (f32 [R,D], contiguous) the result is ADDED to that tensor in place and it is returned.
+    ``emit_bf16``: returns (dx, dx_bf16) -- dx_bf16 = dx.to(bfloat16) written by the same kernel, or None where the rows took the
+    scalar kernel (which writes no copy)."""
     require_cuda(dy, x, gamma, mean, rstd, accumulate_into)
     R, D = x.shape
     dy = dy.contiguous()
@@ -1165,6 +1223,11 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=None):
     else:
         assert accumulate_into.dtype == torch.float32 and accumulate_into.is_contiguous() and accumulate_into.shape == x.shape
         dx, acc = accumulate_into, 1
+    if emit_bf16:
+        dxb, did = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16), c_int(0)
+        check(_L().cddmsl_layernorm_bwd_emit(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dxb), R, D, acc, _dt(dy),
+                                             ctypes.byref(did), stream_ptr()), "cddmsl_layernorm_bwd_emit")
+        return dx, (dxb if did.value else None)
     check(_L().cddmsl_layernorm_bwd(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), R, D, acc, _dt(dy), stream_ptr()),
           "cddmsl_layernorm_bwd")
     return dx

@@ -374,6 +374,34 @@ def cat_prepared(weights, dtype):
 # ------------------------------------------------------------------------------------------------
 # generic conv / linear with bias (+ReLU)   -- RPN head, projections, projector, mapper linears
 # ------------------------------------------------------------------------------------------------
+# The mapper's f32 residual-stream gradient is cast to the compute dtype by every sublayer it enters (the GEMM operand).  The
+# LayerNorm backward that WROTE that gradient can store the bf16 rounding next to it (hip.layernorm_bwd emit_bf16): it is handed
+# over here, keyed by the f32 tensor's storage -- no tensor attribute has to survive the autograd engine.  One entry: a copy not
+# picked up by the time the next one is registered is dropped.  The entry keeps the f32 tensor alive (its address cannot be handed
+# to another tensor meanwhile) and remembers its version (an in-place write through torch invalidates the copy).
+_BF16_OF = {}
+
+
+def _bf16_key(g):
+    # (the element count, not the shape: the same contiguous rows reach a linear layer's backward as [1, 1, rows, D])
+    return (g.data_ptr(), g.numel(), g.device)
+
+
+def _register_bf16(g, gb):
+    _BF16_OF.clear()
+    if gb is not None:
+        _BF16_OF[_bf16_key(g)] = (g, g._version, gb)
+
+
+def bf16_of(g):
+    """``g.to(torch.bfloat16)`` for a contiguous f32 ``g``: the copy its producer registered (removed on use), or the cast."""
+    if _BF16_OF and g.dtype == torch.float32 and g.is_contiguous():
+        e = _BF16_OF.pop(_bf16_key(g), None)
+        if e is not None and e[0]._version == e[1] and g._version == e[1]:
+            return e[2].view(g.shape)
+    return g.to(torch.bfloat16)
+
+
 class ConvFn(torch.autograd.Function):
     """y = relu?(conv(x, W) + b).  x NHWC T; W f32 master; optional f32 output.  ``train_w`` False = frozen
     weights (input gradient only)."""
@@ -401,7 +429,7 @@ class ConvFn(torch.autograd.Function):
         if relu:
             dy = hip.relu_bwd(dy, y if y.dtype == T else y.to(T))
         elif dy.dtype != T:
-            dy = dy.to(T)
+            dy = bf16_of(dy) if T == torch.bfloat16 else dy.to(T)
         w = ctx.pw.param
         if train_w:
             if f8:
@@ -455,7 +483,7 @@ class FrozenMlpFn(torch.autograd.Function):
         M = h.shape[2]
         g = dy.contiguous()
         if g.dtype != T:
-            g = g.to(T)
+            g = bf16_of(g) if T == torch.bfloat16 else g.to(T)
         _, w2d = ctx.pw[1].get(T, need_dgrad=True)
         _, w1d = ctx.pw[0].get(T, need_dgrad=True)
         dh = hip.conv_fwd(g.view(1, 1, M, -1), w2d, relu_mask=h)
@@ -543,6 +571,16 @@ class BlockParams:
         self.pw = tuple(None if w is None else PreparedWeight(w, b[0], frozen) for w, b in zip(self.w, self.bn))
 
 
+def _pool_bits_wanted(bp, o2):
+    """Does a pooled block keep its conv2 output ``o2`` for the backward pass as ONE MASK BYTE per 16-byte chunk
+    (hip.avgpool2_fwd_bits) instead of the tensor?  The backward reads o2 for its ReLU mask alone.  bf16; not where the backward
+    pooling pass also writes the e4m3 copy of its result (fp8 configuration: that kernel reads the full mask).
+    CDDMSL_POOL_MASK_BITS=0 (read per call, so one process can A/B) keeps o2."""
+    if os.environ.get("CDDMSL_POOL_MASK_BITS", "1") == "0" or o2.dtype != torch.bfloat16 or o2.shape[-1] % 8:
+        return False
+    return not (bp.fp8 and _fp8_dgrad_wanted(bp.pw[1], o2.shape, 1, True))
+
+
 def _block_forward(x, bp, save, px_given=None, next_pw=None, out_spec=None):
     # (next_pw: conv1 of the block that reads this block's output -- fp8 configuration: its e4m3 copy is written here)
     """Bottleneck forward (clip_backbone.py:57-70).  AvgPool2d(stride) runs as its own HBM-bound kernel: fusing it into
@@ -558,7 +596,11 @@ def _block_forward(x, bp, save, px_given=None, next_pw=None, out_spec=None):
     e8o2 = fp8_act_slot(bp.pw[2]).emit() if save and not pool and _fp8_wgrad1x1_wanted(bp.pw[2], M2, f8) else None
     o2 = conv_fwd_auto(o1, bp.pw[1], s2, b2, f8, emit8=e8o2, relu=True, pad=1)
     o2_8 = _fp8_made_for(o2, bp.pw[2]) if e8o2 is not None else None
-    p2 = hip.avgpool2_fwd(o2) if pool else o2
+    o2_shape, bits = tuple(o2.shape), None
+    if pool and save and _pool_bits_wanted(bp, o2):
+        p2, bits = hip.avgpool2_fwd_bits(o2)          # (o2 itself is not kept: ``bits`` takes its slot in the saved list)
+    else:
+        p2 = hip.avgpool2_fwd(o2) if pool else o2
     if pool and px_given is not None and tuple(px_given.shape) == (x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.shape[3]):
         px = px_given                              # the producer of x pooled it on the way (roi_align with_pooled)
     else:
@@ -569,15 +611,17 @@ def _block_forward(x, bp, save, px_given=None, next_pw=None, out_spec=None):
         idn = x
     out_shape = (p2.shape[0], p2.shape[1], p2.shape[2], _ohwi(bp.w[2]).shape[0])
     out = conv_fwd_auto(p2, bp.pw[2], s3, b3, f8, emit8=fp8_emit_for(next_pw, out_shape, 0, f8), residual=idn, relu=True, out_spec=out_spec)
-    return out, ((o1, o2, p2 if pool else None, px if pool else None, (x8, _fp8_made_for(o1, bp.pw[1]) if f8 else None, o2_8)) if save else None)
+    return out, ((o1, o2 if bits is None else bits, p2 if pool else None, px if pool else None,
+                  (x8, _fp8_made_for(o1, bp.pw[1]) if f8 else None, o2_8), o2_shape) if save else None)
 
 
-def _block_backward(gs, x, o1, o2, p2, px, bp, need_dx, mask_x, prev_bp=None, c8=(None, None, None)):
+def _block_backward(gs, x, o1, o2, p2, px, bp, need_dx, mask_x, prev_bp=None, c8=(None, None, None), o2_shape=None):
     """gs = dL/d(pre-ReLU sum) of this block (already masked by out>0).  Returns dL/dx, masked by x>0 when
     ``mask_x`` (x is the previous block's post-ReLU output) so it is directly the previous block's ``gs``.
     fp8 configuration: the input-gradient convolutions with a long reduction (conv3's, conv2's, the downsample conv's) run on
     e4m3 operands (``dgrad_auto``); ``prev_bp`` = the block that receives the returned gradient as ITS ``gs`` (its e4m3 copy is
-    then written by this block's last launch)."""
+    then written by this block's last launch).  A pooled block may have kept ``o2`` as mask bits (int32, ``_pool_bits_wanted``);
+    ``o2_shape`` is then the tensor's shape."""
     T = x.dtype
     (s1, _), (s2, _), (s3, _), bnd = bp.bn
     pool = bp.stride > 1
@@ -587,7 +631,9 @@ def _block_backward(gs, x, o1, o2, p2, px, bp, need_dx, mask_x, prev_bp=None, c8
     gs_slot = fp8_slot_of(bp, "_fp8_gs") if f8 else None
     d2_slot = fp8_slot_of(bp.pw[1], "_fp8_g") if f8 else None
     x8, o1_8, o2_8 = c8                               # e4m3 copies kept from the forward pass (fp8 configuration): inputs of conv1, conv2, conv3
-    M2 = o2.shape[0] * o2.shape[1] * o2.shape[2]
+    o2_bits = o2.dtype == torch.int32
+    o2_shape = tuple(o2.shape) if o2_shape is None else tuple(o2_shape)
+    M2 = o2_shape[0] * o2_shape[1] * o2_shape[2]
     if o2_8 is not None and not pool:
         wgrad_auto(o2, gs, bp.pw[2], s3, 0, _ohwi(_grad_buf(w3p)), f8, o2_8, gs_slot, taps_only=False)
     else:
@@ -595,9 +641,12 @@ def _block_backward(gs, x, o1, o2, p2, px, bp, need_dx, mask_x, prev_bp=None, c8
     d1_slot = fp8_slot_of(bp.pw[0], "_fp8_g") if f8 and x8 is not None and _fp8_wgrad1x1_wanted(bp.pw[0], M2, f8) else None
     if pool:
         dp2 = dgrad_auto(gs, bp.pw[2], f8, gs_slot)
-        dpre2 = hip.avgpool2_bwd(dp2, tuple(o2.shape), mask=o2, emit8=d2_slot.emit() if f8 and _fp8_dgrad_wanted(bp.pw[1], o2.shape, 1, f8) else None)
+        if o2_bits:
+            dpre2 = hip.avgpool2_bwd_bits(dp2, o2_shape, o2)
+        else:
+            dpre2 = hip.avgpool2_bwd(dp2, o2_shape, mask=o2, emit8=d2_slot.emit() if f8 and _fp8_dgrad_wanted(bp.pw[1], o2_shape, 1, f8) else None)
     else:
-        e8 = d2_slot.emit() if f8 and _fp8_dgrad_wanted(bp.pw[1], o2.shape, 1, f8) else None
+        e8 = d2_slot.emit() if f8 and _fp8_dgrad_wanted(bp.pw[1], o2_shape, 1, f8) else None
         dpre2 = dgrad_auto(gs, bp.pw[2], f8, gs_slot, emit8=e8, relu_mask=o2)
     # (conv2's input gradient first: it leaves the e4m3 copy of dpre2 attached, which the fp8 weight gradient reads as well)
     dpre1 = dgrad_auto(dpre2, bp.pw[1], f8, d2_slot, pad=1, relu_mask=o1, emit8=d1_slot.emit() if d1_slot is not None else None)
@@ -631,14 +680,15 @@ class ResStageFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, anchor, blocks, out_grad_premasked=False, px0=None, out_spec=None):
         ctx.out_grad_premasked = out_grad_premasked
-        saved, o1_8s = [x], []
+        saved, o1_8s, o2_shapes = [x], [], []
         cur = x
         for bi, bp in enumerate(blocks):
             cur, mids = _block_forward(cur, bp, True, px0 if bi == 0 else None, blocks[bi + 1].pw[0] if bi + 1 < len(blocks) else None,
                                        out_spec if bi + 1 == len(blocks) else None)
             saved += [mids[0], mids[1], mids[2], mids[3], cur]
             o1_8s += list(mids[4])
-        ctx.blocks = blocks
+            o2_shapes.append(mids[5])
+        ctx.blocks, ctx.o2_shapes = blocks, o2_shapes
         ctx.save_for_backward(*saved, *o1_8s)         # (fp8 configuration: three e4m3 input copies per block, for the weight gradients)
         return cur
 
@@ -652,7 +702,7 @@ class ResStageFn(torch.autograd.Function):
         for i in range(len(blocks) - 1, -1, -1):
             x, o1, o2, p2, px = saved[5 * i: 5 * i + 5]
             gs = _block_backward(gs, x, o1, o2, p2, px, blocks[i], need_dx or i > 0, mask_x=i > 0, prev_bp=blocks[i - 1] if i > 0 else None,
-                                 c8=tuple(o1_8s[3 * i: 3 * i + 3]))
+                                 c8=tuple(o1_8s[3 * i: 3 * i + 3]), o2_shape=ctx.o2_shapes[i])
         return gs, None, None, None, None, None
 
 
@@ -757,7 +807,7 @@ def roi_downsample_on_map(K, out_size, N, H, W):
     return K * (out_size // 2) ** 2 > N * H * W
 
 
-def _roi_block0_forward(feat, rois, bp, out_size, scale, sr, extra, next_pw=None, on_map=None):
+def _roi_block0_forward(feat, rois, bp, out_size, scale, sr, extra, next_pw=None, on_map=None, save=False):
     """First Bottleneck of the RoI head's layer4 (clip_roi_heads.py:113-115 -> clip_backbone.py:57-70) on the pooled crops, WITHOUT
     the crops: RoIAlign is a linear map over pixels and conv1 / the downsample conv are 1x1 (linear over channels), so
 
@@ -773,7 +823,8 @@ def _roi_block0_forward(feat, rois, bp, out_size, scale, sr, extra, next_pw=None
 
     and the pooled crops ``px`` are not formed either (only the appended maps' are: they keep the literal arithmetic).
     ``on_map``: that decision when the caller took it already (RoIStageFn: its backward follows the same one).
-    Returns (o1, o2, p2, px, out, e4m3 copy of o1 or None); ``px`` = the pooled appended maps (or None) when commuted."""
+    Returns (o1, o2, p2, px, out, e4m3 copy of o1 or None, o2's shape); ``px`` = the pooled appended maps (or None) when commuted.
+    ``save`` (the caller keeps the results for the backward pass): ``o2`` may come back as its mask bits (``_pool_bits_wanted``)."""
     T = feat.dtype
     (s1, b1), (s2, b2), (s3, b3), bnd = bp.bn
     w1, _ = bp.pw[0].get(T, False)
@@ -804,12 +855,16 @@ def _roi_block0_forward(feat, rois, bp, out_size, scale, sr, extra, next_pw=None
         if idn is None:
             px[K:].copy_(hip.avgpool2_fwd(extra))
     o2 = conv_fwd_auto(o1, bp.pw[1], s2, b2, f8, relu=True, pad=1)
-    p2 = hip.avgpool2_fwd(o2)
+    o2_shape = tuple(o2.shape)
+    if save and _pool_bits_wanted(bp, o2):
+        p2, o2 = hip.avgpool2_fwd_bits(o2)
+    else:
+        p2 = hip.avgpool2_fwd(o2)
     if idn is None:
         idn = conv_fwd_auto(px, bp.pw[3], bnd[0], bnd[1], f8)
     out_shape = (p2.shape[0], p2.shape[1], p2.shape[2], _ohwi(bp.w[2]).shape[0])
     out = conv_fwd_auto(p2, bp.pw[2], s3, b3, f8, emit8=fp8_emit_for(next_pw, out_shape, 0, f8), residual=idn, relu=True)
-    return o1, o2, p2, px, out, (_fp8_made_for(o1, bp.pw[1]) if f8 else None)
+    return o1, o2, p2, px, out, (_fp8_made_for(o1, bp.pw[1]) if f8 else None), o2_shape
 
 
 class RoIStageFn(torch.autograd.Function):
@@ -825,12 +880,14 @@ class RoIStageFn(torch.autograd.Function):
         feat = feat.contiguous()
         nxt = lambda i: blocks[i + 1].pw[0] if i + 1 < len(blocks) else None
         on_map = roi_downsample_on_map(rois.shape[0], out_size, feat.shape[0], feat.shape[1], feat.shape[2])
-        o1, o2, p2, px, cur, o1_8 = _roi_block0_forward(feat, rois, blocks[0], out_size, scale, sr, extra, nxt(0), on_map)
-        saved, o1_8s = [feat, rois, roi_start, extra, o1, o2, p2, px, cur], [None, o1_8, None]
+        o1, o2, p2, px, cur, o1_8, o2_shape = _roi_block0_forward(feat, rois, blocks[0], out_size, scale, sr, extra, nxt(0), on_map, save=True)
+        saved, o1_8s, o2_shapes = [feat, rois, roi_start, extra, o1, o2, p2, px, cur], [None, o1_8, None], [o2_shape]
         for bi, bp in enumerate(blocks[1:], start=1):
             cur, mids = _block_forward(cur, bp, True, None, nxt(bi))
             saved += [mids[0], mids[1], mids[2], mids[3], cur]
             o1_8s += list(mids[4])
+            o2_shapes.append(mids[5])
+        ctx.o2_shapes = o2_shapes
         ctx.blocks, ctx.meta = blocks, (out_size, scale, sr, out_grad_premasked, on_map)
         ctx.save_for_backward(*saved, *o1_8s)         # (fp8 configuration: three e4m3 input copies per block, for the weight gradients)
         return cur
@@ -845,9 +902,11 @@ class RoIStageFn(torch.autograd.Function):
         gs = g.contiguous() if premasked else hip.relu_bwd(g.contiguous(), st[-1])
         for i in range(len(blocks) - 1, 0, -1):
             o1, o2, p2, px = st[5 * i: 5 * i + 4]
-            gs = _block_backward(gs, st[5 * i - 1], o1, o2, p2, px, blocks[i], True, mask_x=True, prev_bp=blocks[i - 1], c8=tuple(o1_8s[3 * i: 3 * i + 3]))
+            gs = _block_backward(gs, st[5 * i - 1], o1, o2, p2, px, blocks[i], True, mask_x=True, prev_bp=blocks[i - 1], c8=tuple(o1_8s[3 * i: 3 * i + 3]),
+                                 o2_shape=ctx.o2_shapes[i])
         bp = blocks[0]
         o1, o2, p2, px = st[0:4]
+        o2_shape = ctx.o2_shapes[0]                  # (o2 may be its mask bits: _pool_bits_wanted)
         T = o1.dtype
         (s1, _), (s2, _), (s3, _), bnd = bp.bn
         w1p, w2p, w3p, wdp = bp.w
@@ -857,8 +916,11 @@ class RoIStageFn(torch.autograd.Function):
         gs_slot = fp8_slot_of(bp, "_fp8_gs") if f8 else None
         d2_slot = fp8_slot_of(bp.pw[1], "_fp8_g") if f8 else None
         hip.conv_wgrad(p2, gs, shp(w3p), s3, out=_ohwi(_grad_buf(w3p)))
-        e8 = d2_slot.emit() if f8 and _fp8_dgrad_wanted(bp.pw[1], o2.shape, 1, f8) else None   # (the e4m3 copy conv2's two gradient GEMMs read)
-        dpre2 = hip.avgpool2_bwd(dgrad_auto(gs, bp.pw[2], f8, gs_slot), tuple(o2.shape), mask=o2, emit8=e8)
+        if o2.dtype == torch.int32:
+            dpre2 = hip.avgpool2_bwd_bits(dgrad_auto(gs, bp.pw[2], f8, gs_slot), o2_shape, o2)
+        else:
+            e8 = d2_slot.emit() if f8 and _fp8_dgrad_wanted(bp.pw[1], o2_shape, 1, f8) else None   # (the e4m3 copy conv2's two gradient GEMMs read)
+            dpre2 = hip.avgpool2_bwd(dgrad_auto(gs, bp.pw[2], f8, gs_slot), o2_shape, mask=o2, emit8=e8)
         dpre1 = dgrad_auto(dpre2, bp.pw[1], f8, d2_slot, pad=1, relu_mask=o1)                # [K+E,14,14,planes] wrt bn1's output
         wgrad_auto(o1, dpre2, bp.pw[1], s2, 1, _ohwi(_grad_buf(w2p)), f8, o1_8s[1], d2_slot)
         N, H, W, C = feat.shape
@@ -1203,18 +1265,29 @@ class LayerNormSkipFn(torch.autograd.Function):
         x = x.contiguous()
         y, mean, rstd = hip.layernorm_fwd(x, gamma, beta, out_dtype)
         ctx.save_for_backward(x, gamma, mean, rstd)
+        ctx.emit = out_dtype == torch.bfloat16
         return y, x.view_as(x)
 
     @staticmethod
     def backward(ctx, dy, dskip):
         x, gamma, mean, rstd = ctx.saved_tensors
+        # bf16 compute: the kernel also writes the bf16 copy of the gradient it returns, for the sublayer below (``bf16_of``)
+        emit = ctx.emit and os.environ.get("CDDMSL_LN_EMIT_BF16", "1") != "0"
         if dskip is None:
+            if emit and dy is not None:
+                dx, dxb = hip.layernorm_bwd(dy, x, gamma, mean, rstd, emit_bf16=True)
+                _register_bf16(dx, dxb)
+                return dx, None, None, None
             return hip.layernorm_bwd(dy, x, gamma, mean, rstd), None, None, None
         # In place on the incoming skip gradient: its only other consumer is the sublayer branch hanging off the same residual
         # add, and that branch has necessarily run already (its result is the ``dy`` in hand).
         acc = dskip.contiguous()
         if dy is None:
             return acc, None, None, None
+        if emit:
+            dx, dxb = hip.layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=acc, emit_bf16=True)
+            _register_bf16(dx, dxb)
+            return dx, None, None, None
         return hip.layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=acc), None, None, None
 
 

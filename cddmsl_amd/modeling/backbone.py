@@ -8,6 +8,7 @@ compatible), same ``Backbone`` ABI (``forward(x NCHW) -> dict``, ``output_shape(
 Tensors crossing the module boundary are logically NCHW in ``torch.channels_last`` memory (= NHWC for the kernels,
 zero-copy).  FrozenBN is never a pass of its own: its affine is folded into the conv epilogues.
 """
+import os
 from collections import OrderedDict
 
 import torch
@@ -204,6 +205,10 @@ class ModifiedResNet(nn.Module):
         (s1, b1), (s2, b2), (s3, b3) = self.bn1.affine(), self.bn2.affine(), self.bn3.affine()
         x = hip.conv_fwd(x, w1, s1, b1, relu=True, stride=2, pad=1)
         x = hip.conv_fwd(x, w2, s2, b2, relu=True, pad=1)
+        # the third convolution writes the pooled map itself (bf16; CDDMSL_STEM_POOL=0, read per call: the two launches)
+        # (the kernel is the 32 -> 64 layer's: RN50 / RN101 widths)
+        if x.dtype == torch.bfloat16 and tuple(w3.shape) == (64, 3, 3, 32) and os.environ.get("CDDMSL_STEM_POOL", "1") != "0":
+            return hip.conv3x3_pool_fwd(x, w3, s3, b3)
         x = hip.conv_fwd(x, w3, s3, b3, relu=True, pad=1)
         return hip.avgpool2_fwd(x)
 

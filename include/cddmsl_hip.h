@@ -40,6 +40,12 @@ int cddmsl_abi_version(void);
 int cddmsl_conv_fwd(const void* x, const void* w, void* y, const float* scale, const float* bias, const void* residual,
                     const void* relu_mask, int Nimg, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad,
                     int pool, int ldy, int ldr, int ldm, int relu, int out_f32, int dtype, void* stream);
+/* The CLIP stem's third convolution and the AvgPool2d(2) behind it (clip_backbone.py:139-147) as ONE launch:
+ *   y [Nimg][Hi/2][Wi/2][64] = avgpool2(relu(conv3x3(x, pad 1) * scale + bias)), bit-identical to cddmsl_conv_fwd + cddmsl_avgpool2_fwd;
+ * the full-resolution map is never written.  bf16 (dtype 0), Cin 32, Cout 64, stride 1, scale and bias given, relu_mask NULL:
+ * anything else is CDDMSL_ERR_ARG.  Plan-only mode reports kernel 8. */
+int cddmsl_conv3x3_pool_fwd(const void* x, const void* w, void* y, const float* scale, const float* bias, const void* relu_mask,
+                            int Nimg, int Hi, int Wi, int Cin, int Cout, int stride, int dtype, void* stream);
 /* One frozen 64-plane CLIP Bottleneck behind its conv1 as ONE launch (clip_backbone.py:57-70 at stride 1; bf16, forward only):
  *   o2  = relu(o1 (*) w2 * s2 + b2)                   3x3 pad 1, 64 -> 64, never written to memory
  *   out = relu(o2 . w3 * s3 + b3 + residual)          [Nimg][H][W][256]
@@ -316,6 +322,10 @@ int cddmsl_layernorm_fwd(const float* x, const float* gamma, const float* beta, 
                          float eps, int dtype, void* stream);
 int cddmsl_layernorm_bwd(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd, float* dx,
                          long R, int D, int accumulate, int dtype, void* stream);
+/* the same on the vector kernel (D 256/512/768/1024, 16-byte aligned) with a second output dx_bf16 [R][D] = bf16(dx), nearest even;
+ * *emitted = 1 when it was written, 0 when the rows took the scalar kernel (dx alone is written then) */
+int cddmsl_layernorm_bwd_emit(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd, float* dx,
+                              void* dx_bf16, long R, int D, int accumulate, int dtype, int* emitted, void* stream);
 int cddmsl_focal_ce_fwd(const float* logits, const long* target, float* row_loss, float* probs, long R, int C, float gamma,
                         int bg_class, float bg_weight, void* stream);
 int cddmsl_focal_ce_bwd(const float* logits, const long* target, const float* probs, const float* gscale, float* dlogits, long R,
@@ -350,6 +360,10 @@ int cddmsl_preprocess224_batch(const unsigned char* const* imgs, const int* hs, 
 int cddmsl_avgpool2_fwd(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
 int cddmsl_avgpool2_bwd(const void* dy, const void* mask, const void* add, void* dx, int N, int H, int W, int C, int dtype,
                         void* stream);
+/* bf16 only: the forward also writes the ReLU mask of x, bits [N][H/2][W/2][C/8] u32 -- byte (dy*2+dx) of a word = (x[2oy+dy][2ox+dx][8c+j] > 0)
+ * in bit j; the backward reads that word instead of the full-resolution mask: dx = (bit ? dy/4 : 0), zero on a floor-dropped row / column */
+int cddmsl_avgpool2_fwd_bits(const void* x, void* y, void* bits, int N, int H, int W, int C, int dtype, void* stream);
+int cddmsl_avgpool2_bwd_bits(const void* dy, const void* bits, void* dx, int N, int H, int W, int C, int dtype, void* stream);
 /* fp8 configuration: the same pass (bf16 only) with a second output, y8 = e4m3 of sat(dx * q8[0]), max|dx| recorded in amax8 (64 floats) */
 int cddmsl_avgpool2_bwd_q8(const void* dy, const void* mask, const void* add, void* dx, int N, int H, int W, int C, void* y8,
                            const float* q8, float* amax8, void* stream);

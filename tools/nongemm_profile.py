@@ -64,12 +64,19 @@ def main():
     add("gemm_tn_batched", 2 * (tok + big) + 2 * big * 2, "Z = P.tok, dU = dS.tok (tokens read, [K,32,2048] written), dWv / dWk reductions ([K,32,2048] read)")
     add("gemm_nt_batched", 3 * big + 2 * (big + tok) + 3 * big, "U, dZ written; S = U.tok^T, dP = dZ.tok^T (both operands read); o, dq0 ([K,32,2048] read)")
     # avgpool: stem, layer2.0 / layer3.0 (o2 and x), RoI head o2 -> p2; two backbone passes (source, target) + the 224 branch (small)
+    # (switches of the three folded passes, read as the library's callers read them: the stem's pool inside its third convolution, the
+    #  pooled blocks' ReLU mask as one byte per 16-byte chunk, the bf16 copy of the mapper's residual gradient from the LayerNorm backward)
+    on = lambda k: os.environ.get(k, "1") != "0"
+    stem_pool, mask_bits, ln_emit = on("CDDMSL_STEM_POOL"), on("CDDMSL_POOL_MASK_BITS"), on("CDDMSL_LN_EMIT_BF16")
     bb = 2 * B
-    apf = bb * (400 * 667 * 64) * 2 * 1.25 + bb * (200 * 333 * (128 + 256)) * 2 * 1.25 + bb * (100 * 166 * (256 + 512)) * 2 * 1.25 + sum(k * 196 * 512 * 2 * 1.25 for k in Kp)
-    add("avgpool2_fwd", apf, "stem, layer2.0, layer3.0 (conv2 output and block input), RoI head conv2 output: read + quarter-size write")
-    apb = B * 2 * (200 * 333 * 128 + 100 * 166 * 256) * 2 * 2.25 + sum(k * 196 * 512 * 2 * 2.25 for k in Kp)
-    add("avgpool2_bwd", apb, "pooled gradient read, ReLU mask read, full-size gradient written")
-    add("layernorm", 16 * rows * 768 * (4 + 2) + 16 * rows * 768 * (2 + 4 + 4 + 4), "16 forward (f32 in, bf16 out) + 16 backward (bf16 dy, f32 x, f32 accumulate read + write) over [43520,768]")
+    o2b = B * 2 * (200 * 333 * 128 + 100 * 166 * 256) * 2 + sum(k * 196 * 512 * 2 for k in Kp)      # conv2 outputs of the trainable pooled blocks
+    apf = (0 if stem_pool else bb * (400 * 667 * 64) * 2 * 1.25) + (o2b / 16 if mask_bits else 0) + bb * (200 * 333 * (128 + 256)) * 2 * 1.25 + bb * (100 * 166 * (256 + 512)) * 2 * 1.25 + sum(k * 196 * 512 * 2 * 1.25 for k in Kp)
+    add("avgpool2_fwd", apf, ("" if stem_pool else "stem, ") + "layer2.0, layer3.0 (conv2 output and block input), RoI head conv2 output: read + quarter-size write"
+        + (" + mask bytes (1/16)" if mask_bits else ""))
+    apb = o2b * (1.25 + 1.0 / 16 if mask_bits else 2.25)
+    add("avgpool2_bwd", apb, "pooled gradient read, ReLU mask read" + (" (one byte per 16-byte chunk)" if mask_bits else "") + ", full-size gradient written")
+    add("layernorm", 16 * rows * 768 * (4 + 2) + 16 * rows * 768 * (2 + 4 + 4 + 4) + (13 * rows * 768 * 2 if ln_emit else 0),
+        "16 forward (f32 in, bf16 out) + 16 backward (bf16 dy, f32 x, f32 accumulate read + write" + ("; 13 also write the bf16 copy" if ln_emit else "") + ") over [43520,768]")
     add("relu_bwd", 0.0, "")
     table = []
     for name, v in sorted(tot.items(), key=lambda kv: -kv[1]["ms"]):
