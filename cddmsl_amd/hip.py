@@ -56,6 +56,7 @@ def _L():
         L.cddmsl_roi_align_forward.argtypes = [vp] * 5 + [ci] * 7 + [cf, ci, ci, ci, vp]
         L.cddmsl_roi_align_backward.argtypes = [vp] * 7 + [ci] * 7 + [cf, ci, ci, ci, vp]
         L.cddmsl_nms_anyorder.argtypes = [vp] * 4 + [ci, cf, vp, vp, vp]
+        L.cddmsl_soft_nms.argtypes = [vp] * 6 + [ci, ci, cf, cf, cf, ci, vp, vp, vp]
         L.cddmsl_roi_align_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
         L.cddmsl_roi_align_backward_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
         L.cddmsl_quantize_fp8.argtypes = [vp] * 4 + [c_long, ci, vp]
@@ -1039,6 +1040,38 @@ def nms_anyorder(boxes, scores, iou_threshold):
     check(_L().cddmsl_nms_anyorder(ptr(boxes), ptr(scores), ptr(keep), ptr(nkeep), K, iou_threshold, ptr(ws), ctypes.byref(nbytes), stream_ptr()),
           "cddmsl_nms_anyorder")
     return keep, nkeep
+
+
+SOFT_NMS_METHODS = {"gaussian": 0, "linear": 1, "hard": 2}
+SOFT_NMS_MAX_CANDIDATES = 32768      # cddmsl_soft_nms: candidates per call, any split over categories
+
+
+@_timed("soft_nms")
+def soft_nms(boxes, scores, idxs, method, sigma, iou_threshold, prune_threshold, max_keep=-1):
+    """layers/soft_nms.py batched_soft_nms(boxes [K,4], scores [K], idxs [K] int64, ...) on the per-category walk kernel ->
+    (keep int64 [K]: kept input indices in pick order, then -1; keep_scores f32 [K]: their rescored scores, valid up to nkeep;
+    nkeep int32 [1]), all on the device, no synchronisation.  ``method``: "gaussian" / "linear" / "hard" (or 0 / 1 / 2);
+    ``max_keep`` >= 0 stops every category's walk after that many picks and cuts the output there (the first max_keep entries
+    of the uncapped result)."""
+    require_cuda(boxes, scores, idxs)
+    K = boxes.shape[0]
+    assert boxes.dtype == scores.dtype == torch.float32 and idxs.dtype == torch.int64 and scores.numel() == idxs.numel() == K
+    assert boxes.is_contiguous() and scores.is_contiguous() and idxs.is_contiguous()
+    if isinstance(method, str):
+        if method not in SOFT_NMS_METHODS:
+            raise NotImplementedError("{} soft nms method not implemented.".format(method))
+        method = SOFT_NMS_METHODS[method]
+    keep = torch.empty(K, device=boxes.device, dtype=torch.int64)
+    keep_scores = torch.empty(K, device=boxes.device, dtype=torch.float32)
+    nkeep = torch.zeros(1, device=boxes.device, dtype=torch.int32)
+    nbytes = ctypes.c_size_t(0)
+    args = (K, int(method), float(sigma), float(iou_threshold), float(prune_threshold), int(max_keep))
+    check(_L().cddmsl_soft_nms(ptr(boxes), ptr(scores), ptr(idxs), ptr(keep), ptr(keep_scores), ptr(nkeep), *args, None, ctypes.byref(nbytes),
+                               stream_ptr()), "cddmsl_soft_nms(size)")
+    ws = workspace("soft_nms", max(nbytes.value, 1), boxes.device)
+    check(_L().cddmsl_soft_nms(ptr(boxes), ptr(scores), ptr(idxs), ptr(keep), ptr(keep_scores), ptr(nkeep), *args, ptr(ws), ctypes.byref(nbytes),
+                               stream_ptr()), "cddmsl_soft_nms")
+    return keep, keep_scores, nkeep
 
 
 @_timed("rpn_decode")

@@ -105,11 +105,34 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
     return ki[scores[ki].sort(descending=True, stable=True)[1]]
 
 
-def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, nms_thresh, topk_per_image, proposal_indices=False):
-    """fast_rcnn.py:130-209 (hard NMS): drop non-finite rows, clip, score threshold per (proposal, class), per-class NMS,
-    keep the top-k.  boxes [R, 4K], scores [R, K+1] -> (Instances, indices of the kept proposals).  As in the reference, those
-    indices count the rows left after the non-finite ones are dropped; ``proposal_indices=True`` maps them back to rows of the
-    input (the proposal each detection came from)."""
+SOFT_NMS_METHODS = tuple(hip.SOFT_NMS_METHODS)
+
+
+def batched_soft_nms(boxes, scores, idxs, method, gaussian_sigma, linear_threshold, prune_threshold, max_keep=-1):
+    """layers/soft_nms.py:85-132 -> (kept indices int64 in pick order, their rescored scores f32), on the per-category walk kernel
+    (hip.soft_nms): one launch sequence for all categories, ONE host readback (the number of picks).  ``max_keep`` >= 0 (not in
+    the reference's signature) returns the first max_keep entries and lets every category's walk stop there.  More candidates
+    than the kernel takes is an error, never a truncation."""
+    n = boxes.shape[0]
+    if method not in SOFT_NMS_METHODS:
+        raise NotImplementedError("{} soft nms method not implemented.".format(method))
+    if n == 0:
+        return torch.empty((0,), dtype=torch.int64, device=boxes.device), torch.empty((0,), dtype=torch.float32, device=scores.device)
+    if n > hip.SOFT_NMS_MAX_CANDIDATES:
+        raise ValueError(f"soft_nms: {n} candidates exceed the kernel's limit of {hip.SOFT_NMS_MAX_CANDIDATES}")
+    keep, keep_scores, nkeep = hip.soft_nms(boxes.float().contiguous(), scores.float().contiguous(), idxs.long().contiguous(), method,
+                                            gaussian_sigma, linear_threshold, prune_threshold, max_keep)
+    k = int(nkeep[0])
+    return keep[:k], keep_scores[:k]
+
+
+def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, nms_thresh, topk_per_image, proposal_indices=False, *,
+                                     soft_nms_enabled=False, soft_nms_method="gaussian", soft_nms_sigma=0.5, soft_nms_prune=0.001):
+    """fast_rcnn.py:130-209: drop non-finite rows, clip, score threshold per (proposal, class), per-class NMS, keep the top-k.
+    boxes [R, 4K], scores [R, K+1] -> (Instances, indices of the kept proposals).  As in the reference, those indices count the
+    rows left after the non-finite ones are dropped; ``proposal_indices=True`` maps them back to rows of the input (the proposal
+    each detection came from).  With ``soft_nms_enabled`` (fast_rcnn.py:186-201) the per-class walk is soft-NMS: the kept
+    detections carry the RESCORED scores and the top-k cut follows the pick order; ``nms_thresh`` is the linear / hard threshold."""
     valid = torch.isfinite(boxes).all(dim=1) & torch.isfinite(scores).all(dim=1)
     rows = None
     if not bool(valid.all()):
@@ -124,7 +147,12 @@ def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, n
     inds = mask.nonzero()                            # [R', 2] (proposal, class), row-major order as the reference
     boxes = boxes[inds[:, 0], 0] if k == 1 else boxes[mask]
     scores = scores[mask]
-    keep = batched_nms(boxes, scores, inds[:, 1], nms_thresh)
+    if not soft_nms_enabled:
+        keep = batched_nms(boxes, scores, inds[:, 1], nms_thresh)
+    else:
+        keep, soft_scores = batched_soft_nms(boxes, scores, inds[:, 1], soft_nms_method, soft_nms_sigma, nms_thresh, soft_nms_prune,
+                                             max_keep=topk_per_image if topk_per_image >= 0 else -1)
+        scores[keep] = soft_scores
     if topk_per_image >= 0:
         keep = keep[:topk_per_image]
     res = Instances(tuple(image_shape))
@@ -169,7 +197,13 @@ class FastRCNNOutputLayers(nn.Module):
         self.test_topk_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         self.no_box_delta = bool(c.NO_BOX_DELTA)
         self.multiply_rpn_score = bool(c.MULTIPLY_RPN_SCORE)
-        assert not cfg.MODEL.ROI_HEADS.get("SOFT_NMS_ENABLED", False), "soft-NMS is off the hot path (defaults.py:399)"
+        # soft-NMS at inference (fast_rcnn.py:401-404; defaults.py:399-404)
+        self.soft_nms_enabled = bool(cfg.MODEL.ROI_HEADS.get("SOFT_NMS_ENABLED", False))
+        self.soft_nms_method = cfg.MODEL.ROI_HEADS.get("SOFT_NMS_METHOD", "gaussian")
+        self.soft_nms_sigma = cfg.MODEL.ROI_HEADS.get("SOFT_NMS_SIGMA", 0.5)
+        self.soft_nms_prune = cfg.MODEL.ROI_HEADS.get("SOFT_NMS_PRUNE", 0.001)
+        if self.soft_nms_method not in SOFT_NMS_METHODS:
+            raise NotImplementedError("{} soft nms method not implemented.".format(self.soft_nms_method))
         self.compute_dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "fp8": torch.bfloat16}[cfg.MODEL.get("COMPUTE_DTYPE", "bf16")]
         self.fp8 = cfg.MODEL.get("COMPUTE_DTYPE", "bf16") == "fp8"
         self._wn = None
@@ -253,7 +287,9 @@ class FastRCNNOutputLayers(nn.Module):
         if self.multiply_rpn_score and not self.training:   # geometric mean with the RPN objectness (fast_rcnn.py:708-710)
             scores = [(s * p.objectness_logits[:, None]) ** 0.5 for s, p in zip(scores, proposals)]
         out = [fast_rcnn_inference_single_image(b, s, p.image_size, self.test_score_thresh, self.test_nms_thresh,
-                                                self.test_topk_per_image, proposal_indices) for b, s, p in zip(boxes, scores, proposals)]
+                                                self.test_topk_per_image, proposal_indices, soft_nms_enabled=self.soft_nms_enabled,
+                                                soft_nms_method=self.soft_nms_method, soft_nms_sigma=self.soft_nms_sigma,
+                                                soft_nms_prune=self.soft_nms_prune) for b, s, p in zip(boxes, scores, proposals)]
         return [o[0] for o in out], [o[1] for o in out]
 
     def _log_stats(self, scores, gt_classes):

@@ -184,6 +184,29 @@ int cddmsl_nms(const float* boxes, const unsigned char* valid, unsigned long lon
  * Scratch from the caller: call with temp == NULL to get *temp_bytes.  K <= 12288. */
 int cddmsl_nms_anyorder(const float* boxes, const float* scores, long* keep, int* nkeep, int K, float iou_threshold, void* temp,
                         size_t* temp_bytes, void* stream);
+/* batched_soft_nms + _soft_nms + pairwise_iou (layers/soft_nms.py:85-132,186-261, structures/boxes.py:322-367) as
+ * fast_rcnn_inference_single_image calls them (modeling/roi_heads/fast_rcnn.py:186-194): boxes [K][4] f32 XYXY, scores [K] f32
+ * (finite), idxs [K] int64 categories in ANY order (ids need not be contiguous).  method 0 gaussian (sigma > 0), 1 linear,
+ * 2 hard; iou_threshold is the linear / hard threshold, prune_threshold the strict survival threshold.  max_keep -1: no cap;
+ * >= 0: every category's walk stops after max_keep picks and the output holds at most max_keep entries -- exactly the first
+ * max_keep entries of the uncapped result.
+ * -> keep [K] int64 = input indices in pick order (rescored score descending, equal scores by input index; entries past *nkeep
+ * are -1), keep_scores [K] f32 = the rescored scores (entries past *nkeep are not written), nkeep [1] int (device).
+ * Arithmetic: coordinates are shifted by (float)cls * (max coordinate + 1) in f32 and the IoU is pairwise_iou's form on the
+ * SHIFTED values, every operation one IEEE f32 operation in the reference's order: linear and hard are bit-exact, gaussian up to
+ * expf's 1 ulp.  One workgroup walks one category with its state in LDS (up to 2048 candidates of a category; a larger category
+ * walks in the scratch buffer, same result, slower: ONE workgroup walks it with its state in global memory, unmeasured, and a call
+ * with thousands of picks in such a category can take seconds).  As in the reference's single walk, a candidate whose score starts
+ * at or below prune_threshold is dropped after the first pick of all (the global arg-max) unless it is that pick or shares its
+ * category, where the ordinary decay-and-prune test decides.
+ * Caps: K <= 32768 per call (any split over categories).  K above that, an unknown method, sigma <= 0 with the gaussian method,
+ * or max_keep < -1 return CDDMSL_ERR_ARG with nothing written.  K == 0 writes *nkeep = 0 and nothing else.
+ * Scratch from the caller: call with temp == NULL to get *temp_bytes.  temp == NULL always means "size query": with K == 0 the
+ * query returns 0 bytes and the run still needs a non-NULL temp (any address, never dereferenced) to write *nkeep = 0.
+ * No allocation, no synchronisation, no global state. */
+int cddmsl_soft_nms(const float* boxes, const float* scores, const long* idxs, long* keep, float* keep_scores, int* nkeep, int K,
+                    int method, float sigma, float iou_threshold, float prune_threshold, int max_keep, void* temp,
+                    size_t* temp_bytes, void* stream);
 int cddmsl_iou_match(const float* gt, int G, const float* preds, int P, long* matches, signed char* labels,
                      unsigned int* best_ws, int nthr, float t0, float t1, int l0, int l1, int l2, int allow_low_quality,
                      void* stream);
