@@ -176,7 +176,28 @@ def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False):
     res = inference_on_dataset(model, loader, ev)
     if rank == 0:
         print({k: round(v, 4) for k, v in res["bbox"].items()})
+    if tta_enabled(cfg):            # train_caption_consistency.py:105-118,149-150: the same set again through the TTA model
+        loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
+        tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, ev))
+        if rank == 0:
+            print({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()})
+            res.update(tta)
     return res if return_results else 0
+
+
+def tta_enabled(cfg):
+    return bool(cfg.TEST.get("AUG", {}).get("ENABLED", False))
+
+
+def tta_model(cfg, model):
+    """``GeneralizedRCNNWithTTA(cfg, model)`` (looked up at call time: with ``TEST.AUG.ENABLED`` off it is never constructed)"""
+    from .modeling import test_time_augmentation
+    return test_time_augmentation.GeneralizedRCNNWithTTA(cfg, model)
+
+
+def with_tta_suffix(res):
+    """train_caption_consistency.py:117: ``{k + "_TTA": v}`` over the top-level keys (``bbox_TTA``); None (not rank 0) stays empty"""
+    return OrderedDict((k + "_TTA", v) for k, v in (res or {}).items())
 
 
 # ------------------------------------------------------------------------------------------------ COCO-style box AP
@@ -368,4 +389,10 @@ def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_res
         if rank == 0:
             print(f"{name}: " + str({k: round(v, 4) for k, v in res["bbox"].items()}), flush=True)
             results[name] = res
+        if tta_enabled(cfg):
+            loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
+            tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, COCODetectionEvaluator(dicts, cityscapes.THING_CLASSES)))
+            if rank == 0:
+                print(f"{name}: " + str({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()}), flush=True)
+                results[name].update(tta)
     return results if return_results else 0

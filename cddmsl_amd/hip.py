@@ -38,6 +38,7 @@ def _L():
         L.cddmsl_preprocess224.argtypes = [vp, vp] + [ci] * 11 + [vp, vp, ci, vp]
         L.cddmsl_preprocess_batch.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, vp]
         L.cddmsl_preprocess224_batch.argtypes = [vp, vp, vp, ci, vp] + [ci] * 8 + [vp, vp, ci, vp]
+        L.cddmsl_tta_view.argtypes = [vp] + [ci] * 4 + [vp, vp, vp, ci] * 2 + [vp, ci, ci, ci] * 2 + [ci, vp, vp, ci, ci, vp]
         L.cddmsl_avgpool2_fwd.argtypes = [vp, vp] + [ci] * 5 + [vp]
         L.cddmsl_avgpool2_bwd.argtypes = [vp] * 4 + [ci] * 5 + [vp]
         L.cddmsl_avgpool2_bwd_q8.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 4
@@ -590,6 +591,103 @@ def preprocess224(images_u8, Hp, Wp, mean, std, dtype, size=224, Cp=None):
     check(_L().cddmsl_preprocess224_batch(ptrs, hs, ws, len(images_u8), ptr(out), Hp, Wp, RH, RW, top, left, size, Cp,
                                            m, s, DT[dtype], stream_ptr()), "cddmsl_preprocess224_batch")
     return out
+
+
+_RESAMPLE_BITS = 22          # Pillow's PRECISION_BITS (ImagingResample, 8 bits per channel)
+_resample_cache = {}
+
+
+def _resample_table(insize, outsize):
+    """Pillow's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for the bilinear filter along one axis -> (lo [out], n [out],
+    k [out, ksize], ksize), int32: output i reads inputs lo[i] .. lo[i] + n[i] - 1 with the weights k[i, :n[i]] (the rest 0).  Computed in
+    double in Pillow's own order of operations -- window from the centre, triangle weight of ``(x + lo - centre + 0.5) * (1 / fs)``, a
+    running sum in tap order, one division per tap, ``int(0.5 + w * 2^22)`` -- because another order moves a coefficient by one and
+    with it pixels.  The kernel only reads these tables."""
+    import math
+
+    import numpy as np
+    key = (int(insize), int(outsize))
+    if key in _resample_cache:
+        return _resample_cache[key]
+    scale = key[0] / key[1]
+    fs = max(scale, 1.0)
+    support = 1.0 * fs                                   # the bilinear filter's support is 1
+    ks = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    center = (np.arange(key[1], dtype=np.float64) + 0.5) * scale
+    lo = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    hi = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), key[0])
+    n = hi - lo
+    k = np.zeros((key[1], ks), dtype=np.float64)
+    ww = np.zeros(key[1], dtype=np.float64)
+    for t in range(ks):
+        a = np.abs(((t + lo) - center + 0.5) * ss)
+        k[:, t] = np.where((a < 1.0) & (t < n), 1.0 - a, 0.0)
+        ww = ww + k[:, t]
+    nz = ww != 0.0
+    k[nz] = k[nz] / ww[nz, None]
+    ki = np.trunc(0.5 + k * float(1 << _RESAMPLE_BITS)).astype(np.int32)       # bilinear weights are never negative
+    if len(_resample_cache) >= 256:
+        _resample_cache.clear()
+    _resample_cache[key] = (lo.astype(np.int32), n.astype(np.int32), ki, ks)
+    return _resample_cache[key]
+
+
+def tta_view_list(sizes, flip):
+    """the reference's view order (test_time_augmentation.py:79-86): [s0, s0 mirrored, s1, s1 mirrored, ...] -> [(newh, neww, flipped)]"""
+    return [(int(nh), int(nw), f) for nh, nw in sizes for f in ((False, True) if flip else (False,))]
+
+
+@_timed("tta_views")
+def tta_views(image_u8, sizes, flip, mean, std, dtype, batch_size=3, div255=True):
+    """Test-time-augmentation views of ONE u8 CHW device image, made on the device: for every (newh, neww) of ``sizes`` the PIL
+    bilinear resize (bit-equal to ``Image.resize((neww, newh), BILINEAR)``), with ``flip`` also its left-right mirror, normalised
+    and zero-padded like ``preprocess``.  Returns the reference's batches (test_time_augmentation.py:162-186): a list of groups
+    ``(NHWC tensor [g, Hp, Wp, Cp], [(newh, neww), ...])`` of ``batch_size`` views in the order [s0, s0 mirrored, s1, ...] (the last
+    group may be short), each padded to its own largest view.  One launch per size writes the view and its mirror, each into its
+    own group's slot; a size equal to the image's makes the plain view a copy."""
+    import numpy as np
+    require_cuda(image_u8)
+    assert image_u8.dtype == torch.uint8 and image_u8.dim() == 3 and image_u8.shape[0] == 3 and image_u8.is_contiguous()
+    assert batch_size >= 1
+    h, w = int(image_u8.shape[1]), int(image_u8.shape[2])
+    Cp = 8 if dtype == torch.bfloat16 else 4
+    sizes = [(int(a), int(b)) for a, b in sizes]
+    views = tta_view_list(sizes, flip)
+    groups = []
+    for g0 in range(0, len(views), batch_size):
+        vs = views[g0:g0 + batch_size]
+        Hp, Wp = max(v[0] for v in vs), max(v[1] for v in vs)
+        groups.append((torch.empty((len(vs), Hp, Wp, Cp), device=image_u8.device, dtype=dtype), [(v[0], v[1]) for v in vs]))
+    # every table of the call in ONE int32 upload
+    parts, where, off = [], {}, 0
+    for insize, outsize in sorted({(w, nw) for _, nw in sizes if nw != w} | {(h, nh) for nh, _ in sizes if nh != h}):
+        lo, n, k, ks = _resample_table(insize, outsize)
+        where[(insize, outsize)] = (off, off + outsize, off + 2 * outsize, ks)
+        parts += [lo, n, k.reshape(-1)]
+        off += 2 * outsize + outsize * ks
+    tab = None
+    if parts:
+        from ._lib import to_device_async
+        tab = to_device_async(torch.from_numpy(np.concatenate(parts)), image_u8.device)
+
+    def axis(insize, outsize):
+        if insize == outsize:
+            return c_void_p(0), c_void_p(0), c_void_p(0), 0
+        a, b, c, ks = where[(insize, outsize)]
+        base = tab.data_ptr()
+        return c_void_p(base + 4 * a), c_void_p(base + 4 * b), c_void_p(base + 4 * c), ks
+
+    m, s = _f3(mean), _f3(std)
+    per = 2 if flip else 1
+    for i, (nh, nw) in enumerate(sizes):
+        v0 = i * per
+        t0, t1 = groups[v0 // batch_size][0], (groups[(v0 + 1) // batch_size][0] if flip else None)
+        check(_L().cddmsl_tta_view(ptr(image_u8), h, w, nh, nw, *axis(w, nw), *axis(h, nh),
+                                   ptr(t0), v0 % batch_size, t0.shape[1], t0.shape[2],
+                                   ptr(t1), (v0 + 1) % batch_size if flip else 0, t1.shape[1] if flip else 0, t1.shape[2] if flip else 0,
+                                   Cp, m, s, int(div255), DT[dtype], stream_ptr()), "cddmsl_tta_view")
+    return groups
 
 
 @_timed("avgpool2_fwd")

@@ -4,3 +4,4 @@ from .rpn import RPN, StandardRPNHead, DefaultAnchorGenerator, build_proposal_ge
 from .resnet import build_resnet_backbone, ResNet, BasicStem, BottleneckBlock  # noqa
 from .roi_heads import Res5ROIHeads, CLIPRes5ROIHeads, FastRCNNOutputLayers, ROIPooler, build_roi_heads  # noqa
 from .rcnn import GeneralizedRCNN, GatherLayer, build_model  # noqa
+from .test_time_augmentation import DatasetMapperTTA, GeneralizedRCNNWithTTA  # noqa

@@ -223,6 +223,15 @@ class GeneralizedRCNN(nn.Module):
     def inference(self, batched_inputs: List[Dict], detected_instances=None, do_postprocess: bool = True):
         assert not self.training
         images, sizes = self.preprocess_image(batched_inputs, "image")
+        results = self._inference_preprocessed(images, sizes, detected_instances)
+        return self._postprocess(results, batched_inputs, sizes) if do_postprocess else results
+
+    @torch.no_grad()
+    def _inference_preprocessed(self, images, sizes, detected_instances=None):
+        """``inference`` behind ``preprocess_image``: images = the normalised, zero-padded NHWC batch in the compute dtype, sizes = each
+        image's (h, w) inside it -> per-image Instances in the coordinates of those sizes (no postprocess).  The entry of callers that
+        make the batch tensor themselves (test-time augmentation builds its views on the device)."""
+        assert not self.training
         res4 = self.backbone.forward_nhwc(images, want_res5=False)["res4"]
         feats = {"res4": to_nchw(res4)}
         if detected_instances is None:
@@ -231,7 +240,7 @@ class GeneralizedRCNN(nn.Module):
             results, _ = self.roi_heads(ImageList(None, sizes), feats, proposals, None, **kw)
         else:
             results = self.roi_heads.forward_with_given_boxes(feats, [x.to(self.device) for x in detected_instances])
-        return self._postprocess(results, batched_inputs, sizes) if do_postprocess else results
+        return results
 
     @torch.no_grad()
     def inference_with_region_embeddings(self, batched_inputs: List[Dict]):

@@ -380,6 +380,16 @@ int cddmsl_preprocess_batch(const unsigned char* const* imgs, const int* hs, con
                             const float* mean3, const float* std3, int div255, int dtype, void* stream);
 int cddmsl_preprocess224_batch(const unsigned char* const* imgs, const int* hs, const int* ws, int N, void* out, int Hp, int Wp, int RH,
                                int RW, int top, int left, int S, int Cp, const float* mean3, const float* std3, int dtype, void* stream);
+/* test-time-augmentation views (modeling/test_time_augmentation.py:58-98) made on the device (tta_views.hip): img u8 [3][h][w] ->
+ * Pillow's bilinear resize to (newh, neww), bit for bit (two separable passes, 22-bit fixed-point coefficients, uint8 between the
+ * passes, a pass whose size does not change skipped) -> the normalisation of cddmsl_preprocess -> slot n0 of out0 [N][Hp0][Wp0][Cp],
+ * and, with out1 != NULL, the left-right mirror of the view -> slot n1 of out1 [N][Hp1][Wp1][Cp].  Padding and channels 3..Cp are
+ * zeroed; other slots are not touched.  xlo / xn [neww], xk [neww][xks] (horizontal pass) and ylo / yn [newh], yk [newh][yks]
+ * (vertical pass) are DEVICE int32 tables: window start, window length, coefficients int(0.5 + w * 2^22), computed on the host in
+ * double in Pillow's order (cddmsl_amd/hip.py); NULL is allowed for a pass that is skipped (neww == w / newh == h). */
+int cddmsl_tta_view(const unsigned char* img, int h, int w, int newh, int neww, const int* xlo, const int* xn, const int* xk, int xks,
+                    const int* ylo, const int* yn, const int* yk, int yks, void* out0, int n0, int Hp0, int Wp0, void* out1, int n1,
+                    int Hp1, int Wp1, int Cp, const float* mean3, const float* std3, int div255, int dtype, void* stream);
 int cddmsl_avgpool2_fwd(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
 int cddmsl_avgpool2_bwd(const void* dy, const void* mask, const void* add, void* dx, int N, int H, int W, int C, int dtype,
                         void* stream);
