@@ -560,3 +560,189 @@ extern "C" int cddmsl_box_l1(const float* deltas, int ld, const long* fg, int nf
                      gout1, ddeltas);
   return launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The same two losses with the reference's other box-regression terms (box_regression.py:229-270, fast_rcnn.py:646-689):
+//   loc_type 0  smooth-L1 with beta (fvcore smooth_l1_loss): n = |delta - target|; beta < 1e-5: n (the kernels above); else
+//               n < beta ? 0.5 n n / beta : n - 0.5 beta, gradient n < beta ? e / beta : sgn(e)
+//   loc_type 1  GIoU (fvcore giou_loss, eps 1e-7) of Box2BoxTransform.apply_deltas(delta, anchor / proposal) against the gt box
+// f32, one IEEE operation at a time in the reference's order; one block, fixed-order sum.  The GIoU backward is the analytic gradient
+// of that chain with torch autograd's conventions: max / min of equal operands hands each HALF the gradient, the clamp passes it at
+// dw == scale_clamp and blocks it above, a row whose intersection test fails has no gradient through the intersection.
+namespace {
+constexpr float GIOU_EPS = 1e-7f;
+
+__device__ __forceinline__ float sl1_term(float e, float beta) {
+  const float n = fabsf(e);
+  if (beta < 1e-5f) return n;
+  return n < beta ? 0.5f * n * n / beta : n - 0.5f * beta;
+}
+__device__ __forceinline__ float sl1_grad(float e, float beta) {
+  if (beta < 1e-5f) return sgn(e);
+  return fabsf(e) < beta ? e / beta : sgn(e);
+}
+// torch.max / torch.min of two tensors: a NaN operand gives NaN (fmaxf / fminf would drop it)
+__device__ __forceinline__ float tmax(float p, float g) { return (p != p || g != g) ? p + g : (p > g ? p : g); }
+__device__ __forceinline__ float tmin(float p, float g) { return (p != p || g != g) ? p + g : (p < g ? p : g); }
+// share of the gradient that max(p, g) (HI) or min(p, g) (!HI) hands to p
+template <bool HI> __device__ __forceinline__ float share(float p, float g) {
+  return p == g ? 0.5f : ((HI ? p > g : p < g) ? 1.f : 0.f);
+}
+
+// b: anchor / proposal, d: the row's four deltas, t: gt box.  Returns the loss term; with gd, also d term / d delta (unscaled).
+__device__ __forceinline__ float giou_row(const float* b, const float* d, const float* t, BoxW w, float clampv, float* gd) {
+  const float bw = b[2] - b[0], bh = b[3] - b[1];
+  const float cx = b[0] + 0.5f * bw, cy = b[1] + 0.5f * bh;
+  const float dx = d[0] / w.wx, dy = d[1] / w.wy, dw0 = d[2] / w.ww, dh0 = d[3] / w.wh;
+  const float dw = dw0 > clampv ? clampv : dw0, dh = dh0 > clampv ? clampv : dh0;     // torch.clamp(max=): a NaN stays NaN
+  const float pcx = dx * bw + cx, pcy = dy * bh + cy;
+  const float pw = expf(dw) * bw, ph = expf(dh) * bh;
+  const float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
+  const float x1g = t[0], y1g = t[1], x2g = t[2], y2g = t[3];
+  const float xk1 = tmax(x1, x1g), yk1 = tmax(y1, y1g), xk2 = tmin(x2, x2g), yk2 = tmin(y2, y2g);
+  const bool hit = yk2 > yk1 && xk2 > xk1;
+  const float iw = xk2 - xk1, ih = yk2 - yk1;
+  const float inter = hit ? iw * ih : 0.f;
+  const float sw = x2 - x1, sh = y2 - y1;
+  const float uni = sw * sh + (x2g - x1g) * (y2g - y1g) - inter;
+  const float ue = uni + GIOU_EPS;
+  const float iou = inter / ue;
+  const float xc1 = tmin(x1, x1g), yc1 = tmin(y1, y1g), xc2 = tmax(x2, x2g), yc2 = tmax(y2, y2g);
+  const float cw = xc2 - xc1, ch = yc2 - yc1;
+  const float ac = cw * ch;
+  const float ce = ac + GIOU_EPS;
+  const float loss = 1.f - (iou - (ac - uni) / ce);
+  if (gd) {
+    // loss = 1 - inter / ue + (ac - uni) / ce:  d/d uni = inter / ue^2 - 1 / ce,  d/d inter (direct) = -1 / ue,
+    // d/d ac = 1 / ce - (ac - uni) / ce^2 = ue / ce^2  (ce - (ac - uni) = ue: the form without the cancellation)
+    const float g_u = inter / (ue * ue) - 1.f / ce;
+    const float g_i = hit ? -1.f / ue - g_u : 0.f;               // uni = a1 + a2 - inter
+    const float g_c = ue / (ce * ce);
+    const float kx1 = share<true>(x1, x1g), ky1 = share<true>(y1, y1g), kx2 = share<false>(x2, x2g), ky2 = share<false>(y2, y2g);
+    const float ex1 = share<false>(x1, x1g), ey1 = share<false>(y1, y1g), ex2 = share<true>(x2, x2g), ey2 = share<true>(y2, y2g);
+    const float gx1 = -(g_u * sh) - (g_i * ih) * kx1 - (g_c * ch) * ex1;
+    const float gx2 = (g_u * sh) + (g_i * ih) * kx2 + (g_c * ch) * ex2;
+    const float gy1 = -(g_u * sw) - (g_i * iw) * ky1 - (g_c * cw) * ey1;
+    const float gy2 = (g_u * sw) + (g_i * iw) * ky2 + (g_c * cw) * ey2;
+    gd[0] = (gx1 + gx2) * bw / w.wx;
+    gd[1] = (gy1 + gy2) * bh / w.wy;
+    gd[2] = dw0 <= clampv ? 0.5f * (gx2 - gx1) * pw / w.ww : 0.f;
+    gd[3] = dh0 <= clampv ? 0.5f * (gy2 - gy1) * ph / w.wh : 0.f;
+  }
+  return loss;
+}
+
+template <int LOC>
+__global__ __launch_bounds__(256) void k_rpn_losses_reg(const float* logits, const float* deltas, const long* pos, int npos, const long* neg, int nneg,
+                                                         const long* midx, const float* gt, const long* gt_off, const float* anchors, long A, BoxW w,
+                                                         float inv_norm, float beta, float clampv, float* out2, const float* gout2, float* dlogits,
+                                                         float* ddeltas) {
+  __shared__ float red[4];
+  const bool bwd = gout2 != nullptr;
+  const float gc = bwd ? gout2[0] * inv_norm : 0.f, gl = bwd ? gout2[1] * inv_norm : 0.f;
+  float cls = 0.f, loc = 0.f;
+  for (int i = threadIdx.x; i < npos + nneg; i += blockDim.x) {
+    const bool is_pos = i < npos;
+    const long r = is_pos ? pos[i] : neg[i - npos];
+    const float x = logits[r], y = is_pos ? 1.f : 0.f;
+    if (!bwd) cls += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));          // binary_cross_entropy_with_logits
+    else dlogits[r] = (1.f / (1.f + expf(-x)) - y) * gc;
+    if (is_pos) {
+      const long img = r / A, a = r - img * A;
+      const float* tb = gt + 4 * (midx[r] + gt_off[img]);
+      if (LOC == 0) {
+        float d[4];
+        get_deltas4(anchors + 4 * a, tb, w, d);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float e = deltas[4 * r + c] - d[c];
+          if (!bwd) loc += sl1_term(e, beta); else ddeltas[4 * r + c] = sl1_grad(e, beta) * gl;
+        }
+      } else {
+        float gd[4];
+        const float t = giou_row(anchors + 4 * a, deltas + 4 * r, tb, w, clampv, bwd ? gd : nullptr);
+        if (!bwd) loc += t;
+        else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) ddeltas[4 * r + c] = gd[c] * gl;
+        }
+      }
+    }
+  }
+  if (!bwd) {
+    cls = block_sum(cls, red);
+    loc = block_sum(loc, red);
+    if (threadIdx.x == 0) { out2[0] = cls * inv_norm; out2[1] = loc * inv_norm; }
+  }
+}
+
+template <int LOC>
+__global__ __launch_bounds__(256) void k_box_reg_loss(const float* deltas, int ld, const long* fg, int nfg, const long* cls, const float* src,
+                                                       const float* tgt, BoxW w, float inv_norm, float beta, float clampv, float* out1,
+                                                       const float* gout1, float* ddeltas) {
+  __shared__ float red[4];
+  const bool bwd = gout1 != nullptr;
+  const float g = bwd ? gout1[0] * inv_norm : 0.f;
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nfg; i += blockDim.x) {
+    const long r = fg[i], c0 = cls ? 4 * cls[r] : 0;
+    if (LOC == 0) {
+      float d[4];
+      get_deltas4(src + 4 * r, tgt + 4 * r, w, d);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float e = deltas[r * ld + c0 + c] - d[c];
+        if (!bwd) acc += sl1_term(e, beta); else ddeltas[r * ld + c0 + c] = sl1_grad(e, beta) * g;
+      }
+    } else {
+      float gd[4];
+      const float t = giou_row(src + 4 * r, deltas + r * ld + c0, tgt + 4 * r, w, clampv, bwd ? gd : nullptr);
+      if (!bwd) acc += t;
+      else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) ddeltas[r * ld + c0 + c] = gd[c] * g;
+      }
+    }
+  }
+  if (!bwd) {
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) out1[0] = acc * inv_norm;
+  }
+}
+
+__host__ inline bool reg_args_ok(int loc_type, float beta, float scale_clamp) {
+  if (loc_type != 0 && loc_type != 1) return false;
+  if (!(beta >= 0.f)) return false;                                  // negative or NaN
+  return loc_type == 0 || std::isfinite(scale_clamp);
+}
+}  // namespace
+
+// cddmsl_rpn_losses with the box-regression term chosen by loc_type (0 smooth-L1 with beta, 1 GIoU; beta ignored for GIoU).
+// loc_type 0, beta 0 returns the bytes of cddmsl_rpn_losses.
+extern "C" int cddmsl_rpn_losses_reg(const float* logits, const float* deltas, const long* pos, int npos, const long* neg, int nneg, const long* midx,
+                                     const float* gt, const long* gt_off, const float* anchors, long A, float wx, float wy, float ww, float wh,
+                                     float inv_norm, int loc_type, float beta, float scale_clamp, float* out2, const float* gout2, float* dlogits,
+                                     float* ddeltas, void* stream) {
+  if (npos < 0 || nneg < 0 || A <= 0 || (gout2 ? (!dlogits || !ddeltas) : !out2) || !reg_args_ok(loc_type, beta, scale_clamp)) return CDDMSL_ERR_ARG;
+  if (loc_type == 0)
+    hipLaunchKernelGGL(k_rpn_losses_reg<0>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, deltas, pos, npos, neg, nneg, midx, gt, gt_off, anchors,
+                       A, BoxW{wx, wy, ww, wh}, inv_norm, beta, scale_clamp, out2, gout2, dlogits, ddeltas);
+  else
+    hipLaunchKernelGGL(k_rpn_losses_reg<1>, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, deltas, pos, npos, neg, nneg, midx, gt, gt_off, anchors,
+                       A, BoxW{wx, wy, ww, wh}, inv_norm, beta, scale_clamp, out2, gout2, dlogits, ddeltas);
+  return launch_status();
+}
+
+// cddmsl_box_l1 with the term chosen by loc_type; GIoU decodes the row's class-specific four deltas on src and compares with tgt.
+extern "C" int cddmsl_box_reg_loss(const float* deltas, int ld, const long* fg, int nfg, const long* cls, const float* src, const float* tgt, float wx,
+                                   float wy, float ww, float wh, float inv_norm, int loc_type, float beta, float scale_clamp, float* out1,
+                                   const float* gout1, float* ddeltas, void* stream) {
+  if (nfg < 0 || ld < 4 || (gout1 ? !ddeltas : !out1) || !reg_args_ok(loc_type, beta, scale_clamp)) return CDDMSL_ERR_ARG;
+  if (loc_type == 0)
+    hipLaunchKernelGGL(k_box_reg_loss<0>, dim3(1), dim3(256), 0, (hipStream_t)stream, deltas, ld, fg, nfg, cls, src, tgt, BoxW{wx, wy, ww, wh},
+                       inv_norm, beta, scale_clamp, out1, gout1, ddeltas);
+  else
+    hipLaunchKernelGGL(k_box_reg_loss<1>, dim3(1), dim3(256), 0, (hipStream_t)stream, deltas, ld, fg, nfg, cls, src, tgt, BoxW{wx, wy, ww, wh},
+                       inv_norm, beta, scale_clamp, out1, gout1, ddeltas);
+  return launch_status();
+}

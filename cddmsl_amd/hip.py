@@ -89,6 +89,8 @@ def _L():
         L.cddmsl_attnpool_dx.argtypes = [vp] * 6 + [ci] * 6 + [vp]
         L.cddmsl_rpn_losses.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, c_long, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]
         L.cddmsl_box_l1.argtypes = [vp, ci, vp, ci, vp, vp, vp, cf, cf, cf, cf, cf, vp, vp, vp, vp]
+        L.cddmsl_rpn_losses_reg.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, c_long, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp, vp, vp, vp]
+        L.cddmsl_box_reg_loss.argtypes = [vp, ci, vp, ci, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp, vp, vp]
         L.cddmsl_attn_last_fwd.argtypes = [vp] * 4 + [ci] * 8 + [cf, ci, vp]
         L.cddmsl_attn_last_bwd.argtypes = [vp] * 6 + [ci] * 8 + [cf, ci, vp]
         L.cddmsl_contrastive_fwd.argtypes = [vp] * 4 + [ci, ci, vp]
@@ -801,6 +803,48 @@ def box_l1(deltas, fg, cls, src, tgt, weights, inv_norm, gout=None):
     dd = torch.zeros_like(deltas)
     g = gout.contiguous().float().view(1)
     check(_L().cddmsl_box_l1(*args, None, ptr(g), ptr(dd), stream_ptr()), "cddmsl_box_l1(backward)")
+    return dd
+
+
+LOC_TYPES = {"smooth_l1": 0, "giou": 1}
+
+
+def rpn_losses_reg(logits, deltas, pos, neg, midx, gt, gt_off, anchors, weights, inv_norm, loc_type, beta, scale_clamp, gout=None):
+    """``rpn_losses`` with the box-regression term of ``loc_type`` ("smooth_l1" with ``beta``, or "giou" of the decoded anchors,
+    dw / dh clamped at ``scale_clamp``): cddmsl_rpn_losses_reg"""
+    require_cuda(logits, deltas, pos, neg, midx, gt, gt_off, anchors)
+    for t in (logits, deltas, gt, anchors):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    for t in (pos, neg, midx, gt_off):
+        assert t.dtype == torch.int64 and t.is_contiguous()
+    A = anchors.shape[0]
+    assert deltas.numel() == 4 * logits.numel() and midx.numel() == logits.numel()
+    args = (ptr(logits), ptr(deltas), ptr(pos), pos.numel(), ptr(neg), neg.numel(), ptr(midx), ptr(gt), ptr(gt_off), ptr(anchors), A,
+            *[float(w) for w in weights], float(inv_norm), LOC_TYPES[loc_type], float(beta), float(scale_clamp))
+    if gout is None:
+        out = torch.empty(2, device=logits.device, dtype=torch.float32)
+        check(_L().cddmsl_rpn_losses_reg(*args, ptr(out), None, None, None, stream_ptr()), "cddmsl_rpn_losses_reg")
+        return out
+    dl, dd = torch.zeros_like(logits), torch.zeros_like(deltas)
+    g = gout.contiguous().float()
+    check(_L().cddmsl_rpn_losses_reg(*args, None, ptr(g), ptr(dl), ptr(dd), stream_ptr()), "cddmsl_rpn_losses_reg(backward)")
+    return dl, dd
+
+
+def box_reg_loss(deltas, fg, cls, src, tgt, weights, inv_norm, loc_type, beta, scale_clamp, gout=None):
+    """``box_l1`` with the term of ``loc_type`` ("smooth_l1" with ``beta``, or "giou" of the decoded proposals): cddmsl_box_reg_loss"""
+    require_cuda(deltas, fg, src, tgt)
+    assert deltas.dtype == torch.float32 and deltas.dim() == 2 and deltas.is_contiguous() and fg.dtype == torch.int64 and fg.is_contiguous()
+    assert src.dtype == tgt.dtype == torch.float32 and src.is_contiguous() and tgt.is_contiguous() and (cls is None or (cls.dtype == torch.int64 and cls.is_contiguous()))
+    args = (ptr(deltas), deltas.shape[1], ptr(fg), fg.numel(), ptr(cls), ptr(src), ptr(tgt), *[float(w) for w in weights], float(inv_norm),
+            LOC_TYPES[loc_type], float(beta), float(scale_clamp))
+    if gout is None:
+        out = torch.empty(1, device=deltas.device, dtype=torch.float32)
+        check(_L().cddmsl_box_reg_loss(*args, ptr(out), None, None, stream_ptr()), "cddmsl_box_reg_loss")
+        return out
+    dd = torch.zeros_like(deltas)
+    g = gout.contiguous().float().view(1)
+    check(_L().cddmsl_box_reg_loss(*args, None, ptr(g), ptr(dd), stream_ptr()), "cddmsl_box_reg_loss(backward)")
     return dd
 
 

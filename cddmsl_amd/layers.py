@@ -1359,6 +1359,47 @@ def box_l1(deltas, fg, cls, src, tgt, weights, inv_norm):
     return BoxL1Fn.apply(deltas, fg, cls, src.contiguous(), tgt.contiguous(), tuple(weights), float(inv_norm))
 
 
+class RpnLossesRegFn(torch.autograd.Function):
+    """RpnLossesFn with the reference's other box-regression terms (smooth-L1 with beta > 0, GIoU): cddmsl_rpn_losses_reg"""
+
+    @staticmethod
+    def forward(ctx, logits, deltas, pos, neg, midx, gt, gt_off, anchors, weights, inv_norm, loc_type, beta, scale_clamp):
+        logits, deltas = logits.contiguous(), deltas.contiguous()
+        ctx.save_for_backward(logits, deltas, pos, neg, midx, gt, gt_off, anchors)
+        ctx.cfg = (weights, inv_norm, loc_type, beta, scale_clamp)
+        return hip.rpn_losses_reg(logits, deltas, pos, neg, midx, gt, gt_off, anchors, *ctx.cfg)
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, dd = hip.rpn_losses_reg(*ctx.saved_tensors, *ctx.cfg, gout=g)
+        return (dl, dd) + (None,) * 11
+
+
+def rpn_losses_reg(logits, deltas, pos, neg, midx, gt, gt_off, anchors, weights, inv_norm, loc_type, beta, scale_clamp):
+    return RpnLossesRegFn.apply(logits, deltas, pos, neg, midx, gt, gt_off, anchors, tuple(weights), float(inv_norm), loc_type, float(beta),
+                                float(scale_clamp))
+
+
+class BoxRegLossFn(torch.autograd.Function):
+    """BoxL1Fn with the reference's other box-regression terms (smooth-L1 with beta > 0, GIoU): cddmsl_box_reg_loss"""
+
+    @staticmethod
+    def forward(ctx, deltas, fg, cls, src, tgt, weights, inv_norm, loc_type, beta, scale_clamp):
+        deltas = deltas.contiguous()
+        ctx.save_for_backward(deltas, fg, cls, src, tgt)
+        ctx.cfg = (weights, inv_norm, loc_type, beta, scale_clamp)
+        return hip.box_reg_loss(deltas, fg, cls, src, tgt, *ctx.cfg).view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return (hip.box_reg_loss(*ctx.saved_tensors, *ctx.cfg, gout=g),) + (None,) * 9
+
+
+def box_reg_loss(deltas, fg, cls, src, tgt, weights, inv_norm, loc_type, beta, scale_clamp):
+    return BoxRegLossFn.apply(deltas, fg, cls, src.contiguous(), tgt.contiguous(), tuple(weights), float(inv_norm), loc_type, float(beta),
+                              float(scale_clamp))
+
+
 class MeanPoolFn(torch.autograd.Function):
     """box_features.mean(dim=[2, 3]) of Res5ROIHeads (roi_heads.py:487): [K,h,w,C] T -> [K,C] f32"""
 

@@ -18,7 +18,7 @@ from .._lib import to_device_async
 from ..registry import ROI_HEADS_REGISTRY
 from ..structures import Boxes, Instances, ShapeSpec, as_instances
 from .backbone import to_nhwc, to_nchw
-from .rpn import apply_deltas, get_deltas, subsample_begin, subsample_finish, subsample_labels_batched
+from .rpn import SCALE_CLAMP, apply_deltas, box_reg_loss_terms, get_deltas, subsample_begin, subsample_finish, subsample_labels_batched
 
 GT_LOGIT = math.log((1.0 - 1e-10) / (1 - (1.0 - 1e-10)))  # proposal_utils.py:183
 
@@ -187,7 +187,12 @@ class FastRCNNOutputLayers(nn.Module):
         self.bbox_pred = _Linear(d, self.num_classes * 4)
         nn.init.normal_(self.bbox_pred.weight, std=0.001)
         self.box_weights = tuple(cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS)
-        assert cfg.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA == 0.0 and not cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG
+        assert not cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG, "MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG is not supported"
+        self.box_reg_loss_type = cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE
+        self.smooth_l1_beta = float(cfg.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA)
+        if self.box_reg_loss_type not in ("smooth_l1", "giou"):
+            raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}'")                  # fast_rcnn.py:677
+        assert self.smooth_l1_beta >= 0.0, "MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA must not be negative"
         self.bg_cls_loss_weight = c.BG_CLS_LOSS_WEIGHT
         self.focal_scaled_loss = c.FOCAL_SCALED_LOSS
         self.loss_weight = {"loss_box_reg": cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT}
@@ -256,11 +261,15 @@ class FastRCNNOutputLayers(nn.Module):
             fg = torch.nonzero((gt_classes >= 0) & (gt_classes < self.num_classes), as_tuple=True)[0]
         if deltas.is_cuda and deltas.dtype == torch.float32 and deltas.shape[1] == 4 * self.num_classes:
             # one kernel per direction over the foreground index list (class-specific columns picked inside)
-            loss_box = layers.box_l1(deltas, fg, gt_classes, pboxes.float(), gboxes.float(), self.box_weights, 1.0 / max(gt_classes.numel(), 1.0))
+            args = (deltas, fg, gt_classes, pboxes.float(), gboxes.float(), self.box_weights, 1.0 / max(gt_classes.numel(), 1.0))
+            if self.box_reg_loss_type == "smooth_l1" and self.smooth_l1_beta == 0.0:
+                loss_box = layers.box_l1(*args)
+            else:
+                loss_box = layers.box_reg_loss(*args, self.box_reg_loss_type, self.smooth_l1_beta, SCALE_CLAMP)
         else:
             fg_pred = deltas.view(-1, self.num_classes, 4)[fg, gt_classes[fg]]
-            gt_d = get_deltas(pboxes[fg], gboxes[fg], self.box_weights)
-            loss_box = torch.abs(fg_pred - gt_d).sum() / max(gt_classes.numel(), 1.0)
+            loss_box = box_reg_loss_terms(fg_pred, pboxes[fg], gboxes[fg], self.box_weights, self.box_reg_loss_type,
+                                          self.smooth_l1_beta) / max(gt_classes.numel(), 1.0)
         out = {"loss_cls": loss_cls, "loss_box_reg": loss_box}
         return {k: v * self.loss_weight.get(k, 1.0) for k, v in out.items()}
 

@@ -50,6 +50,37 @@ def apply_deltas(deltas, boxes, weights, scale_clamp=SCALE_CLAMP):
     return out.reshape(deltas.shape)
 
 
+def smooth_l1_loss(inp, tgt, beta):
+    """fvcore.nn.smooth_l1_loss, reduction "sum": |x| below beta 1e-5, else 0.5 x^2 / beta under beta and |x| - 0.5 beta above"""
+    n = torch.abs(inp - tgt)
+    if beta < 1e-5:
+        return n.sum()
+    return torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta).sum()
+
+
+def giou_loss(boxes1, boxes2, eps=1e-7):
+    """fvcore.nn.giou_loss, reduction "sum" (Generalized IoU, arXiv:1902.09630): boxes [n, 4] XYXY"""
+    x1, y1, x2, y2 = boxes1.unbind(dim=-1)
+    x1g, y1g, x2g, y2g = boxes2.unbind(dim=-1)
+    xk1, yk1, xk2, yk2 = torch.max(x1, x1g), torch.max(y1, y1g), torch.min(x2, x2g), torch.min(y2, y2g)
+    hit = (yk2 > yk1) & (xk2 > xk1)
+    inter = torch.where(hit, (xk2 - xk1) * (yk2 - yk1), torch.zeros_like(x1))
+    union = (x2 - x1) * (y2 - y1) + (x2g - x1g) * (y2g - y1g) - inter
+    iou = inter / (union + eps)
+    xc1, yc1, xc2, yc2 = torch.min(x1, x1g), torch.min(y1, y1g), torch.max(x2, x2g), torch.max(y2, y2g)
+    ac = (xc2 - xc1) * (yc2 - yc1)
+    return (1 - (iou - (ac - union) / (ac + eps))).sum()
+
+
+def box_reg_loss_terms(pred_deltas, src, tgt, weights, loss_type, beta, scale_clamp=SCALE_CLAMP):
+    """sum over the rows of the box-regression term (box_regression.py:252-269, fast_rcnn.py:663-677): pred_deltas, src, tgt [n, 4]"""
+    if loss_type == "smooth_l1":
+        return smooth_l1_loss(pred_deltas, get_deltas(src, tgt, weights), beta)
+    if loss_type == "giou":
+        return giou_loss(apply_deltas(pred_deltas, src, weights, scale_clamp), tgt)
+    raise ValueError(f"Invalid dense box regression loss type '{loss_type}'")
+
+
 def subsample_labels(labels, num_samples, positive_fraction, bg_label, gen):
     """sampling.py:9-54 with both permutations drawn from the replayable CPU generator ``gen``."""
     positive = torch.nonzero((labels != -1) & (labels != bg_label), as_tuple=True)[0]
@@ -218,8 +249,11 @@ class RPN(nn.Module):
         self.post_nms_topk = {True: r.POST_NMS_TOPK_TRAIN, False: r.POST_NMS_TOPK_TEST}
         self.nms_thresh, self.min_box_size = r.NMS_THRESH, float(cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE)
         self.weights = tuple(r.BBOX_REG_WEIGHTS)
-        self.smooth_l1_beta = r.SMOOTH_L1_BETA
-        assert r.BBOX_REG_LOSS_TYPE == "smooth_l1" and self.smooth_l1_beta == 0.0 and r.BOUNDARY_THRESH < 0
+        self.box_reg_loss_type, self.smooth_l1_beta = r.BBOX_REG_LOSS_TYPE, float(r.SMOOTH_L1_BETA)
+        assert r.BOUNDARY_THRESH < 0, "MODEL.RPN.BOUNDARY_THRESH >= 0 is not supported"
+        if self.box_reg_loss_type not in ("smooth_l1", "giou"):
+            raise ValueError(f"Invalid dense box regression loss type '{self.box_reg_loss_type}'")     # box_regression.py:269
+        assert self.smooth_l1_beta >= 0.0, "MODEL.RPN.SMOOTH_L1_BETA must not be negative"
         lw = r.LOSS_WEIGHT
         self.loss_weight = {"loss_rpn_cls": lw, "loss_rpn_loc": lw * r.BBOX_REG_LOSS_WEIGHT}
         self.sample_generator = torch.Generator()  # replayable CPU stream (seed it per rank: utils/env.py:27-46)
@@ -261,7 +295,7 @@ class RPN(nn.Module):
             torch.randperm(nneg, generator=self.sample_generator)
 
     def losses(self, anchors, logits, labels, deltas, matched):
-        """rpn.py:365-429 (+ _dense_box_regression_loss box_regression.py:229-270, smooth-L1 beta 0 = L1).
+        """rpn.py:365-429 (+ _dense_box_regression_loss box_regression.py:229-270: smooth-L1 with beta -- 0, the default, is L1 -- or GIoU).
         ``labels`` int8 [N, A]; ``matched`` = (matched gt index [N, A], per-image gt boxes)."""
         gl = labels
         n, A = gl.shape
@@ -275,8 +309,12 @@ class RPN(nn.Module):
             neg_g = self.last_neg_global
             self.storage["rpn/num_pos_anchors"] = pos_g.numel() / n      # (= (labels == 1).sum() / n: every positive label IS a sampled index)
             self.storage["rpn/num_neg_anchors"] = neg_g.numel() / n
-            both = layers.rpn_losses(logits.reshape(-1), deltas.reshape(-1, 4), pos_g, neg_g, midx.view(-1), gt_cat.float().contiguous(), gt_off,
-                                     anchors, self.weights, 1.0 / norm)
+            args = (logits.reshape(-1), deltas.reshape(-1, 4), pos_g, neg_g, midx.view(-1), gt_cat.float().contiguous(), gt_off, anchors,
+                    self.weights, 1.0 / norm)
+            if self.box_reg_loss_type == "smooth_l1" and self.smooth_l1_beta == 0.0:
+                both = layers.rpn_losses(*args)
+            else:
+                both = layers.rpn_losses_reg(*args, self.box_reg_loss_type, self.smooth_l1_beta, SCALE_CLAMP)
             out = {"loss_rpn_cls": both[0], "loss_rpn_loc": both[1]}
             return {k: v * self.loss_weight.get(k, 1.0) for k, v in out.items()}
         pos = gl == 1
@@ -285,8 +323,7 @@ class RPN(nn.Module):
         # positives = the sampled foreground picks (known index list, image by image in pick order): no nonzero, no host sync
         img, a = torch.div(pos_g, A, rounding_mode="floor"), pos_g % A
         mbox = gt_cat[midx.view(-1)[pos_g] + gt_off[img]]          # an image without boxes has no positives, so no row of it is read
-        gt_d = get_deltas(anchors[a], mbox, self.weights)
-        loc = torch.abs(deltas.reshape(-1, 4)[pos_g] - gt_d).sum()
+        loc = box_reg_loss_terms(deltas.reshape(-1, 4)[pos_g], anchors[a], mbox, self.weights, self.box_reg_loss_type, self.smooth_l1_beta)
         # (weight = validity instead of ``logits[valid]``: a boolean-mask gather sizes its result on the host -- a device sync in
         # the middle of the step; ignored anchors (-1) contribute exactly 0 to the sum and to the gradient either way)
         valid = gl >= 0

@@ -367,6 +367,21 @@ int cddmsl_rpn_losses(const float* logits, const float* deltas, const long* pos,
                       float* out2, const float* gout2, float* dlogits, float* ddeltas, void* stream);
 int cddmsl_box_l1(const float* deltas, int ld, const long* fg, int nfg, const long* cls, const float* src, const float* tgt, float wx, float wy,
                   float ww, float wh, float inv_norm, float* out1, const float* gout1, float* ddeltas, void* stream);
+/* The same pair with the reference's other box-regression terms (MODEL.RPN / ROI_BOX_HEAD .BBOX_REG_LOSS_TYPE, .SMOOTH_L1_BETA;
+ * box_regression.py:229-270, fast_rcnn.py:646-689): three scalars in front of the outputs, every other argument and convention as above.
+ *   loc_type 0: smooth-L1 with beta (fvcore smooth_l1_loss): n = |delta - get_deltas(..)|; beta < 1e-5: n; else n < beta ? 0.5 n n / beta : n - 0.5 beta,
+ *     gradient n < beta ? e / beta : sgn(e).  loc_type 0 with beta 0 returns the bytes of cddmsl_rpn_losses / cddmsl_box_l1.
+ *   loc_type 1: GIoU (fvcore giou_loss, reduction sum, eps 1e-7) of Box2BoxTransform.apply_deltas(the row's 4 deltas, anchor / src) (box_regression.py:77-115,
+ *     dw / dh clamped from above at scale_clamp) against the gt box / tgt; beta is ignored.  Backward = the analytic gradient with torch autograd's
+ *     conventions: max / min of EQUAL operands hands the prediction HALF the gradient, the clamp passes it at dw == scale_clamp and blocks it above,
+ *     a row whose intersection test (both comparisons strict) fails has no gradient through the intersection.
+ * CDDMSL_ERR_ARG, nothing written: loc_type not 0 / 1, beta < 0 or NaN, scale_clamp not finite at loc_type 1, and what the pair above refuses. */
+int cddmsl_rpn_losses_reg(const float* logits, const float* deltas, const long* pos, int npos, const long* neg, int nneg, const long* midx,
+                          const float* gt, const long* gt_off, const float* anchors, long A, float wx, float wy, float ww, float wh, float inv_norm,
+                          int loc_type, float beta, float scale_clamp, float* out2, const float* gout2, float* dlogits, float* ddeltas, void* stream);
+int cddmsl_box_reg_loss(const float* deltas, int ld, const long* fg, int nfg, const long* cls, const float* src, const float* tgt, float wx, float wy,
+                        float ww, float wh, float inv_norm, int loc_type, float beta, float scale_clamp, float* out1, const float* gout1, float* ddeltas,
+                        void* stream);
 
 /* ---- elementwise: preprocessing (modeling/meta_arch/rcnn.py:161-179,758-768, structures/image_list.py:72-124),
  * AvgPool2d(2) (clip_backbone.py:36,46,147), ReLU backward, column sums, fused clip+SGD (solver/build.py:59-130) -- */
