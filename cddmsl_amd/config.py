@@ -134,7 +134,9 @@ def get_cfg():
                              "POOLER_SAMPLING_RATIO": 0, "POOLER_TYPE": "ROIAlignV2", "CLS_AGNOSTIC_BBOX_REG": False},
             "CLIP": {"CROP_REGION_TYPE": "", "USE_TEXT_EMB_CLASSIFIER": False, "TEXT_EMB_PATH": None, "TEXT_EMB_DIM": 1024,
                      "NO_BOX_DELTA": False, "BG_CLS_LOSS_WEIGHT": None, "ONLY_SAMPLE_FG_PROPOSALS": False,
-                     "CLSS_TEMP": 0.01, "FOCAL_SCALED_LOSS": None, "MULTIPLY_RPN_SCORE": False},
+                     "CLSS_TEMP": 0.01, "FOCAL_SCALED_LOSS": None, "MULTIPLY_RPN_SCORE": False,
+                     # open-vocabulary inference (defaults.py: MODEL.CLIP.OPENSET_TEST_*): embeddings of the vocabulary to evaluate on
+                     "OPENSET_TEST_NUM_CLASSES": None, "OPENSET_TEST_TEXT_EMB_PATH": None},
         },
         "INPUT": {"MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR",
                   "MIN_SIZE_TRAIN_SAMPLING": "choice", "RANDOM_FLIP": "horizontal"},

@@ -170,9 +170,10 @@ def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False):
     ws = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     assert world == ws, f"run_eval_only: world={world} but the process group has {ws} ranks"
     from .data import build_detection_test_loader, load_voc_instances
-    dicts = load_voc_instances(args.voc_root, args.voc_split, VOC_CLASS_NAMES[: cfg.MODEL.ROI_HEADS.NUM_CLASSES])
+    names = VOC_CLASS_NAMES[: num_test_classes(model, cfg)]
+    dicts = load_voc_instances(args.voc_root, args.voc_split, names)
     loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
-    ev = PascalVOCDetectionEvaluator(args.voc_root, args.voc_split, args.voc_year, VOC_CLASS_NAMES[: cfg.MODEL.ROI_HEADS.NUM_CLASSES])
+    ev = PascalVOCDetectionEvaluator(args.voc_root, args.voc_split, args.voc_year, names)
     res = inference_on_dataset(model, loader, ev)
     if rank == 0:
         print({k: round(v, 4) for k, v in res["bbox"].items()})
@@ -183,6 +184,13 @@ def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False):
             print({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()})
             res.update(tta)
     return res if return_results else 0
+
+
+def num_test_classes(model, cfg):
+    """classes of the detections the model returns: the box head's test vocabulary (open-set inference evaluates on another
+    vocabulary than the head was trained on), NUM_CLASSES for a model without such a head"""
+    from .modeling.tta_vocabulary import merge_num_classes
+    return merge_num_classes(model, cfg)
 
 
 def tta_enabled(cfg):

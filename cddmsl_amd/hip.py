@@ -4,6 +4,7 @@ Every function here requires CUDA (=HIP) tensors and enqueues on torch's current
 fallbacks: a CPU tensor or a missing library raises ``HipLibraryError``.
 """
 import ctypes
+import math
 import os
 from ctypes import c_float, c_int, c_long, c_void_p
 
@@ -58,6 +59,8 @@ def _L():
         L.cddmsl_roi_align_backward.argtypes = [vp] * 7 + [ci] * 7 + [cf, ci, ci, ci, vp]
         L.cddmsl_nms_anyorder.argtypes = [vp] * 4 + [ci, cf, vp, vp, vp]
         L.cddmsl_soft_nms.argtypes = [vp] * 6 + [ci, ci, cf, cf, cf, ci, vp, vp, vp]
+        L.cddmsl_openset_logits.argtypes = [vp] * 4 + [ci] * 4 + [cf, cf, vp]
+        L.cddmsl_openset_select.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, cf, cf, cf] + [vp] * 6 + [ci, vp, vp, vp]
         L.cddmsl_roi_align_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
         L.cddmsl_roi_align_backward_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
         L.cddmsl_quantize_fp8.argtypes = [vp] * 4 + [c_long, ci, vp]
@@ -1214,6 +1217,76 @@ def soft_nms(boxes, scores, idxs, method, sigma, iou_threshold, prune_threshold,
     check(_L().cddmsl_soft_nms(ptr(boxes), ptr(scores), ptr(idxs), ptr(keep), ptr(keep_scores), ptr(nkeep), *args, ptr(ws), ctypes.byref(nbytes),
                                stream_ptr()), "cddmsl_soft_nms")
     return keep, keep_scores, nkeep
+
+
+OPENSET_MAX_CLASSES = 16384          # cddmsl_openset_logits / _select: classes of the test vocabulary
+
+
+@_timed("openset_logits")
+def openset_logits(x, wn, temperature, eps=1e-12, ld=None):
+    """x [R, D] f32, wn [K, D] f32 unit rows -> (logits [R, ld] f32 with column K exactly 0, stats [R, 2] f32 = (row max, sum
+    exp(logit - max)) over the K+1 logits): the open-vocabulary classifier on the exact-f32 MFMA (cddmsl_openset_logits).
+    ``ld`` (default K + 1) is the row pitch; columns beyond K are left as allocated."""
+    require_cuda(x, wn)
+    R, D = x.shape
+    K = wn.shape[0]
+    ld = K + 1 if ld is None else int(ld)
+    assert x.dtype == wn.dtype == torch.float32 and x.is_contiguous() and wn.is_contiguous() and wn.dim() == 2 and wn.shape[1] == D
+    logits = torch.empty((R, max(ld, 0)), device=x.device, dtype=torch.float32)
+    stats = torch.empty((R, 2), device=x.device, dtype=torch.float32)
+    check(_L().cddmsl_openset_logits(ptr(x), ptr(wn), ptr(logits), ptr(stats), R, D, K, ld, float(temperature), float(eps), stream_ptr()),
+          "cddmsl_openset_logits")
+    return logits, stats
+
+
+def openset_cap(R, K, score_thresh, with_objectness):
+    """Candidate slots ``openset_select`` allocates: a softmax row holds at most ceil(1 / thresh) - and never more than K - entries
+    above ``thresh``; with the objectness product (the square root of a product with an unbounded factor) any entry may pass."""
+    if with_objectness or not score_thresh > 0.0:
+        return R * K
+    return R * min(K, int(math.ceil(1.0 / score_thresh)))
+
+
+@_timed("openset_select")
+def openset_select_raw(logits, stats, K, boxes, objectness, img_h, img_w, score_thresh, cap):
+    """cddmsl_openset_select without the readback -> (cand_row int32 [cap], cand_cls int32 [cap], cand_score f32 [cap], cand_box
+    f32 [cap, 4], valid u8 [R], count int32 [1]); count is the full number of candidates, only the first ``cap`` are written."""
+    require_cuda(logits, stats, boxes, objectness)
+    R, ld = logits.shape
+    assert logits.dtype == stats.dtype == boxes.dtype == torch.float32 and logits.is_contiguous() and stats.is_contiguous() and boxes.is_contiguous()
+    assert tuple(stats.shape) == (R, 2) and boxes.dim() == 2 and boxes.shape[0] == R
+    assert objectness is None or (objectness.dtype == torch.float32 and objectness.is_contiguous() and objectness.numel() == R)
+    dev = logits.device
+    cap = int(cap)
+    cand_row = torch.empty(cap, device=dev, dtype=torch.int32)
+    cand_cls = torch.empty(cap, device=dev, dtype=torch.int32)
+    cand_score = torch.empty(cap, device=dev, dtype=torch.float32)
+    cand_box = torch.empty((cap, 4), device=dev, dtype=torch.float32)
+    valid = torch.empty(R, device=dev, dtype=torch.uint8)
+    count = torch.zeros(1, device=dev, dtype=torch.int32)
+    nbytes = ctypes.c_size_t(0)
+    head = (ptr(logits), ptr(stats), ld, ptr(boxes), boxes.shape[1], ptr(objectness), R, int(K), float(img_h), float(img_w), float(score_thresh),
+            ptr(cand_row), ptr(cand_cls), ptr(cand_score), ptr(cand_box), ptr(valid), ptr(count), cap)
+    check(_L().cddmsl_openset_select(*head, None, ctypes.byref(nbytes), stream_ptr()), "cddmsl_openset_select(size)")
+    ws = workspace("openset_select", max(nbytes.value, 1), dev)
+    check(_L().cddmsl_openset_select(*head, ptr(ws), ctypes.byref(nbytes), stream_ptr()), "cddmsl_openset_select")
+    return cand_row, cand_cls, cand_score, cand_box, valid, count
+
+
+def openset_select(logits, stats, K, boxes, objectness, img_h, img_w, score_thresh, cap=None):
+    """fast_rcnn_inference_single_image up to its NMS on the open-vocabulary logits: softmax from ``stats``, optional geometric
+    mean with ``objectness`` [R], rows with a non-finite box or score dropped, boxes clipped to the image, entries above
+    ``score_thresh`` in (row, class) order -> (rows int32 [n], classes int32 [n], scores f32 [n], boxes f32 [n, 4], valid u8 [R]).
+    ONE host readback (n).  ``cap`` defaults to ``openset_cap``; more candidates than ``cap`` raise ValueError, never a truncation."""
+    R = logits.shape[0]
+    if cap is None:
+        cap = openset_cap(R, K, score_thresh, objectness is not None)
+    cand_row, cand_cls, cand_score, cand_box, valid, count = openset_select_raw(logits, stats, K, boxes, objectness, img_h, img_w,
+                                                                                score_thresh, cap)
+    n = int(count[0])
+    if n > cap:
+        raise ValueError(f"openset_select: {n} candidates exceed the {cap} slots of this call")
+    return cand_row[:n], cand_cls[:n], cand_score[:n], cand_box[:n], valid
 
 
 @_timed("rpn_decode")

@@ -5,3 +5,4 @@ from .resnet import build_resnet_backbone, ResNet, BasicStem, BottleneckBlock  #
 from .roi_heads import Res5ROIHeads, CLIPRes5ROIHeads, FastRCNNOutputLayers, ROIPooler, build_roi_heads  # noqa
 from .rcnn import GeneralizedRCNN, GatherLayer, build_model  # noqa
 from .test_time_augmentation import DatasetMapperTTA, GeneralizedRCNNWithTTA  # noqa
+from . import tta_vocabulary  # noqa  (the wrapper merges over the box head's test vocabulary)

@@ -105,6 +105,46 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
     return ki[scores[ki].sort(descending=True, stable=True)[1]]
 
 
+def plan_nms_groups(counts, cap):
+    """Packs the categories 0 .. len(counts)-1 (``counts[c]`` candidates each), in ascending id order, greedily into runs whose
+    totals stay within ``cap`` -> list of (first category, one past the last).  Every category lies in exactly one run; a single
+    category above ``cap`` raises ValueError."""
+    runs, lo, total = [], 0, 0
+    for c, n in enumerate(counts):
+        n = int(n)
+        if n > cap:
+            raise ValueError(f"nms: {n} candidates in one group exceed the kernel's limit of {cap}")
+        if total + n > cap:
+            runs.append((lo, c))
+            lo, total = c, 0
+        total += n
+    if lo < len(counts):
+        runs.append((lo, len(counts)))
+    return runs
+
+
+def batched_nms_grouped(boxes, scores, idxs, iou_threshold, cap=NMS_MAX_CANDIDATES):
+    """``batched_nms`` for many categories: up to ``cap`` candidates it IS ``batched_nms``; above, ONE readback of the
+    per-category counts, ``plan_nms_groups`` packs neighbouring categories into runs of at most ``cap`` candidates and each run gets
+    one coordinate-trick pass (the shift of the single pass, so a run sees the boxes the single pass would) -- a handful of passes
+    where the per-category loop of ``batched_nms`` makes one per category.  Same result order: descending score, ties by ascending
+    candidate index."""
+    n = boxes.shape[0]
+    if n <= cap:
+        return batched_nms(boxes, scores, idxs, iou_threshold)
+    boxes = boxes.float()
+    idxs = idxs.long()
+    runs = plan_nms_groups(torch.bincount(idxs).tolist(), cap)
+    shifted = boxes + (idxs.to(boxes) * (boxes.max() + 1.0))[:, None]
+    keep_mask = torch.zeros(n, dtype=torch.bool, device=boxes.device)
+    for lo, hi in runs:
+        sel = torch.nonzero((idxs >= lo) & (idxs < hi)).squeeze(1)
+        if sel.numel():
+            keep_mask[sel[_nms_sorted(shifted[sel], scores[sel], iou_threshold)]] = True
+    ki = torch.nonzero(keep_mask).squeeze(1)
+    return ki[scores[ki].sort(descending=True, stable=True)[1]]
+
+
 SOFT_NMS_METHODS = tuple(hip.SOFT_NMS_METHODS)
 
 
@@ -169,6 +209,9 @@ class FastRCNNOutputLayers(nn.Module):
         c = cfg.MODEL.CLIP
         self.num_classes = cfg.MODEL.ROI_HEADS.NUM_CLASSES
         self.use_clip_cls_emb = bool(c.USE_TEXT_EMB_CLASSIFIER)
+        if c.get("OPENSET_TEST_TEXT_EMB_PATH", None) and not self.use_clip_cls_emb:
+            # (the reference ignores the path here; a closed-set evaluation nobody asked for helps no one)
+            raise ValueError("MODEL.CLIP.OPENSET_TEST_TEXT_EMB_PATH needs MODEL.CLIP.USE_TEXT_EMB_CLASSIFIER True")
         if self.use_clip_cls_emb:       # CLIP text embeddings as the classifier (fast_rcnn.py:440-475)
             d = c.TEXT_EMB_DIM
             self.temperature = c.CLSS_TEMP
@@ -180,14 +223,31 @@ class FastRCNNOutputLayers(nn.Module):
                 self.cls_score.weight.data.copy_(torch.load(c.TEXT_EMB_PATH, map_location="cpu", weights_only=True))
             self.cls_score.weight.requires_grad = False       # frozen embeddings fast_rcnn.py:453
             self.cls_bg_score.weight.requires_grad = False    # zero background embedding :458-463
+            test_path = c.get("OPENSET_TEST_TEXT_EMB_PATH", None)
+            if test_path:                                     # the vocabulary to evaluate on (fast_rcnn.py:465-475)
+                w = torch.load(test_path, map_location="cpu", weights_only=True)
+                if w.dim() != 2 or w.shape[1] != d:
+                    raise ValueError(f"MODEL.CLIP.OPENSET_TEST_TEXT_EMB_PATH holds {tuple(w.shape)}, expected [K_test, {d}]")
+                want = c.get("OPENSET_TEST_NUM_CLASSES", None)
+                if want is not None and int(want) != w.shape[0]:
+                    raise ValueError(f"MODEL.CLIP.OPENSET_TEST_NUM_CLASSES is {want}, the embedding file has {w.shape[0]} rows")
+                if not 1 <= w.shape[0] <= hip.OPENSET_MAX_CLASSES:
+                    raise ValueError(f"open-set test vocabulary of {w.shape[0]} classes: the kernels take 1 .. {hip.OPENSET_MAX_CLASSES}")
+                self.test_cls_score = _Linear(d, w.shape[0], bias=False)
+                self.test_cls_score.weight.data.copy_(w)
+                self.test_cls_score.weight.requires_grad = False
         else:                           # regular linear classifier (fast_rcnn.py:476-479), stock R50-C4
             d = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)
             self.cls_score = _Linear(d, self.num_classes + 1)
             nn.init.normal_(self.cls_score.weight, std=0.01)
-        self.bbox_pred = _Linear(d, self.num_classes * 4)
+        self.cls_agnostic_bbox_reg = bool(cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG)
+        # class-agnostic deltas come with the open-vocabulary configuration (the reference's ovd configs set both); without an open-set
+        # test vocabulary everything is as before, this refusal included
+        assert not self.cls_agnostic_bbox_reg or self.openset, \
+            "MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG is supported together with MODEL.CLIP.OPENSET_TEST_TEXT_EMB_PATH only"
+        self.bbox_pred = _Linear(d, 4 if self.cls_agnostic_bbox_reg else self.num_classes * 4)      # fast_rcnn.py:482-484
         nn.init.normal_(self.bbox_pred.weight, std=0.001)
         self.box_weights = tuple(cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS)
-        assert not cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG, "MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG is not supported"
         self.box_reg_loss_type = cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE
         self.smooth_l1_beta = float(cfg.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA)
         if self.box_reg_loss_type not in ("smooth_l1", "giou"):
@@ -201,6 +261,10 @@ class FastRCNNOutputLayers(nn.Module):
         self.test_nms_thresh = cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST
         self.test_topk_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         self.no_box_delta = bool(c.NO_BOX_DELTA)
+        if self.openset and self.num_test_classes != self.num_classes and not self.cls_agnostic_bbox_reg and not self.no_box_delta:
+            # (the reference fails at its boxes[filter_mask] in the middle of the evaluation)
+            raise ValueError(f"open-set test vocabulary of {self.num_test_classes} classes on a head with class-specific box deltas for "
+                             f"{self.num_classes}: set MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG or MODEL.CLIP.NO_BOX_DELTA")
         self.multiply_rpn_score = bool(c.MULTIPLY_RPN_SCORE)
         # soft-NMS at inference (fast_rcnn.py:401-404; defaults.py:399-404)
         self.soft_nms_enabled = bool(cfg.MODEL.ROI_HEADS.get("SOFT_NMS_ENABLED", False))
@@ -212,7 +276,18 @@ class FastRCNNOutputLayers(nn.Module):
         self.compute_dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "fp8": torch.bfloat16}[cfg.MODEL.get("COMPUTE_DTYPE", "bf16")]
         self.fp8 = cfg.MODEL.get("COMPUTE_DTYPE", "bf16") == "fp8"
         self._wn = None
+        self._test_wn = None
         self.storage = {}
+
+    @property
+    def openset(self):
+        """an open-set test vocabulary was given: not training, scores come from ``test_cls_score``"""
+        return getattr(self, "test_cls_score", None) is not None
+
+    @property
+    def num_test_classes(self):
+        """classes of the detections ``inference`` returns: the test vocabulary's with open-set on, else NUM_CLASSES"""
+        return self.test_cls_score.weight.shape[0] if self.openset else self.num_classes
 
     def _text_emb(self):
         w = self.cls_score.weight
@@ -221,9 +296,28 @@ class FastRCNNOutputLayers(nn.Module):
             self._wn = ((w.device, w._version), F.normalize(w.detach().float(), p=2.0, dim=1).contiguous())
         return self._wn[1]
 
+    def _test_text_emb(self):
+        w = self.test_cls_score.weight
+        if self._test_wn is None or self._test_wn[0] != (w.device, w._version):
+            assert float(self.cls_bg_score.weight.abs().max()) == 0.0, "background embedding must stay zero (fast_rcnn.py:460)"
+            self._test_wn = ((w.device, w._version), F.normalize(w.detach().float(), p=2.0, dim=1).contiguous())
+        return self._test_wn[1]
+
+    def _box_deltas(self, xt):
+        if self.cls_agnostic_bbox_reg:
+            # 4 output columns are no whole 16-byte chunk in bf16: the zero-padded heads GEMM the RPN's heads use, forward and backward
+            y = layers.fused_heads(xt.contiguous().view(1, 1, xt.shape[0], xt.shape[1]), [(self.bbox_pred.weight, self.bbox_pred.bias)])
+            return y.view(xt.shape[0], -1)[:, :4].contiguous()
+        return layers.linear(xt, self.bbox_pred.pw(), self.bbox_pred.bias, out_f32=True)
+
     def forward(self, x):
-        """x [R, 1024] f32 -> (scores [R, K+1] f32, deltas [R, 4K] f32)   fast_rcnn.py:529-572"""
+        """x [R, 1024] f32 -> (scores [R, K+1] f32, deltas [R, 4K] f32, or [R, 4] class-agnostic)   fast_rcnn.py:529-572.
+        Open-set and not training: (logits [R, K_test+1] f32, deltas, stats [R, 2] f32) from the test vocabulary's embeddings
+        (hip.openset_logits, always f32); ``inference`` takes the softmax from ``stats``."""
         xt = x.to(self.compute_dtype)
+        if self.openset and not self.training:              # fast_rcnn.py:549-552
+            logits, stats = hip.openset_logits(x.float().contiguous(), self._test_text_emb(), self.temperature)
+            return logits, self._box_deltas(xt), stats
         if self.use_clip_cls_emb:
             wn = self._text_emb()
             wn8 = None
@@ -232,8 +326,7 @@ class FastRCNNOutputLayers(nn.Module):
                     self._wn8 = (wn, layers.fp8_unit_rows(wn))
                 wn8 = self._wn8[1]
             scores = layers.cosine_logits(x, wn, self.temperature, fp8=self.fp8, wn8=wn8)
-            deltas = layers.linear(xt, self.bbox_pred.pw(), self.bbox_pred.bias, out_f32=True)
-            return scores, deltas
+            return scores, self._box_deltas(xt)
         # plain classifier: cls_score (K+1) and bbox_pred (4K) as ONE padded GEMM (row widths must be whole 16-B chunks)
         k1 = self.num_classes + 1
         y = layers.fused_heads(xt.contiguous().view(1, 1, xt.shape[0], xt.shape[1]),
@@ -259,15 +352,17 @@ class FastRCNNOutputLayers(nn.Module):
             fg = to_device_async(torch.cat(idx), gt_classes.device)
         else:
             fg = torch.nonzero((gt_classes >= 0) & (gt_classes < self.num_classes), as_tuple=True)[0]
-        if deltas.is_cuda and deltas.dtype == torch.float32 and deltas.shape[1] == 4 * self.num_classes:
+        agnostic = self.cls_agnostic_bbox_reg               # [R, 4] deltas: the kernels take cls = NULL with a row pitch of 4
+        if deltas.is_cuda and deltas.dtype == torch.float32 and deltas.shape[1] == (4 if agnostic else 4 * self.num_classes):
             # one kernel per direction over the foreground index list (class-specific columns picked inside)
-            args = (deltas, fg, gt_classes, pboxes.float(), gboxes.float(), self.box_weights, 1.0 / max(gt_classes.numel(), 1.0))
+            args = (deltas, fg, None if agnostic else gt_classes, pboxes.float(), gboxes.float(), self.box_weights,
+                    1.0 / max(gt_classes.numel(), 1.0))
             if self.box_reg_loss_type == "smooth_l1" and self.smooth_l1_beta == 0.0:
                 loss_box = layers.box_l1(*args)
             else:
                 loss_box = layers.box_reg_loss(*args, self.box_reg_loss_type, self.smooth_l1_beta, SCALE_CLAMP)
         else:
-            fg_pred = deltas.view(-1, self.num_classes, 4)[fg, gt_classes[fg]]
+            fg_pred = deltas[fg] if agnostic else deltas.view(-1, self.num_classes, 4)[fg, gt_classes[fg]]
             loss_box = box_reg_loss_terms(fg_pred, pboxes[fg], gboxes[fg], self.box_weights, self.box_reg_loss_type,
                                           self.smooth_l1_beta) / max(gt_classes.numel(), 1.0)
         out = {"loss_cls": loss_cls, "loss_box_reg": loss_box}
@@ -278,20 +373,22 @@ class FastRCNNOutputLayers(nn.Module):
         """fast_rcnn.py:760-790 -> per image [Ri, 4K] class-specific boxes"""
         if not len(proposals):
             return []
-        _, deltas = predictions
+        deltas = predictions[1]
         pboxes = torch.cat([p.proposal_boxes.tensor for p in proposals], dim=0)
         boxes = pboxes if self.no_box_delta else apply_deltas(deltas, pboxes, self.box_weights)
         return boxes.split([len(p) for p in proposals])
 
     def predict_probs(self, predictions, proposals):
         """fast_rcnn.py:792-811: softmax over the K+1 logits"""
-        scores, _ = predictions
+        scores = predictions[0]
         return F.softmax(scores.float(), dim=-1).split([len(p) for p in proposals], dim=0)
 
     def inference(self, predictions, proposals, proposal_indices=False):
         """fast_rcnn.py:691-724 -> (list[Instances(pred_boxes, scores, pred_classes)], list[kept proposal indices]); the indices
         count finite rows only unless ``proposal_indices`` (fast_rcnn_inference_single_image)"""
         boxes = self.predict_boxes(predictions, proposals)
+        if self.openset and not self.training:
+            return self._openset_inference(predictions, boxes, proposals, proposal_indices)
         scores = self.predict_probs(predictions, proposals)
         if self.multiply_rpn_score and not self.training:   # geometric mean with the RPN objectness (fast_rcnn.py:708-710)
             scores = [(s * p.objectness_logits[:, None]) ** 0.5 for s, p in zip(scores, proposals)]
@@ -300,6 +397,39 @@ class FastRCNNOutputLayers(nn.Module):
                                                 soft_nms_method=self.soft_nms_method, soft_nms_sigma=self.soft_nms_sigma,
                                                 soft_nms_prune=self.soft_nms_prune) for b, s, p in zip(boxes, scores, proposals)]
         return [o[0] for o in out], [o[1] for o in out]
+
+    def _openset_inference(self, predictions, boxes, proposals, proposal_indices):
+        """``inference`` on the open-vocabulary pair: per image one hip.openset_select (softmax, objectness product, finite-row
+        filter, clip, threshold and the (row, class) candidate list, one readback) where the closed-set path runs softmax, mask,
+        nonzero and gathers over [R, K+1]; then the same per-category NMS and top-k."""
+        if len(predictions) != 3:
+            raise ValueError("open-set inference takes the (logits, deltas, stats) that forward() returns in eval mode")
+        logits, _, stats = predictions
+        k = self.num_test_classes
+        insts, kepts, off = [], [], 0
+        for b, p in zip(boxes, proposals):
+            n = len(p)
+            obj = p.objectness_logits.float().contiguous() if self.multiply_rpn_score else None       # fast_rcnn.py:708-710
+            rows, cls, scores, cboxes, valid = hip.openset_select(logits[off:off + n], stats[off:off + n], k, b.float().contiguous(), obj,
+                                                                   p.image_size[0], p.image_size[1], self.test_score_thresh)
+            off += n
+            cls = cls.long()
+            if not self.soft_nms_enabled:
+                keep = batched_nms_grouped(cboxes, scores, cls, self.test_nms_thresh)
+            else:
+                keep, soft_scores = batched_soft_nms(cboxes, scores, cls, self.soft_nms_method, self.soft_nms_sigma, self.test_nms_thresh,
+                                                     self.soft_nms_prune, max_keep=self.test_topk_per_image if self.test_topk_per_image >= 0 else -1)
+                scores[keep] = soft_scores
+            if self.test_topk_per_image >= 0:
+                keep = keep[:self.test_topk_per_image]
+            res = Instances(tuple(p.image_size))
+            res.pred_boxes, res.scores, res.pred_classes = Boxes(cboxes[keep]), scores[keep], cls[keep]
+            kept = rows[keep].long()
+            if not proposal_indices:        # the reference's indices count the rows left after the non-finite ones are dropped
+                kept = (valid.long().cumsum(0) - 1)[kept]
+            insts.append(res)
+            kepts.append(kept)
+        return insts, kepts
 
     def _log_stats(self, scores, gt_classes):
         """_log_classification_stats fast_rcnn.py:100-127 (kept on device; no sync)."""

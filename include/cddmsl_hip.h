@@ -207,6 +207,30 @@ int cddmsl_nms_anyorder(const float* boxes, const float* scores, long* keep, int
 int cddmsl_soft_nms(const float* boxes, const float* scores, const long* idxs, long* keep, float* keep_scores, int* nkeep, int K,
                     int method, float sigma, float iou_threshold, float prune_threshold, int max_keep, void* temp,
                     size_t* temp_bytes, void* stream);
+/* ---- open-vocabulary inference (csrc/openset.hip): the test_cls_score branch of FastRCNNOutputLayers.forward, predict_probs,
+ * the RPN-objectness product and fast_rcnn_inference_single_image up to its NMS (roi_heads/fast_rcnn.py:546-565, 793-810, 706-710,
+ * 155-180).  Everything f32; no atomics: two runs give the same bits.
+ *   cddmsl_openset_logits  x [R][D], wn [K][D] unit rows -> logits [R][ld]: logits[r][c] = (x_hat_r . wn_c) * (1/T) for c < K with
+ *                          x_hat = x * (1 / max(||x||, eps)) rounded per element and the contraction accumulated in f32 on the
+ *                          32x32x2 f32 MFMA; logits[r][K] = 0 (zero background embedding); columns beyond K are not touched.
+ *                          stats [R][2] = (m_r, l_r): the maximum of the row's K+1 logits and sum exp(logit - m_r).
+ *                          D % 4 == 0, 1 <= K <= 16384, ld >= K + 1, T > 0; R == 0 succeeds with nothing launched.
+ *   cddmsl_openset_select  score = expf(logit - m) / l, with objectness (nullable, [R]) sqrtf(score * objectness[r]).  A row with a
+ *                          non-finite value among its ldb box values or its K+1 scores gets valid[r] = 0 and contributes nothing.
+ *                          Entries with score > score_thresh and c < K are written in (row, class) order -- mask.nonzero()'s --
+ *                          as cand_row / cand_cls / cand_score / cand_box; the box is the row's box of that class (ldb == 4:
+ *                          class-agnostic, ldb == 4K: class-specific) clipped to [0, img_w] x [0, img_h].  count[0] is the FULL
+ *                          number of entries; only the first cap are written -- the caller compares.  Scratch from the caller:
+ *                          temp == NULL returns *temp_bytes.  No allocation, no synchronisation.
+ * Alignment: x, wn (logits call) and boxes, cand_box (select call) are accessed as 16-byte vectors and must be 16-byte aligned; the
+ * other buffers need their element's alignment only.
+ * Any other argument, a misaligned pointer included, returns CDDMSL_ERR_ARG with nothing written. */
+int cddmsl_openset_logits(const float* x, const float* wn, float* logits, float* stats, int R, int D, int K, int ld,
+                          float temperature, float eps, void* stream);
+int cddmsl_openset_select(const float* logits, const float* stats, int ld, const float* boxes, int ldb, const float* objectness,
+                          int R, int K, float img_h, float img_w, float score_thresh, int* cand_row, int* cand_cls,
+                          float* cand_score, float* cand_box, unsigned char* valid, int* count, int cap, void* temp,
+                          size_t* temp_bytes, void* stream);
 int cddmsl_iou_match(const float* gt, int G, const float* preds, int P, long* matches, signed char* labels,
                      unsigned int* best_ws, int nthr, float t0, float t1, int l0, int l1, int l2, int allow_low_quality,
                      void* stream);
