@@ -141,7 +141,10 @@ def get_cfg():
         "INPUT": {"MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR",
                   "MIN_SIZE_TRAIN_SAMPLING": "choice", "RANDOM_FLIP": "horizontal"},
         "DATASETS": {"TRAIN": (), "TEST": ()},
-        "DATALOADER": {"NUM_WORKERS": 4, "ASPECT_RATIO_GROUPING": True, "FILTER_EMPTY_ANNOTATIONS": True},
+        "DATALOADER": {"NUM_WORKERS": 4, "ASPECT_RATIO_GROUPING": True, "FILTER_EMPTY_ANNOTATIONS": True,
+                       # build-specific: ResizeShortestEdge / RandomFlip / HWC -> CHW / RGB -> BGR of the loader's images in one HIP launch per
+                       # batch (bit-equal to the PIL path) instead of in the mapper; the loader's device must be a GPU
+                       "DEVICE_RESIZE": False},
         "SOLVER": {"IMS_PER_BATCH": 16, "BASE_LR": 0.001, "MOMENTUM": 0.9, "NESTEROV": False, "WEIGHT_DECAY": 0.0001,
                    "WEIGHT_DECAY_NORM": 0.0, "GAMMA": 0.1, "STEPS": (30000,), "MAX_ITER": 40000, "WARMUP_FACTOR": 1.0 / 1000,
                    "WARMUP_ITERS": 1000, "WARMUP_METHOD": "linear", "CHECKPOINT_PERIOD": 5000, "BIAS_LR_FACTOR": 1.0,

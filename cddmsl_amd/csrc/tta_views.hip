@@ -2,14 +2,8 @@
 // one u8 CHW image -> PIL-exact bilinear resize to (newh, neww) -> (x/div - mean)/std -> zero-padded NHWC slot, and the same view
 // mirrored left-right into a second slot, in ONE launch.  The host never sees a view.
 //
-// The resize is Pillow's ImagingResample (bilinear, 8 bits per channel), reproduced bit for bit:
-//   * two separable passes, horizontal first, with a uint8 intermediate between them;
-//   * per output index a window [min, min + n) of the input axis and n <= ksize coefficients, int(0.5 + w * 2^22) of the normalised
-//     triangle weights.  The tables are built on the HOST in double (cddmsl_amd/hip.py:_resample_table) in Pillow's order of
-//     operations and only READ here: recomputing one on the device (contraction, another rounding) changes pixels;
-//   * each pass is clip8((2^21 + sum k * pixel) >> 22).  The coefficients of one output sum to 2^22 up to rounding and are never
-//     negative, so the sum stays below 255 * 2^22 + 2^21 + ksize * 255 < 2^31: the int32 accumulator is exact;
-//   * a pass whose size does not change is skipped (the pixels are copied), as Pillow skips it: its table is not the identity.
+// The resize is Pillow's ImagingResample (bilinear, 8 bits per channel), reproduced bit for bit from host-built coefficient tables
+// (cddmsl_amd/resample.py); its arithmetic, the tile geometry and the LDS staging are resample.h, shared with loader_resize.hip.
 // The normalisation is the expression of preprocess_px (elementwise.hip), so a slot is bit-equal to cddmsl_preprocess_batch of the
 // resized uint8 view.
 //
@@ -19,40 +13,13 @@
 // one tile column (window and coefficients in registers across the rows); in the vertical pass a wave is one output row, so the
 // window and coefficients are wave-uniform.  A tile whose rows do not fit the LDS buffer (vertical scale beyond ~4)
 // recomputes the horizontal taps per vertical tap instead: slower, same values.
-#include "common.h"
+#include "resample.h"
 
 namespace {
 
-constexpr int TH = 16, TW = 64, NT = 256;      // output tile, threads (4 pixels per thread)
-constexpr int RMAX = 80;                       // horizontally resampled rows kept in LDS: TH * 4 + 2 * 4 + 1 = 73 at scale 4
-constexpr int PREC = 22;                       // Pillow's PRECISION_BITS
-constexpr int KREG = 5;                        // horizontal coefficients a thread keeps in registers
-static_assert(NT % TW == 0, "a thread owns one tile column");
-
-__device__ __forceinline__ int clip8(int v) {
-  v >>= PREC;
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
-struct Axis { const int* lo; const int* n; const int* k; int ks; };   // window start, length, coefficients [out][ks]; lo == null: copy
+using namespace resample;      // tile geometry, the two passes and their LDS staging: shared with loader_resize.hip
 
 struct Dst { char* out; int n, Hp, Wp; };
-
-// the horizontal pass for one (plane row, output column)
-__device__ __forceinline__ int hpass(const unsigned char* row, int x, int w, const Axis& ax) {
-  if (!ax.lo) return row[x];
-  const int lo = ax.lo[x];
-  int n = ax.n[x];
-  n = n < ax.ks ? n : ax.ks;
-  const int* k = ax.k + (long)x * ax.ks;
-  int s = 1 << (PREC - 1);
-  for (int t = 0; t < n; ++t) {
-    int xi = lo + t;
-    xi = xi < 0 ? 0 : (xi < w ? xi : w - 1);        // (a valid table never reaches the clamp: it keeps a bad one inside the image)
-    s += (int)row[xi] * k[t];
-  }
-  return clip8(s);
-}
 
 template <typename T> struct Px;
 template <> struct Px<__bf16> {
@@ -81,94 +48,20 @@ template <typename T>
 __global__ void __launch_bounds__(NT) k_tta_view(const unsigned char* __restrict__ img, int h, int w, int newh, int neww, Axis ax, Axis ay,
                                                  Dst d0, Dst d1, int Cp, float m0, float m1, float m2, float s0, float s1, float s2,
                                                  float div) {
-  __shared__ unsigned char hrow[3 * RMAX * TW];
+  __shared__ unsigned char hrow[HROW_BYTES];
   const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
   const bool inside = y0 < newh && x0 < neww;       // block-uniform: the tile holds view pixels, not padding only
+  const Src<1> src{img, (long)h * w, (long)w};
   int r0 = 0, nrows = 0;
-  if (inside) {
-    const int yl = (y0 + TH < newh ? y0 + TH : newh) - 1;
-    if (ay.lo) {
-      r0 = ay.lo[y0];
-      const int nl = ay.n[yl] < ay.ks ? ay.n[yl] : ay.ks;
-      nrows = ay.lo[yl] + nl - r0;                  // windows move monotonically with y
-    } else {
-      r0 = y0;
-      nrows = yl + 1 - y0;
-    }
-  }
+  if (inside) tile_rows(ay, y0, newh, r0, nrows);
   const bool staged = inside && nrows <= RMAX;      // block-uniform
-  const long plane = (long)h * w;
-  if (staged) {
-    // a thread keeps ONE column of the tile (NT is a multiple of TW) and walks the staged rows: its window and its first KREG
-    // coefficients are read once and stay in registers (ksize <= 5 up to a horizontal ratio of 2; longer windows read the rest)
-    const int cx = threadIdx.x % TW, x = x0 + cx;
-    if (x < neww) {
-      int lo = x, n = 0, kr[KREG];
-      const int* k = nullptr;
-      if (ax.lo) {
-        lo = ax.lo[x];
-        n = ax.n[x] < ax.ks ? ax.n[x] : ax.ks;
-        k = ax.k + (long)x * ax.ks;
-      }
-#pragma unroll
-      for (int t = 0; t < KREG; ++t) kr[t] = t < n ? k[t] : 0;
-      for (int r = threadIdx.x / TW; r < nrows; r += NT / TW) {
-        int yi = r0 + r;
-        yi = yi < 0 ? 0 : (yi < h ? yi : h - 1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const unsigned char* row = img + c * plane + (long)yi * w;
-          int v;
-          if (!ax.lo) {
-            v = row[x];
-          } else {
-            int s = 1 << (PREC - 1);
-#pragma unroll
-            for (int t = 0; t < KREG; ++t) {
-              int xi = lo + t;
-              xi = xi < 0 ? 0 : (xi < w ? xi : w - 1);     // (a valid table never reaches the clamp)
-              if (t < n) s += (int)row[xi] * kr[t];
-            }
-            for (int t = KREG; t < n; ++t) {
-              int xi = lo + t;
-              xi = xi < 0 ? 0 : (xi < w ? xi : w - 1);
-              s += (int)row[xi] * k[t];
-            }
-            v = clip8(s);
-          }
-          hrow[(c * RMAX + r) * TW + cx] = (unsigned char)v;
-        }
-      }
-    }
-  }
+  if (staged) stage_rows<1>(hrow, src, h, w, neww, ax, x0, r0, nrows);
   __syncthreads();
   for (int i = threadIdx.x; i < TH * TW; i += NT) {
     const int cx = i % TW, x = x0 + cx, y = y0 + i / TW;
     if (y < newh && x < neww) {
       int v[3];
-      if (!ay.lo) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          v[c] = staged ? hrow[(c * RMAX + (y - r0)) * TW + cx] : hpass(img + c * plane + (long)y * w, x, w, ax);
-      } else {
-        const int lo = ay.lo[y];
-        int n = ay.n[y];
-        n = n < ay.ks ? n : ay.ks;
-        const int* k = ay.k + (long)y * ay.ks;
-        int s[3] = {1 << (PREC - 1), 1 << (PREC - 1), 1 << (PREC - 1)};
-        for (int t = 0; t < n; ++t) {
-          const int kt = k[t];
-          int yi = lo + t;
-          yi = yi < 0 ? 0 : (yi < h ? yi : h - 1);
-          int rr = yi - r0;                          // staged: inside [0, nrows) for a valid table
-          rr = rr < 0 ? 0 : (rr < RMAX ? rr : RMAX - 1);
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            s[c] += kt * (staged ? (int)hrow[(c * RMAX + rr) * TW + cx] : hpass(img + c * plane + (long)yi * w, x, w, ax));
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = clip8(s[c]);
-      }
+      vpass<1, 3>(hrow, staged, src, 0, h, w, ax, ay, x, y, cx, r0, v);
       const float a = ((float)v[0] / div - m0) / s0, b = ((float)v[1] / div - m1) / s1, c = ((float)v[2] / div - m2) / s2;
       if (y < d0.Hp && x < d0.Wp) store_px<T>(d0, y, x, Cp, a, b, c);
       if (d1.out && y < d1.Hp && neww - 1 - x < d1.Wp) store_px<T>(d1, y, neww - 1 - x, Cp, a, b, c);

@@ -16,6 +16,10 @@ Host -> device: images leave the loader as pinned uint8 tensors and are copied w
 padding happen on the GPU (``cddmsl_preprocess``).  Resizing is PIL bilinear on uint8, exactly the call the reference makes
 (``Image.resize((w, h), BILINEAR)``, transforms/transform.py ResizeTransform); the reference's transform classes derive from
 fvcore, which is not installed here, so their numerics are pinned by that shared PIL call, not by a fixture (parity unpinned).
+
+``DATALOADER.DEVICE_RESIZE`` (default off) moves resize, flip, HWC -> CHW and RGB -> BGR into ONE HIP launch per batch on the staging
+stream (``cddmsl_resize_batch_u8``, Pillow's resample bit for bit): the mapper then only decodes and records what is left to do, and
+``DeviceBatches`` hands out the same bytes as the host path.
 """
 import os
 import xml.etree.ElementTree as ET
@@ -82,6 +86,9 @@ def resize_image(img, newh, neww):
     return np.asarray(Image.fromarray(img).resize((neww, newh), Image.BILINEAR))
 
 
+DEVICE_RESIZE_KEY = "device_resize"      # a sample's record of the resize / mirror / channel reversal still to be done on the device
+
+
 class DatasetMapper:
     """Dataset dict -> model input dict; the random draws (short-edge choice, flip) come from ``rng``."""
 
@@ -91,13 +98,15 @@ class DatasetMapper:
         self.min_sizes = list(i.MIN_SIZE_TRAIN) if is_train else [i.MIN_SIZE_TEST]
         self.max_size = i.MAX_SIZE_TRAIN if is_train else i.MAX_SIZE_TEST
         self.flip = is_train and i.get("RANDOM_FLIP", "horizontal") == "horizontal"
+        self.device_resize = bool(cfg.DATALOADER.get("DEVICE_RESIZE", False))
         self.rng = rng or np.random.RandomState()
 
     def __call__(self, d: Dict) -> Dict:
         d = dict(d)
-        img = read_image(d["file_name"], self.fmt)
+        fmt = "RGB" if self.device_resize else self.fmt            # (the device reverses the channels while it resizes)
+        img = read_image(d["file_name"], fmt)
         assert img.shape[:2] == (d["height"], d["width"]), f"{d['file_name']}: image size differs from its annotation"
-        twin = read_image(d["data_dt_file_name"], self.fmt) if "data_dt_file_name" in d else None
+        twin = read_image(d["data_dt_file_name"], fmt) if "data_dt_file_name" in d else None
         h, w = img.shape[:2]
         size = int(self.rng.choice(self.min_sizes))
         newh, neww = shortest_edge_size(h, w, size, self.max_size) if size else (h, w)
@@ -107,10 +116,23 @@ class DatasetMapper:
             a = resize_image(a, newh, neww)
             return a[:, ::-1] if do_flip else a
 
-        d["image"] = torch.from_numpy(np.ascontiguousarray(tf(img).transpose(2, 0, 1)))
         if twin is not None:
             assert twin.shape[:2] == (h, w), f"{d['data_dt_file_name']}: twin size differs"
-            d["image_trgt"] = torch.from_numpy(np.ascontiguousarray(tf(twin).transpose(2, 0, 1)))
+        if self.device_resize:
+            # DATALOADER.DEVICE_RESIZE: the decoded [h, w, 3] RGB arrays go on as they are, with a record of what is still to do;
+            # DeviceBatches resizes, mirrors, reverses and transposes the whole batch in one kernel launch.  Only the coefficient
+            # tables of the changed axes are built here -- in the worker, where the PIL resize used to run
+            from .resample import packed_table
+            d[DEVICE_RESIZE_KEY] = {"size": (newh, neww), "flip": do_flip, "reverse_channels": self.fmt == "BGR",
+                                    "xtab": packed_table(w, neww) if neww != w else None,
+                                    "ytab": packed_table(h, newh) if newh != h else None}
+            d["image"] = torch.from_numpy(np.array(img))           # (a copy: PIL hands out a read-only buffer)
+            if twin is not None:
+                d["image_trgt"] = torch.from_numpy(np.array(twin))
+        else:
+            d["image"] = torch.from_numpy(np.ascontiguousarray(tf(img).transpose(2, 0, 1)))
+            if twin is not None:
+                d["image_trgt"] = torch.from_numpy(np.ascontiguousarray(tf(twin).transpose(2, 0, 1)))
         anns = d.pop("annotations", None)
         if not self.is_train or anns is None:
             return d
@@ -167,7 +189,9 @@ def aspect_ratio_batches(stream, batch_size):
     """data/common.py:152-186: two buckets (w > h, w <= h); a bucket is emitted when it holds batch_size samples"""
     buckets = ([], [])
     for d in stream:
-        b = buckets[0 if d["image"].shape[2] > d["image"].shape[1] else 1]
+        # (a sample still to be resized on the device is bucketed by its target size: what this sees after a host resize)
+        h, w = d[DEVICE_RESIZE_KEY]["size"] if DEVICE_RESIZE_KEY in d else d["image"].shape[1:]
+        b = buckets[0 if w > h else 1]
         b.append(d)
         if len(b) == batch_size:
             yield b[:]
@@ -237,16 +261,28 @@ class DeviceBatches:
         return torch.empty(self._cap, dtype=torch.uint8, pin_memory=True)
 
     def _stage(self, batch):
-        """host batch -> (device batch, event, device buffer): every image, twin, box and class tensor of the batch packed into one
-        pinned buffer (256-byte slots) and sent with ONE copy"""
+        """host batch -> (device batch, event, device buffers): every image, twin, box and class tensor of the batch packed into one
+        pinned buffer (256-byte slots) and sent with ONE copy.  Samples that carry a DATALOADER.DEVICE_RESIZE record arrive as decoded
+        [h, w, 3] images: those and their coefficient tables (one per distinct (in, out) axis pair of the batch) ride in the same
+        copy, and ONE kernel launch on the staging stream resizes / mirrors / transposes them into a second device buffer whose
+        [3, newh, neww] views are handed out; the event is recorded behind the kernel."""
         items = []                                         # (sample index, field, tensor)
+        recs, tabs = {}, {}                                # sample index -> record; (insize, outsize) -> index of that table in items
         for i, d in enumerate(batch):
+            if DEVICE_RESIZE_KEY in d:
+                recs[i] = d[DEVICE_RESIZE_KEY]
             for k in ("image", "image_trgt"):
                 if k in d:
                     items.append((i, k, d[k]))
             if "instances" in d:
                 items.append((i, "gt_boxes", d["instances"].gt_boxes.tensor.contiguous()))
                 items.append((i, "gt_classes", d["instances"].gt_classes.contiguous()))
+        for i, rec in recs.items():
+            h, w = batch[i]["image"].shape[:2]
+            for ax, insize, outsize in (("xtab", w, rec["size"][1]), ("ytab", h, rec["size"][0])):
+                if rec[ax] is not None and (insize, outsize) not in tabs:
+                    tabs[(insize, outsize)] = len(items)
+                    items.append((i, ax, torch.as_tensor(rec[ax][0])))      # (numpy from the mapper, a tensor through DataLoader workers)
         sizes = [(t.numel() * t.element_size() + 255) // 256 * 256 for _, _, t in items]
         buf = self._pinned(sum(sizes))
         off, slots = 0, []
@@ -256,22 +292,43 @@ class DeviceBatches:
                 buf[off:off + nb].view(t.dtype).view(t.shape).copy_(t)
             slots.append((i, k, off, nb, t.dtype, tuple(t.shape)))
             off += n
+        work, res_bytes = [], 0                            # the kernel's item descriptors, and where each result goes
+        for i, k, o, nb, dt, shape in slots:
+            if i in recs and k in ("image", "image_trgt"):
+                rec = recs[i]
+                (newh, neww), (h, w) = rec["size"], shape[:2]
+                assert dt == torch.uint8 and len(shape) == 3 and shape[2] == 3, "a DEVICE_RESIZE sample holds a uint8 [h, w, 3] image"
+                xt = (slots[tabs[(w, neww)]][2] // 4, rec["xtab"][1]) if neww != w else (-1, 0)
+                yt = (slots[tabs[(h, newh)]][2] // 4, rec["ytab"][1]) if newh != h else (-1, 0)
+                work.append((o, res_bytes, h, w, newh, neww, int(rec["flip"]), int(rec["reverse_channels"]), *xt, *yt))
+                res_bytes += (3 * newh * neww + 255) // 256 * 256
+        owned = []
         with torch.cuda.stream(self._stream):
             dev = buf[:max(off, 1)].to(self.device, non_blocking=True)
+            owned.append(dev)
+            if work:
+                from . import hip
+                res = torch.empty(res_bytes, dtype=torch.uint8, device=self.device)
+                hip.resize_batch_u8(dev, res, dev.view(torch.int32) if tabs else None, work)
+                owned.append(res)
             ev = torch.cuda.Event()
             ev.record(self._stream)
         self._busy.append((ev, buf))
-        out = [dict(d) for d in batch]
-        fields = {}
+        out = [{k: v for k, v in d.items() if k != DEVICE_RESIZE_KEY} for d in batch]
+        fields, done = {}, 0
         for i, k, o, nb, dt, shape in slots:
-            v = dev[o:o + nb].view(dt).view(shape)
             if k in ("image", "image_trgt"):
-                out[i][k] = v
-            else:
-                fields.setdefault(i, {})[k] = v
+                if i in recs:
+                    _, ro, _, _, newh, neww = work[done][:6]
+                    out[i][k] = res[ro:ro + 3 * newh * neww].view(3, newh, neww)
+                    done += 1
+                else:
+                    out[i][k] = dev[o:o + nb].view(dt).view(shape)
+            elif k in ("gt_boxes", "gt_classes"):
+                fields.setdefault(i, {})[k] = dev[o:o + nb].view(dt).view(shape)
         for i, f in fields.items():
             out[i]["instances"] = Instances(batch[i]["instances"].image_size, gt_boxes=Boxes(f["gt_boxes"]), gt_classes=f["gt_classes"])
-        return out, ev, [dev]
+        return out, ev, owned
 
     def _run(self):
         import time
@@ -323,8 +380,14 @@ class DeviceBatches:
         return out
 
 
+def _check_device_resize(cfg, device):
+    if cfg.DATALOADER.get("DEVICE_RESIZE", False) and torch.device(device).type != "cuda":
+        raise ValueError(f"DATALOADER.DEVICE_RESIZE resizes in a HIP kernel: the loader's device must be a GPU, not {device!r} (there is no host path behind the switch)")
+
+
 def build_detection_train_loader(cfg, dicts, per_rank_batch, rank=0, world=1, device="cuda", num_workers=None):
     """data/build.py:262-308: mapped infinite stream -> aspect-ratio batches -> device"""
+    _check_device_resize(cfg, device)
     mapper = DatasetMapper(cfg, True, np.random.RandomState(cfg.SEED + rank if cfg.SEED >= 0 else None))
     sampler = TrainingSampler(len(dicts), True, max(cfg.SEED, 0), rank, world)
     nw = cfg.DATALOADER.NUM_WORKERS if num_workers is None else num_workers
@@ -333,11 +396,16 @@ def build_detection_train_loader(cfg, dicts, per_rank_batch, rank=0, world=1, de
     stream = torch.utils.data.DataLoader(ds, batch_size=None, num_workers=nw, prefetch_factor=4, multiprocessing_context="spawn", worker_init_fn=_worker_init) if nw else ds
     # upper bound of a batch's bytes: image + twin, short edge <= max(MIN_SIZE_TRAIN), long edge <= MAX_SIZE_TRAIN
     cap = per_rank_batch * 2 * 3 * (max(cfg.INPUT.MIN_SIZE_TRAIN) or cfg.INPUT.MAX_SIZE_TRAIN) * cfg.INPUT.MAX_SIZE_TRAIN + (per_rank_batch << 16)
+    if mapper.device_resize:
+        # the ORIGINALS are uploaded (larger than the resized images where the dataset is downscaled), plus a few tables: sized from
+        # the dataset's own image sizes; a batch beyond it makes the pinned pool grow
+        cap = per_rank_batch * (2 * 3 * max((d.get("height", 0) * d.get("width", 0) for d in dicts), default=0) + (1 << 17))
     return DeviceBatches(aspect_ratio_batches(stream, per_rank_batch), device, max_batch_bytes=cap)
 
 
 def build_detection_test_loader(cfg, dicts, batch_size=1, rank=0, world=1, device="cuda"):
     """data/build.py:311-357: in order, sharded over ranks (InferenceSampler), annotations dropped by the mapper"""
+    _check_device_resize(cfg, device)
     mapper = DatasetMapper(cfg, False)
     n = len(dicts)
     shard = (n + world - 1) // world

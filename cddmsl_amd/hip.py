@@ -40,6 +40,7 @@ def _L():
         L.cddmsl_preprocess_batch.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, vp]
         L.cddmsl_preprocess224_batch.argtypes = [vp, vp, vp, ci, vp] + [ci] * 8 + [vp, vp, ci, vp]
         L.cddmsl_tta_view.argtypes = [vp] + [ci] * 4 + [vp, vp, vp, ci] * 2 + [vp, ci, ci, ci] * 2 + [ci, vp, vp, ci, ci, vp]
+        L.cddmsl_resize_batch_u8.argtypes = [vp, c_long, vp, c_long, vp, c_long, vp, ci, vp]
         L.cddmsl_avgpool2_fwd.argtypes = [vp, vp] + [ci] * 5 + [vp]
         L.cddmsl_avgpool2_bwd.argtypes = [vp] * 4 + [ci] * 5 + [vp]
         L.cddmsl_avgpool2_bwd_q8.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 4
@@ -598,44 +599,7 @@ def preprocess224(images_u8, Hp, Wp, mean, std, dtype, size=224, Cp=None):
     return out
 
 
-_RESAMPLE_BITS = 22          # Pillow's PRECISION_BITS (ImagingResample, 8 bits per channel)
-_resample_cache = {}
-
-
-def _resample_table(insize, outsize):
-    """Pillow's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for the bilinear filter along one axis -> (lo [out], n [out],
-    k [out, ksize], ksize), int32: output i reads inputs lo[i] .. lo[i] + n[i] - 1 with the weights k[i, :n[i]] (the rest 0).  Computed in
-    double in Pillow's own order of operations -- window from the centre, triangle weight of ``(x + lo - centre + 0.5) * (1 / fs)``, a
-    running sum in tap order, one division per tap, ``int(0.5 + w * 2^22)`` -- because another order moves a coefficient by one and
-    with it pixels.  The kernel only reads these tables."""
-    import math
-
-    import numpy as np
-    key = (int(insize), int(outsize))
-    if key in _resample_cache:
-        return _resample_cache[key]
-    scale = key[0] / key[1]
-    fs = max(scale, 1.0)
-    support = 1.0 * fs                                   # the bilinear filter's support is 1
-    ks = int(math.ceil(support)) * 2 + 1
-    ss = 1.0 / fs
-    center = (np.arange(key[1], dtype=np.float64) + 0.5) * scale
-    lo = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
-    hi = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), key[0])
-    n = hi - lo
-    k = np.zeros((key[1], ks), dtype=np.float64)
-    ww = np.zeros(key[1], dtype=np.float64)
-    for t in range(ks):
-        a = np.abs(((t + lo) - center + 0.5) * ss)
-        k[:, t] = np.where((a < 1.0) & (t < n), 1.0 - a, 0.0)
-        ww = ww + k[:, t]
-    nz = ww != 0.0
-    k[nz] = k[nz] / ww[nz, None]
-    ki = np.trunc(0.5 + k * float(1 << _RESAMPLE_BITS)).astype(np.int32)       # bilinear weights are never negative
-    if len(_resample_cache) >= 256:
-        _resample_cache.clear()
-    _resample_cache[key] = (lo.astype(np.int32), n.astype(np.int32), ki, ks)
-    return _resample_cache[key]
+from .resample import resample_table as _resample_table  # noqa: E402  (pure numpy: the loader's workers build the same tables)
 
 
 def tta_view_list(sizes, flip):
@@ -693,6 +657,29 @@ def tta_views(image_u8, sizes, flip, mean, std, dtype, batch_size=3, div255=True
                                    ptr(t1), (v0 + 1) % batch_size if flip else 0, t1.shape[1] if flip else 0, t1.shape[2] if flip else 0,
                                    Cp, m, s, int(div255), DT[dtype], stream_ptr()), "cddmsl_tta_view")
     return groups
+
+
+class ResizeItem(ctypes.Structure):
+    """``cddmsl_resize_item`` of include/cddmsl_hip.h"""
+    _fields_ = [("src_off", c_long), ("dst_off", c_long)] + [(k, c_int) for k in (
+        "h", "w", "newh", "neww", "flip", "reverse_channels", "xtab", "xks", "ytab", "yks")]
+
+
+def resize_batch_u8(src, dst, tab, items):
+    """The loader's resize + mirror for a whole batch in one launch (a launch per 32 items beyond that), on the current stream.
+    ``src``: device uint8 buffer holding the decoded images, interleaved [h, w, 3]; ``dst``: device uint8 buffer that receives the
+    planar [3, newh, neww] results; ``tab``: device int32 buffer of ``resample.packed_table`` tables (None when no axis changes);
+    ``items``: one ``(src_off, dst_off, h, w, newh, neww, flip, reverse_channels, xtab, xks, ytab, yks)`` per image -- byte offsets
+    into ``src`` / ``dst``, int32 positions into ``tab`` with -1 for an axis that keeps its size.  Bit-equal to
+    ``PIL.Image.resize((neww, newh), BILINEAR)``, then ``[:, ::-1]`` with flip and ``[:, :, ::-1]`` with reverse_channels, transposed
+    to CHW.  The library checks every item against the buffer sizes before it launches; a refusal raises."""
+    require_cuda(src, dst, tab)
+    assert src.dtype == torch.uint8 and dst.dtype == torch.uint8 and src.is_contiguous() and dst.is_contiguous()
+    assert tab is None or (tab.dtype == torch.int32 and tab.is_contiguous())
+    arr = (ResizeItem * max(len(items), 1))(*[ResizeItem(*(int(v) for v in it)) for it in items])
+    check(_L().cddmsl_resize_batch_u8(ptr(src), src.numel(), ptr(dst), dst.numel(), ptr(tab), 0 if tab is None else tab.numel(),
+                                      ctypes.cast(arr, c_void_p), len(items), stream_ptr()), "cddmsl_resize_batch_u8")
+    return dst
 
 
 @_timed("avgpool2_fwd")

@@ -429,6 +429,22 @@ int cddmsl_preprocess224_batch(const unsigned char* const* imgs, const int* hs, 
 int cddmsl_tta_view(const unsigned char* img, int h, int w, int newh, int neww, const int* xlo, const int* xn, const int* xk, int xks,
                     const int* ylo, const int* yn, const int* yk, int yks, void* out0, int n0, int Hp0, int Wp0, void* out1, int n1,
                     int Hp1, int Wp1, int Cp, const float* mean3, const float* std3, int div255, int dtype, void* stream);
+/* the loader's ResizeShortestEdge + RandomFlip for a whole batch in ONE launch (loader_resize.hip; a launch per 32 items beyond that):
+ * item i reads the uint8 image [h][w][3] (interleaved, as PIL decodes it) at byte src_off of src and writes Pillow's bilinear resize
+ * to (newh, neww) -- the arithmetic of cddmsl_tta_view, bit for bit -- as planar uint8 [3][newh][neww] at byte dst_off of dst; with
+ * flip column x is written to column neww - 1 - x, with reverse_channels plane c takes source channel 2 - c (INPUT.FORMAT BGR).
+ * xtab / ytab: position (in int32 elements) of the axis' table in tab [tab_len], laid out lo [out] | n [out] | k [out][ks] with
+ * ks = xks / yks (cddmsl_amd/resample.py); -1 for an axis whose size does not change, which is copied.  Items may share tables (an
+ * image and its twin do).  The descriptors are a HOST array.  Every item is checked before the first launch: positive sizes,
+ * offset + extent inside src_bytes / dst_bytes, a table exactly where an axis changes and inside tab_len; anything else is
+ * CDDMSL_ERR_ARG with nothing launched.  count == 0 succeeds with nothing launched.  Bytes of dst outside the items' extents are
+ * not written. */
+typedef struct cddmsl_resize_item {
+  long src_off, dst_off;
+  int h, w, newh, neww, flip, reverse_channels, xtab, xks, ytab, yks;
+} cddmsl_resize_item;
+int cddmsl_resize_batch_u8(const unsigned char* src, long src_bytes, unsigned char* dst, long dst_bytes, const int* tab, long tab_len,
+                           const cddmsl_resize_item* items, int count, void* stream);
 int cddmsl_avgpool2_fwd(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
 int cddmsl_avgpool2_bwd(const void* dy, const void* mask, const void* add, void* dx, int N, int H, int W, int C, int dtype,
                         void* stream);

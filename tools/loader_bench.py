@@ -12,6 +12,9 @@ bench.py times the step on synthetic batches already resident in HBM; this tool 
      buckets), against the same trainer on synthetic 800x1333 batches: ms/step, samples/s, allocator state after iteration 10
      and at the end.
 
+``--device-resize`` runs 2. and 3. with DATALOADER.DEVICE_RESIZE: the workers only decode, and the staging thread's one kernel launch
+per batch (cddmsl_resize_batch_u8) resizes, mirrors and transposes on the GPU -- the same bytes reach the model.
+
 usage (GPU box): python tools/loader_bench.py --iters 50 > profiles/r03_loader.txt
 """
 import argparse
@@ -67,12 +70,15 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--workers", default="0,4,8,12")
     ap.add_argument("--loader-batches", type=int, default=12)
+    ap.add_argument("--device-resize", action="store_true", help="DATALOADER.DEVICE_RESIZE: resize / flip on the GPU in the staging thread")
+    ap.add_argument("--skip-step", action="store_true", help="loader alone: skip the training-step measurements")
     args = ap.parse_args()
     import bench
     from cddmsl_amd import data, engine, synthetic
     from cddmsl_amd.evaluation import VOC_CLASS_NAMES
     cfg = bench.make_cfg("bf16")
     cfg.MODEL.DEVICE = "cuda:0"
+    cfg.merge_from_list(["DATALOADER.DEVICE_RESIZE", bool(args.device_resize)])
     engine.limit_host_threads()       # as build_trainer does: the box grants ~16 CPUs, torch's default intra-op pool has one thread per logical CPU
     root = tempfile.mkdtemp(prefix="cddmsl_voc_")
     t0 = time.perf_counter()
@@ -80,7 +86,9 @@ def main():
     print(f"# synthetic VOC tree: {args.images} JPEG pairs (500x375 / 375x500) under {root}, written in {time.perf_counter() - t0:.1f} s")
     dicts = data.load_voc_instances(base, "trainval", VOC_CLASS_NAMES, dt_data="clipart")
     print(f"# INPUT.MIN_SIZE_TRAIN {tuple(cfg.INPUT.MIN_SIZE_TRAIN)} max {cfg.INPUT.MAX_SIZE_TRAIN}, flip {cfg.INPUT.RANDOM_FLIP}; host: {os.cpu_count()} logical CPUs ({bench.cpu_model_name()})")
-    print("# 1. loader alone (decode 2 JPEGs + resize both + flip + batch + pin + H2D), samples/s after 2 warm-up batches")
+    print(f"# DATALOADER.DEVICE_RESIZE {cfg.DATALOADER.DEVICE_RESIZE}")
+    print("# 1. loader alone (decode 2 JPEGs + resize both + flip + batch + pin + H2D" + (" of the originals + one resize launch per batch" if args.device_resize else "")
+          + "), samples/s after 2 warm-up batches")
     rates = {}
     for nw in [int(x) for x in args.workers.split(",")]:
         ld = data.build_detection_train_loader(cfg, dicts, args.batch, 0, 1, cfg.MODEL.DEVICE, num_workers=nw)
@@ -102,6 +110,8 @@ def main():
         ld.close()
         del ld
     best = max(rates, key=rates.get)
+    if args.skip_step:
+        return
 
     def run(loader, tag):
         tr = engine.build_trainer(cfg, args.batch, 800, 1333)
