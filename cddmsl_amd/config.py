@@ -147,7 +147,7 @@ def get_cfg():
                        "DEVICE_RESIZE": False},
         "SOLVER": {"IMS_PER_BATCH": 16, "BASE_LR": 0.001, "MOMENTUM": 0.9, "NESTEROV": False, "WEIGHT_DECAY": 0.0001,
                    "WEIGHT_DECAY_NORM": 0.0, "GAMMA": 0.1, "STEPS": (30000,), "MAX_ITER": 40000, "WARMUP_FACTOR": 1.0 / 1000,
-                   "WARMUP_ITERS": 1000, "WARMUP_METHOD": "linear", "CHECKPOINT_PERIOD": 5000, "BIAS_LR_FACTOR": 1.0,
+                   "WARMUP_ITERS": 1000, "WARMUP_METHOD": "linear", "LR_SCHEDULER_NAME": "WarmupMultiStepLR", "CHECKPOINT_PERIOD": 5000, "BIAS_LR_FACTOR": 1.0,
                    "WEIGHT_DECAY_BIAS": 0.0001, "REFERENCE_WORLD_SIZE": 0,
                    "CLIP_GRADIENTS": {"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0},
                    "AMP": {"ENABLED": False}},

@@ -658,6 +658,103 @@ __global__ void k_sgd(SgdBatch b, const float* norms, float lr, float momentum, 
   }
 }
 
+// ---------------------------------------------------------------- grouped SGD: per-tensor lr / weight decay, Nesterov, value or L2 / L1 / inf-norm clip
+// (solver/build.py:23-40,113-217 around torch.optim.SGD).  The batch travels by value: 80 items of 40 bytes + the scalars = 3236 bytes of
+// kernel arguments, about what k_sgd's 96 items of 32 bytes take (3104), under the 4 KB limit with the hidden arguments counted.
+struct SgdGItem { float* p; const float* g; float* m; long n; float lr, wd; };
+constexpr int SGDG_MAX = 80;
+struct SgdGBatch { SgdGItem it[SGDG_MAX]; int count; };
+static_assert(sizeof(SgdGBatch) + 8 + 5 * 4 + 256 <= 4096, "SgdGBatch + scalars + hidden arguments exceed the kernel-argument limit");
+enum { SGD_CLIP_NONE = 0, SGD_CLIP_VALUE = 1, SGD_CLIP_L2 = 2, SGD_CLIP_L1 = 3, SGD_CLIP_INF = 4 };
+
+// reduction pass of the norm modes, k_sqnorm's structure: norms[tensor] += sum g^2 (L2) or sum |g| (L1); for the inf norm an integer max over
+// the bit patterns of |g| (absmax_bits: a NaN orders above inf, so it reaches the result as torch's max does), combined with a vector atomic max
+template <int MODE>
+__global__ void k_gnorm(SgdGBatch b, float* norms) {
+  const SgdGItem& t = b.it[blockIdx.y];
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+  float s = 0.f;
+  unsigned mx = 0u;
+  long done = 0;
+  if ((((size_t)t.g) & 15) == 0) {
+    const long n4 = t.n >> 2;
+    for (long i = tid; i < n4; i += nth) {
+      const float4 g = ((const float4*)t.g)[i];
+      if (MODE == SGD_CLIP_L2) s += (g.x * g.x + g.y * g.y) + (g.z * g.z + g.w * g.w);
+      else if (MODE == SGD_CLIP_L1) s += (fabsf(g.x) + fabsf(g.y)) + (fabsf(g.z) + fabsf(g.w));
+      else mx = absmax_bits(absmax_bits(absmax_bits(absmax_bits(mx, g.x), g.y), g.z), g.w);
+    }
+    done = n4 << 2;
+  }
+  for (long i = done + tid; i < t.n; i += nth) {
+    const float g = t.g[i];
+    if (MODE == SGD_CLIP_L2) s += g * g;
+    else if (MODE == SGD_CLIP_L1) s += fabsf(g);
+    else mx = absmax_bits(mx, g);
+  }
+  if (MODE == SGD_CLIP_INF) {
+    mx = wave_max_u(mx);
+    __shared__ unsigned redu[4];
+    if ((threadIdx.x & 63) == 0) redu[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned a = redu[0] > redu[1] ? redu[0] : redu[1], c = redu[2] > redu[3] ? redu[2] : redu[3];
+      atomicMax((unsigned*)norms + blockIdx.y, a > c ? a : c);
+    }
+  } else {
+    s = wave_sum(s);
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(norms + blockIdx.y, red[0] + red[1] + red[2] + red[3]);
+  }
+}
+
+// torch.optim.SGD (dampening 0) on one element.  CLIP: 0 = g as it is, 1 = clamped to [-c, c], 2 = times the tensor's coefficient c.
+// The comparisons keep a NaN gradient NaN, as torch.clamp does (fminf / fmaxf would return the other operand).
+template <int CLIP>
+__device__ __forceinline__ void sgdg_one(float& p, float g, float& m, float c, float lr, float wd, float momentum, int nesterov, int first_step) {
+  if (CLIP == 1) g = g < -c ? -c : (g > c ? c : g);
+  if (CLIP == 2) g = g * c;
+  const float d = g + wd * p;
+  m = first_step ? d : momentum * m + d;
+  const float step = nesterov ? d + momentum * m : m;
+  p = p - lr * step;
+}
+template <int CLIP>
+__global__ void k_sgd_groups(SgdGBatch b, const float* norms, float momentum, int nesterov, int clip_mode, float clip, int first_step) {
+  const SgdGItem& t = b.it[blockIdx.y];
+  const float lr = t.lr, wd = t.wd;
+  float c = clip;
+  if (CLIP == 2) {
+    const float ws = norms[blockIdx.y], nrm = clip_mode == SGD_CLIP_L2 ? sqrtf(ws) : ws;
+    c = clip / (nrm + 1e-6f);          // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1.0); a NaN norm stays NaN
+    c = c > 1.0f ? 1.0f : c;
+  }
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+  long done = 0;
+  if (((((size_t)t.g) | ((size_t)t.p) | ((size_t)t.m)) & 15) == 0) {
+    const long n4 = t.n >> 2;
+    for (long i = tid; i < n4; i += nth) {
+      float4 p = ((float4*)t.p)[i], m = first_step ? make_float4(0.f, 0.f, 0.f, 0.f) : ((float4*)t.m)[i];
+      const float4 g = ((const float4*)t.g)[i];
+      sgdg_one<CLIP>(p.x, g.x, m.x, c, lr, wd, momentum, nesterov, first_step);
+      sgdg_one<CLIP>(p.y, g.y, m.y, c, lr, wd, momentum, nesterov, first_step);
+      sgdg_one<CLIP>(p.z, g.z, m.z, c, lr, wd, momentum, nesterov, first_step);
+      sgdg_one<CLIP>(p.w, g.w, m.w, c, lr, wd, momentum, nesterov, first_step);
+      ((float4*)t.m)[i] = m;
+      ((float4*)t.p)[i] = p;
+    }
+    done = n4 << 2;
+  }
+  for (long i = done + tid; i < t.n; i += nth) {
+    float p = t.p[i], m = first_step ? 0.f : t.m[i];
+    sgdg_one<CLIP>(p, t.g[i], m, c, lr, wd, momentum, nesterov, first_step);
+    t.m[i] = m;
+    t.p[i] = p;
+  }
+}
+
 inline unsigned gsz(long n, int per = 256, long cap = -1) {
   // default cap on the grid of the grid-stride streaming kernels.  tools/hbm_probe.hip: a plain 16-bytes-per-thread copy runs 6.3 TB/s as a
   // ONE-SHOT grid (what ATen's elementwise kernels do) against 4.8-5.0 with 8-32 blocks per CU looping; on these kernels (more index
@@ -924,6 +1021,39 @@ extern "C" int cddmsl_sgd_clip_step(float** params, const float** grads, float**
     unsigned gx = gsz(mx, 256 * 8, 256);
     k_sqnorm<<<dim3(gx, b.count), dim3(256), 0, st>>>(b, norm_ws + base);
     k_sgd<<<dim3(gx, b.count), dim3(256), 0, st>>>(b, norm_ws + base, lr, momentum, wd, clip, first_step);
+  }
+  return launch_status();
+}
+
+// The grouped step: lrs / wds are host arrays like the pointer arrays; tensors are batched SGDG_MAX per launch (modes 0, 1: the update alone,
+// g read once) or launch pair (modes 2-4: norm_ws[i] = sum g^2, sum |g| or max |g|, then the update).
+extern "C" int cddmsl_sgd_step_groups(float** params, const float** grads, float** moms, const long* sizes, const float* lrs,
+                                      const float* wds, int count, float* norm_ws, float momentum, int nesterov, int clip_mode,
+                                      float clip_value, int first_step, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (count < 0 || clip_mode < SGD_CLIP_NONE || clip_mode > SGD_CLIP_INF || (nesterov != 0 && nesterov != 1)) return CDDMSL_ERR_ARG;
+  for (int base = 0; base < count; base += SGDG_MAX) {
+    SgdGBatch b;
+    b.count = count - base < SGDG_MAX ? count - base : SGDG_MAX;
+    long mx = 0;
+    for (int i = 0; i < b.count; ++i) {
+      b.it[i].p = params[base + i]; b.it[i].g = grads[base + i]; b.it[i].m = moms[base + i]; b.it[i].n = sizes[base + i];
+      b.it[i].lr = lrs[base + i]; b.it[i].wd = wds[base + i];
+      if (sizes[base + i] > mx) mx = sizes[base + i];
+    }
+    const dim3 grid(gsz(mx, 256 * 8, 256), b.count), blk(256);
+    float* ws = norm_ws + base;
+    if (clip_mode >= SGD_CLIP_L2) {
+      if (hipMemsetAsync(ws, 0, sizeof(float) * b.count, st) != hipSuccess) return CDDMSL_ERR_LAUNCH;
+      if (clip_mode == SGD_CLIP_L2) k_gnorm<SGD_CLIP_L2><<<grid, blk, 0, st>>>(b, ws);
+      else if (clip_mode == SGD_CLIP_L1) k_gnorm<SGD_CLIP_L1><<<grid, blk, 0, st>>>(b, ws);
+      else k_gnorm<SGD_CLIP_INF><<<grid, blk, 0, st>>>(b, ws);
+      k_sgd_groups<2><<<grid, blk, 0, st>>>(b, ws, momentum, nesterov, clip_mode, clip_value, first_step);
+    } else if (clip_mode == SGD_CLIP_VALUE) {
+      k_sgd_groups<1><<<grid, blk, 0, st>>>(b, ws, momentum, nesterov, clip_mode, clip_value, first_step);
+    } else {
+      k_sgd_groups<0><<<grid, blk, 0, st>>>(b, ws, momentum, nesterov, clip_mode, clip_value, first_step);
+    }
   }
   return launch_status();
 }

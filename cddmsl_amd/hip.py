@@ -56,6 +56,7 @@ def _L():
         L.cddmsl_relu_bwd.argtypes = [vp, vp, vp, c_long, ci, ci, vp]
         L.cddmsl_colsum.argtypes = [vp, vp, c_long, ci, ci, ci, vp]
         L.cddmsl_sgd_clip_step.argtypes = [vp] * 4 + [ci, vp] + [cf] * 4 + [ci, vp]
+        L.cddmsl_sgd_step_groups.argtypes = [vp] * 6 + [ci, vp, cf, ci, ci, cf, ci, vp]
         L.cddmsl_roi_align_forward.argtypes = [vp] * 5 + [ci] * 7 + [cf, ci, ci, ci, vp]
         L.cddmsl_roi_align_backward.argtypes = [vp] * 7 + [ci] * 7 + [cf, ci, ci, ci, vp]
         L.cddmsl_nms_anyorder.argtypes = [vp] * 4 + [ci, cf, vp, vp, vp]
@@ -975,6 +976,34 @@ def sgd_clip_step(params, grads, moms, norm_ws, lr, momentum, wd, clip, first_st
     S = (c_long * n)(*[p.numel() for p in params])
     check(_L().cddmsl_sgd_clip_step(P, G, M, S, n, ptr(norm_ws), lr, momentum, wd, clip, int(first_step), stream_ptr()),
           "cddmsl_sgd_clip_step")
+
+
+SGD_CLIP_MODES = {"none": 0, "value": 1, "l2": 2, "l1": 3, "inf": 4}
+
+
+@_timed("sgd_step_groups")
+def sgd_step_groups(params, grads, moms, norm_ws, lrs, wds, momentum, nesterov, clip_mode, clip_value, first_step):
+    """torch.optim.SGD with one lr and one weight decay per tensor, optional Nesterov momentum and per-parameter gradient clipping
+    over a list of f32 tensors (solver/build.py:23-40,113-217).  ``clip_mode``: SGD_CLIP_MODES (0 none, 1 value, 2 / 3 / 4 the
+    L2 / L1 / inf norm); the norm modes leave sum g^2, sum |g| or max |g| of tensor i in ``norm_ws[i]``."""
+    n = len(params)
+    assert len(lrs) == n and len(wds) == n, "one lr and one weight decay per tensor"
+    if n == 0:
+        return
+    require_cuda(*params, *grads, *moms, norm_ws)
+    assert len(grads) == n and len(moms) == n
+    assert norm_ws.dtype == torch.float32 and norm_ws.is_contiguous() and norm_ws.numel() >= n, "norm_ws holds one f32 per tensor"
+    for p, g, m in zip(params, grads, moms):
+        assert p.dtype == g.dtype == m.dtype == torch.float32
+        assert same_layout(p, g) and same_layout(p, m), "param/grad/momentum must share a memory layout"
+    P = (c_void_p * n)(*[p.data_ptr() for p in params])
+    G = (c_void_p * n)(*[g.data_ptr() for g in grads])
+    M = (c_void_p * n)(*[m.data_ptr() for m in moms])
+    S = (c_long * n)(*[p.numel() for p in params])
+    LR = (c_float * n)(*lrs)
+    WD = (c_float * n)(*wds)
+    check(_L().cddmsl_sgd_step_groups(P, G, M, S, LR, WD, n, ptr(norm_ws), momentum, int(nesterov), int(clip_mode), clip_value,
+                                      int(first_step), stream_ptr()), "cddmsl_sgd_step_groups")
 
 
 # ------------------------------------------------------------------------------------------------ RoIAlign

@@ -1,41 +1,145 @@
-"""Optimizer / LR schedule of the hot path -- detectron2/solver/build.py:43-130,220-262, solver/lr_scheduler.py:17-129.
+"""Optimizer / LR schedule of the hot path -- detectron2/solver/build.py:23-262, solver/lr_scheduler.py:17-116.
 
-``ClippedSGD`` = SGD(momentum 0.9, wd 1e-4) with *per-parameter* L2-norm clipping to 5.0 (solver/build.py:59-67,104),
-run as ONE fused multi-tensor HIP launch pair (norms, update) instead of ~120 tensors x (norm + clip + update).
+``ClippedSGD`` = torch.optim.SGD over one param group per parameter (``get_default_optimizer_params``) with the reference's
+*per-parameter* gradient clipping (solver/build.py:23-110), run as ONE fused multi-tensor HIP launch family instead of ~120
+tensors x (norm + clip + update).  The configuration every shipped YAML uses -- one lr and one weight decay for all parameters, no
+Nesterov, clipping off or by L2 norm -- runs through ``hip.sgd_clip_step``; every other one through ``hip.sgd_step_groups``.
 """
+import math
+
 import torch
 
 from . import hip, layers
 
+# the torch.nn normalisation layers whose parameters take SOLVER.WEIGHT_DECAY_NORM (solver/build.py:188-200)
+NORM_MODULE_TYPES = (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d, torch.nn.BatchNorm3d, torch.nn.SyncBatchNorm, torch.nn.GroupNorm,
+                     torch.nn.InstanceNorm1d, torch.nn.InstanceNorm2d, torch.nn.InstanceNorm3d, torch.nn.LayerNorm,
+                     torch.nn.LocalResponseNorm)
+LR_SCHEDULERS = ("WarmupMultiStepLR", "WarmupCosineLR")
+
+
+def _sched(s, name, it):
+    """the schedule below the warm-up at iteration ``it``: MultiStepParamScheduler / CosineParamScheduler(1, 0)"""
+    if name == "WarmupCosineLR":
+        return 0.5 * (1.0 + math.cos(math.pi * it / s.MAX_ITER))
+    steps = [x for x in s.STEPS if x <= s.MAX_ITER]
+    return s.GAMMA ** sum(1 for x in steps if it >= x)
+
+
+def lr_multiplier(cfg, it):
+    """WarmupParamScheduler(MultiStepParamScheduler | CosineParamScheduler): the factor LRMultiplier puts on every group's
+    initial lr (solver/build.py:220-262, lr_scheduler.py:37-49)"""
+    s = cfg.SOLVER
+    name = s.get("LR_SCHEDULER_NAME", "WarmupMultiStepLR")
+    if name not in LR_SCHEDULERS:
+        raise ValueError("Unknown LR scheduler: {}".format(name))
+    if s.WARMUP_METHOD not in ("linear", "constant"):
+        raise ValueError("Unknown warmup method: {}".format(s.WARMUP_METHOD))
+    warm = min(s.WARMUP_ITERS, s.MAX_ITER)      # warm-up ends at min(WARMUP_ITERS / MAX_ITER, 1) of the run
+    mult = _sched(s, name, it)
+    if it < warm:
+        start = s.WARMUP_FACTOR * _sched(s, name, 0)
+        if s.WARMUP_METHOD == "constant":
+            return start
+        end = _sched(s, name, warm)
+        a = it / warm
+        mult = start * (1 - a) + end * a
+    return mult
+
 
 def lr_at(cfg, it):
-    """WarmupParamScheduler(MultiStepParamScheduler) x LRMultiplier; KAT tests/test_scheduler.py:35-43."""
-    s = cfg.SOLVER
-    steps = [x for x in s.STEPS if x <= s.MAX_ITER]
-    mult = s.GAMMA ** sum(1 for x in steps if it >= x)
-    if it < s.WARMUP_ITERS:
-        end = s.GAMMA ** sum(1 for x in steps if s.WARMUP_ITERS >= x)
-        a = it / s.WARMUP_ITERS
-        mult = s.WARMUP_FACTOR * (1 - a) + end * a
-    return s.BASE_LR * mult
+    """base learning rate at iteration ``it``; KAT tests/test_scheduler.py:14-68."""
+    return cfg.SOLVER.BASE_LR * lr_multiplier(cfg, it)
+
+
+def get_default_optimizer_params(model, base_lr=None, weight_decay=None, weight_decay_norm=None, bias_lr_factor=1.0,
+                                 weight_decay_bias=None, overrides=None):
+    """One param group per trainable parameter, in ``model.parameters()`` order, with the reference's rules (solver/build.py:133-217):
+    ``weight_decay_norm`` for the parameters of torch.nn normalisation layers, then ``overrides[name]`` for parameters called
+    ``name`` inside their module; the "bias" override is made of ``bias_lr_factor`` (when not 1) and ``weight_decay_bias``.
+    A parameter shared between modules appears once, a frozen one not at all."""
+    overrides = dict(overrides or {})
+    defaults = {}
+    if base_lr is not None:
+        defaults["lr"] = base_lr
+    if weight_decay is not None:
+        defaults["weight_decay"] = weight_decay
+    bias = {}
+    if bias_lr_factor is not None and bias_lr_factor != 1.0:
+        if base_lr is None:
+            raise ValueError("bias_lr_factor requires base_lr")
+        bias["lr"] = base_lr * bias_lr_factor
+    if weight_decay_bias is not None:
+        bias["weight_decay"] = weight_decay_bias
+    if bias:
+        if "bias" in overrides:
+            raise ValueError("Conflicting overrides for 'bias'")
+        overrides["bias"] = bias
+    groups, seen = [], set()
+    for module in model.modules():
+        for name, p in module.named_parameters(recurse=False):
+            if not p.requires_grad or id(p) in seen:
+                continue
+            seen.add(id(p))
+            hyper = dict(defaults)
+            if weight_decay_norm is not None and isinstance(module, NORM_MODULE_TYPES):
+                hyper["weight_decay"] = weight_decay_norm
+            hyper.update(overrides.get(name, {}))
+            groups.append({"params": [p], **hyper})
+    return groups
+
+
+def _clip_mode(cg):
+    """SOLVER.CLIP_GRADIENTS -> (hip.SGD_CLIP_MODES value, clip value); solver/build.py:18-40"""
+    if not cg.ENABLED:
+        return hip.SGD_CLIP_MODES["none"], float("inf")
+    if cg.CLIP_TYPE not in ("value", "norm"):
+        raise ValueError("{!r} is not a valid GradientClipType".format(cg.CLIP_TYPE))
+    if cg.CLIP_TYPE == "value":
+        return hip.SGD_CLIP_MODES["value"], float(cg.CLIP_VALUE)
+    nt = cg.NORM_TYPE
+    if isinstance(nt, str) and nt.strip().lower() in ("inf", ".inf", "+inf", "+.inf", "infinity"):
+        nt = float("inf")
+    if isinstance(nt, bool) or not isinstance(nt, (int, float)) or nt not in (1.0, 2.0, float("inf")):
+        raise ValueError("SOLVER.CLIP_GRADIENTS.NORM_TYPE {!r}: the supported norms are 1.0, 2.0 and inf".format(cg.NORM_TYPE))
+    return hip.SGD_CLIP_MODES[{1.0: "l1", 2.0: "l2"}.get(float(nt), "inf")], float(cg.CLIP_VALUE)
 
 
 class ClippedSGD:
     def __init__(self, params, cfg):
-        self.params = [p for p in params if p.requires_grad]
+        """``params``: parameters (every one at BASE_LR / WEIGHT_DECAY) or param groups as get_default_optimizer_params makes them"""
         s = cfg.SOLVER
         self.cfg = cfg
-        self.momentum, self.wd = s.MOMENTUM, s.WEIGHT_DECAY
-        cg = s.CLIP_GRADIENTS
-        if cg.ENABLED:
-            assert cg.CLIP_TYPE == "norm" and cg.NORM_TYPE == 2.0, "hot path = per-parameter L2-norm clipping (solver/build.py:59-67)"
-            self.clip = cg.CLIP_VALUE
-        else:       # solver/build.py:113-130 builds plain torch.optim.SGD (stock config #1): an infinite clip value = factor 1
-            self.clip = float("inf")
+        self.momentum, self.wd, self.nesterov = s.MOMENTUM, s.WEIGHT_DECAY, bool(s.NESTEROV)
+        if self.nesterov and self.momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.params, self.initial_lr, self.weight_decay = [], {}, {}
+        for g in params:
+            g = g if isinstance(g, dict) else {"params": [g]}
+            for p in g["params"]:
+                if p.requires_grad and id(p) not in self.initial_lr:
+                    self.params.append(p)
+                    self.initial_lr[id(p)] = g.get("lr", s.BASE_LR)
+                    self.weight_decay[id(p)] = g.get("weight_decay", s.WEIGHT_DECAY)
+        self.clip_mode, clip = _clip_mode(s.CLIP_GRADIENTS)
+        modes = hip.SGD_CLIP_MODES
+        # the configuration cddmsl_sgd_clip_step implements: plain SGD (solver/build.py:113-130; an infinite clip value = factor 1)
+        # or per-parameter L2-norm clipping (:59-67), one lr and one weight decay for every parameter
+        self.uniform = (not self.nesterov and self.clip_mode in (modes["none"], modes["l2"])
+                        and all(self.initial_lr[id(p)] == s.BASE_LR and self.weight_decay[id(p)] == s.WEIGHT_DECAY for p in self.params))
+        self.clip = clip
         self.moms = None
         self.norm_ws = None
         self.steps_done = 0
         self.iteration = 0
+
+    @property
+    def param_groups(self):
+        """read-only view in torch.optim's layout, one group per parameter (``lr`` is the one the next step will use)"""
+        mult = lr_multiplier(self.cfg, self.iteration)
+        return tuple({"params": [p], "lr": self.initial_lr[id(p)] * mult, "initial_lr": self.initial_lr[id(p)],
+                      "weight_decay": self.weight_decay[id(p)], "momentum": self.momentum, "nesterov": self.nesterov}
+                     for p in self.params)
 
     def zero_grad(self):
         for p in self.params:
@@ -62,8 +166,14 @@ class ClippedSGD:
             self.norm_ws = torch.zeros(len(self.params), device=self.params[0].device, dtype=torch.float32)
         lr = lr_at(self.cfg, self.iteration)
         with torch.no_grad():
-            hip.sgd_clip_step([p.data for p in ps], [p.grad for p in ps], [self.moms[id(p)] for p in ps], self.norm_ws,
-                              lr, self.momentum, self.wd, self.clip, self.steps_done == 0)
+            if self.uniform:
+                hip.sgd_clip_step([p.data for p in ps], [p.grad for p in ps], [self.moms[id(p)] for p in ps], self.norm_ws,
+                                  lr, self.momentum, self.wd, self.clip, self.steps_done == 0)
+            else:
+                mult = lr_multiplier(self.cfg, self.iteration)      # LRMultiplier: every group's initial lr times one multiplier
+                hip.sgd_step_groups([p.data for p in ps], [p.grad for p in ps], [self.moms[id(p)] for p in ps], self.norm_ws,
+                                    [self.initial_lr[id(p)] * mult for p in ps], [self.weight_decay[id(p)] for p in ps],
+                                    self.momentum, self.nesterov, self.clip_mode, self.clip, self.steps_done == 0)
         self.steps_done += 1
         self.iteration += 1
         layers.bump_weight_version()   # prepared (cast / transposed) weights are stale now
@@ -72,4 +182,7 @@ class ClippedSGD:
 
 
 def build_optimizer(cfg, model):
-    return ClippedSGD(model.parameters(), cfg)
+    s = cfg.SOLVER
+    groups = get_default_optimizer_params(model, base_lr=s.BASE_LR, weight_decay=s.WEIGHT_DECAY, weight_decay_norm=s.WEIGHT_DECAY_NORM,
+                                          bias_lr_factor=s.BIAS_LR_FACTOR, weight_decay_bias=s.WEIGHT_DECAY_BIAS)
+    return ClippedSGD(groups, cfg)

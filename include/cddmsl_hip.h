@@ -466,6 +466,18 @@ int cddmsl_relu_bwd(const void* g, const void* y, void* dx, long numel, int g_f3
 int cddmsl_colsum(const void* x, float* out, long rows, int cols, int period, int dtype, void* stream);
 int cddmsl_sgd_clip_step(float** params, const float** grads, float** moms, const long* sizes, int count, float* norm_ws,
                          float lr, float momentum, float wd, float clip, int first_step, void* stream);
+/* torch.optim.SGD (dampening 0) with one lr and one weight decay PER TENSOR (host arrays lrs / wds of `count` entries, like the
+ * pointer arrays), optional Nesterov momentum and the per-parameter gradient clipping of solver/build.py:23-40.
+ * clip_mode 0: none; 1: value, g clamped to [-clip_value, clip_value] (clip_grad_value_); 2 / 3 / 4: L2 / L1 / inf norm of the
+ * tensor, g *= min(clip_value / (norm + 1e-6), 1) (clip_grad_norm_ on the single tensor).  Per element, in f32:
+ *   d = clip(g) + wd_i p;  buf = first_step ? d : momentum buf + d;  p -= lr_i (nesterov ? d + momentum buf : buf)
+ * buf is always written and not read on the first step.  Modes 2-4 leave sum g^2, sum |g| or max |g| in norm_ws[i], i < count;
+ * modes 0 and 1 do not touch norm_ws.  A NaN gradient element is kept: under every norm (the inf norm included) it makes the
+ * tensor's norm_ws entry, coefficient and parameters NaN, as torch does; other tensors are unaffected.
+ * CDDMSL_ERR_ARG for count < 0, clip_mode outside 0..4 or nesterov outside {0, 1}; count == 0 launches nothing. */
+int cddmsl_sgd_step_groups(float** params, const float** grads, float** moms, const long* sizes, const float* lrs, const float* wds,
+                           int count, float* norm_ws, float momentum, int nesterov, int clip_mode, float clip_value, int first_step,
+                           void* stream);
 
 /* ---- Cityscapes instance boxes (input side, not the training step) -------------------------------------------------------
  * replaces the per-id `inst_image == instance_id` + np.nonzero loop of data/datasets/cityscapes.py:501-540 (from_json=False).
