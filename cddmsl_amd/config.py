@@ -139,7 +139,9 @@ def get_cfg():
                      "OPENSET_TEST_NUM_CLASSES": None, "OPENSET_TEST_TEXT_EMB_PATH": None},
         },
         "INPUT": {"MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR",
-                  "MIN_SIZE_TRAIN_SAMPLING": "choice", "RANDOM_FLIP": "horizontal"},
+                  "MIN_SIZE_TRAIN_SAMPLING": "choice", "RANDOM_FLIP": "horizontal",
+                  # defaults.py:68-73: T.RandomCrop in front of the resize (training mapper only)
+                  "CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]}},
         "DATASETS": {"TRAIN": (), "TEST": ()},
         "DATALOADER": {"NUM_WORKERS": 4, "ASPECT_RATIO_GROUPING": True, "FILTER_EMPTY_ANNOTATIONS": True,
                        # build-specific: ResizeShortestEdge / RandomFlip / HWC -> CHW / RGB -> BGR of the loader's images in one HIP launch per

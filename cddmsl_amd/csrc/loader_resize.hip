@@ -2,13 +2,16 @@
 // for a whole batch in ONE launch: 2N differently sized uint8 images, interleaved [h][w][3] as PIL decodes them -> Pillow's bilinear
 // resize to (newh, neww), bit for bit (resample.h) -> planar [3][newh][neww] uint8, mirrored left-right and / or with the channel
 // order reversed (INPUT.FORMAT BGR) per item.  The host only decodes; what the model receives is byte-identical to the host path.
+// flip is a bit set: bit 0 mirrors the columns (RandomFlip horizontal), bit 1 the rows of each plane (vertical), 3 does both.
 //
 // Work decomposition: one flat grid over the TH x TW output tiles of all items (per-item tile prefix in the by-value descriptor
 // block; a workgroup finds its item with a short uniform scan).  A workgroup stages the horizontally resampled rows of its tile in LDS
 // and runs the vertical pass from there (resample.h), a tile whose rows do not fit recomputes.  Output: a row of a plane starts at an
 // arbitrary byte (neww is arbitrary), so a lane makes one ADDRESS-aligned group of 4 bytes of one plane row: a group that lies
 // inside the tile's span is one 4-byte store, the (at most two) groups at the span's ends are byte stores.  With flip the span is
-// the mirrored column range and a group's bytes read the tile's columns backwards.  Plain vector stores only.
+// the mirrored column range and a group's bytes read the tile's columns backwards; with the row mirror output row y is written to
+// row newh - 1 - y, and since the aligned-group / byte-edge split is taken from the row's destination ADDRESS, only the row index
+// changes.  Plain vector stores only.
 #include "cddmsl_hip.h"
 #include "resample.h"
 
@@ -48,16 +51,21 @@ __global__ void __launch_bounds__(NT) k_resize_batch_u8(RsBatch b, const unsigne
   if (staged) stage_rows<3>(hrow, s, h, w, neww, ax, x0, r0, nrows);
   __syncthreads();
   const int len = (x0 + TW < neww ? x0 + TW : neww) - x0;    // the tile's columns [x0, x0 + len) land on [xd0, xd0 + len) of the output row
-  const int xd0 = t.flip ? neww - x0 - len : x0;
+  const bool fx = t.flip & 1, fy = t.flip & 2;               // block-uniform
+  const int xd0 = fx ? neww - x0 - len : x0;
   const int ny = y0 + TH < newh ? TH : newh - y0;
   unsigned char* out = dst + t.dst_off;
   // a wave makes one output row at a time, all three planes: lane = plane * NG + group (51 of 64 lanes), so the row's window and
   // coefficients are the same addresses across the wave and are read once per group, not once per pixel
   const int c = (threadIdx.x & 63) / NG, g = (threadIdx.x & 63) % NG;
   if (c >= 3) return;
+  // output row y0 + ry of the tile lands on row y0 + ry of its plane, or with the row mirror on newh - 1 - (y0 + ry): the tile's rows
+  // walked backwards from newh - 1 - y0 (ry < ny keeps y0 + ry < newh, so the destination row stays inside [0, newh))
+  const long rstep = fy ? -(long)neww : (long)neww;
+  unsigned char* span0 = out + ((long)c * newh + (fy ? newh - 1 - y0 : y0)) * neww + xd0;
   for (int ry = threadIdx.x >> 6; ry < ny; ry += NT / 64) {
     const int y = y0 + ry;
-    unsigned char* span = out + ((long)c * newh + y) * neww + xd0;
+    unsigned char* span = span0 + ry * rstep;
     const int j0 = g * 4 - (int)((size_t)span & 3);           // span index of the group's first byte: -3 .. len + 2
     if (j0 >= len) continue;
     int v[4] = {0, 0, 0, 0};
@@ -69,7 +77,7 @@ __global__ void __launch_bounds__(NT) k_resize_batch_u8(RsBatch b, const unsigne
       for (int q = 0; q < 4; ++q) {
         int jj = j0 + q;
         jj = jj < 0 ? 0 : (jj < len ? jj : len - 1);
-        cxq[q] = t.flip ? len - 1 - jj : jj;
+        cxq[q] = fx ? len - 1 - jj : jj;
       }
       const int lo = ay.lo[y];
       int n = ay.n[y];
@@ -93,7 +101,7 @@ __global__ void __launch_bounds__(NT) k_resize_batch_u8(RsBatch b, const unsigne
       for (int q = 0; q < 4; ++q) {
         const int jj = j0 + q;
         if (jj >= 0 && jj < len) {
-          const int cx = t.flip ? len - 1 - jj : jj;
+          const int cx = fx ? len - 1 - jj : jj;
           vpass<3, 1>(hrow, staged, s, c, h, w, ax, ay, x0 + cx, y, cx, r0, &v[q]);
         }
       }
@@ -108,9 +116,10 @@ __global__ void __launch_bounds__(NT) k_resize_batch_u8(RsBatch b, const unsigne
   }
 }
 
-// offsets + extents inside the buffers, positive sizes, a table exactly for a changed axis and inside the table buffer
+// offsets + extents inside the buffers, positive sizes, a flip code of 0..3, a table exactly for a changed axis and inside the table buffer
 bool item_ok(const cddmsl_resize_item& t, long src_bytes, long dst_bytes, long tab_len) {
   if (t.h <= 0 || t.w <= 0 || t.newh <= 0 || t.neww <= 0) return false;
+  if (t.flip < 0 || t.flip > 3) return false;
   const long sb = 3L * t.h * t.w, db = 3L * t.newh * t.neww;
   if (t.src_off < 0 || t.src_off > src_bytes || sb > src_bytes - t.src_off) return false;
   if (t.dst_off < 0 || t.dst_off > dst_bytes || db > dst_bytes - t.dst_off) return false;

@@ -90,16 +90,57 @@ DEVICE_RESIZE_KEY = "device_resize"      # a sample's record of the resize / mir
 
 
 class DatasetMapper:
-    """Dataset dict -> model input dict; the random draws (short-edge choice, flip) come from ``rng``."""
+    """Dataset dict -> model input dict; the random draws come from ``rng`` in the reference's order: the crop window (INPUT.CROP,
+    ``RandomCrop`` augmentation_impl.py:367-399), the short edge (``choice`` or, with MIN_SIZE_TRAIN_SAMPLING "range", ``randint``),
+    then the flip -- a ``RandomState(s)`` reproduces ``np.random.seed(s)`` on the reference.  With the shipped defaults that is one
+    ``rng.choice`` and one ``rng.uniform`` per sample.  The test mapper resizes only (``build_augmentation(cfg, False)``)."""
+
+    CROP_TYPES = ("relative_range", "relative", "absolute", "absolute_range")
 
     def __init__(self, cfg, is_train=True, rng: Optional[np.random.RandomState] = None):
         i = cfg.INPUT
         self.is_train, self.fmt = is_train, i.FORMAT
         self.min_sizes = list(i.MIN_SIZE_TRAIN) if is_train else [i.MIN_SIZE_TEST]
         self.max_size = i.MAX_SIZE_TRAIN if is_train else i.MAX_SIZE_TEST
-        self.flip = is_train and i.get("RANDOM_FLIP", "horizontal") == "horizontal"
+        self.size_range, self.flip, self.crop_type, self.crop_size = False, 0, None, None
+        if is_train:
+            style, flip, crop = i.get("MIN_SIZE_TRAIN_SAMPLING", "choice"), i.get("RANDOM_FLIP", "horizontal"), i.get("CROP") or {}
+            if style not in ("choice", "range"):
+                raise ValueError(f"INPUT.MIN_SIZE_TRAIN_SAMPLING must be 'choice' or 'range', not {style!r}")
+            if style == "range" and len(self.min_sizes) != 2:
+                raise ValueError(f"INPUT.MIN_SIZE_TRAIN must hold two values (min, max) with INPUT.MIN_SIZE_TRAIN_SAMPLING 'range', not {tuple(self.min_sizes)}")
+            if flip not in ("horizontal", "vertical", "none"):
+                raise ValueError(f"INPUT.RANDOM_FLIP must be 'horizontal', 'vertical' or 'none', not {flip!r}")
+            self.size_range = style == "range"
+            self.flip = {"none": 0, "horizontal": 1, "vertical": 2}[flip]         # the device record's (and the kernel's) flip code
+            if crop.get("ENABLED", False):
+                self.crop_type, self.crop_size = crop.get("TYPE", "relative_range"), tuple(crop.get("SIZE", (0.9, 0.9)))
+                if self.crop_type not in self.CROP_TYPES:
+                    raise ValueError(f"INPUT.CROP.TYPE must be one of {self.CROP_TYPES}, not {self.crop_type!r}")
+                if len(self.crop_size) != 2:
+                    raise ValueError(f"INPUT.CROP.SIZE must hold two values, not {self.crop_size}")
         self.device_resize = bool(cfg.DATALOADER.get("DEVICE_RESIZE", False))
         self.rng = rng or np.random.RandomState()
+
+    def _crop_window(self, h, w):
+        """``RandomCrop.get_crop_size`` + ``get_transform`` -> (y0, x0, ch, cw)"""
+        t, s = self.crop_type, self.crop_size
+        if t == "relative":
+            ch, cw = int(h * s[0] + 0.5), int(w * s[1] + 0.5)
+        elif t == "relative_range":
+            s32 = np.asarray(s, dtype=np.float32)                   # (the reference rounds SIZE to float32, then mixes in float64)
+            fh, fw = s32 + self.rng.rand(2) * (1 - s32)
+            ch, cw = int(h * fh + 0.5), int(w * fw + 0.5)
+        elif t == "absolute":
+            ch, cw = min(int(s[0]), h), min(int(s[1]), w)
+        else:                                                       # "absolute_range": SIZE is (min, max) for both axes
+            assert s[0] <= s[1], "INPUT.CROP.SIZE of 'absolute_range' is (min, max)"
+            ch = int(self.rng.randint(min(h, s[0]), min(h, s[1]) + 1))
+            cw = int(self.rng.randint(min(w, s[0]), min(w, s[1]) + 1))
+        assert 0 < ch <= h and 0 < cw <= w, f"INPUT.CROP.SIZE {s} ({t}) gives a {ch} x {cw} crop of a {h} x {w} image"
+        y0 = int(self.rng.randint(h - ch + 1))
+        x0 = int(self.rng.randint(w - cw + 1))
+        return y0, x0, ch, cw
 
     def __call__(self, d: Dict) -> Dict:
         d = dict(d)
@@ -107,28 +148,35 @@ class DatasetMapper:
         img = read_image(d["file_name"], fmt)
         assert img.shape[:2] == (d["height"], d["width"]), f"{d['file_name']}: image size differs from its annotation"
         twin = read_image(d["data_dt_file_name"], fmt) if "data_dt_file_name" in d else None
-        h, w = img.shape[:2]
-        size = int(self.rng.choice(self.min_sizes))
+        if twin is not None:
+            assert twin.shape[:2] == img.shape[:2], f"{d['data_dt_file_name']}: twin size differs"
+        y0 = x0 = 0
+        if self.crop_type is not None:                             # one window for the image and its twin, in front of the resize
+            y0, x0, ch, cw = self._crop_window(*img.shape[:2])
+            img = img[y0:y0 + ch, x0:x0 + cw]
+            if twin is not None:
+                twin = twin[y0:y0 + ch, x0:x0 + cw]
+        h, w = img.shape[:2]                                       # (the cropped size; d["height"] / d["width"] stay the original's)
+        size = int(self.rng.randint(self.min_sizes[0], self.min_sizes[1] + 1) if self.size_range else self.rng.choice(self.min_sizes))
         newh, neww = shortest_edge_size(h, w, size, self.max_size) if size else (h, w)
-        do_flip = bool(self.flip and self.rng.uniform() < 0.5)
+        flip = bool(self.flip and self.rng.uniform() < 0.5) and self.flip      # False, or the code of the configured mirror
 
         def tf(a):
             a = resize_image(a, newh, neww)
-            return a[:, ::-1] if do_flip else a
+            return a[:, ::-1] if flip == 1 else (a[::-1] if flip == 2 else a)
 
-        if twin is not None:
-            assert twin.shape[:2] == (h, w), f"{d['data_dt_file_name']}: twin size differs"
         if self.device_resize:
-            # DATALOADER.DEVICE_RESIZE: the decoded [h, w, 3] RGB arrays go on as they are, with a record of what is still to do;
-            # DeviceBatches resizes, mirrors, reverses and transposes the whole batch in one kernel launch.  Only the coefficient
-            # tables of the changed axes are built here -- in the worker, where the PIL resize used to run
+            # DATALOADER.DEVICE_RESIZE: the decoded (and cropped) [h, w, 3] RGB arrays go on as they are, with a record of what is still
+            # to do; DeviceBatches resizes, mirrors, reverses and transposes the whole batch in one kernel launch.  Only the coefficient
+            # tables of the changed axes are built here -- in the worker, where the PIL resize used to run.  "flip" is the kernel's
+            # code: False (0) none, 1 left-right, 2 top-bottom
             from .resample import packed_table
-            d[DEVICE_RESIZE_KEY] = {"size": (newh, neww), "flip": do_flip, "reverse_channels": self.fmt == "BGR",
+            d[DEVICE_RESIZE_KEY] = {"size": (newh, neww), "flip": flip, "reverse_channels": self.fmt == "BGR",
                                     "xtab": packed_table(w, neww) if neww != w else None,
                                     "ytab": packed_table(h, newh) if newh != h else None}
-            d["image"] = torch.from_numpy(np.array(img))           # (a copy: PIL hands out a read-only buffer)
+            d["image"] = torch.from_numpy(np.array(img, order="C"))     # (a copy: PIL hands out a read-only buffer; of the window only)
             if twin is not None:
-                d["image_trgt"] = torch.from_numpy(np.array(twin))
+                d["image_trgt"] = torch.from_numpy(np.array(twin, order="C"))
         else:
             d["image"] = torch.from_numpy(np.ascontiguousarray(tf(img).transpose(2, 0, 1)))
             if twin is not None:
@@ -138,9 +186,13 @@ class DatasetMapper:
             return d
         anns = [a for a in anns if not a.get("iscrowd", 0)]                                        # dataset_mapper.py:203
         boxes = np.asarray([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
+        if x0 or y0:
+            boxes = boxes - np.array([x0, y0, x0, y0], dtype=np.float64)               # CropTransform.apply_coords
         boxes = boxes * np.array([neww / w, newh / h, neww / w, newh / h])            # ResizeTransform.apply_coords
-        if do_flip:
+        if flip == 1:
             boxes = np.stack([neww - boxes[:, 2], boxes[:, 1], neww - boxes[:, 0], boxes[:, 3]], axis=1)   # HFlip + re-sort corners
+        elif flip == 2:
+            boxes = np.stack([boxes[:, 0], newh - boxes[:, 3], boxes[:, 2], newh - boxes[:, 1]], axis=1)   # VFlip + re-sort corners
         boxes = np.minimum(boxes, np.array([neww, newh, neww, newh], dtype=np.float64)).clip(min=0)       # transform_instance_annotations
         gt = Boxes(torch.from_numpy(boxes.astype(np.float32)))
         cls = torch.tensor([a["category_id"] for a in anns], dtype=torch.int64)

@@ -672,8 +672,9 @@ def resize_batch_u8(src, dst, tab, items):
     planar [3, newh, neww] results; ``tab``: device int32 buffer of ``resample.packed_table`` tables (None when no axis changes);
     ``items``: one ``(src_off, dst_off, h, w, newh, neww, flip, reverse_channels, xtab, xks, ytab, yks)`` per image -- byte offsets
     into ``src`` / ``dst``, int32 positions into ``tab`` with -1 for an axis that keeps its size.  Bit-equal to
-    ``PIL.Image.resize((neww, newh), BILINEAR)``, then ``[:, ::-1]`` with flip and ``[:, :, ::-1]`` with reverse_channels, transposed
-    to CHW.  The library checks every item against the buffer sizes before it launches; a refusal raises."""
+    ``PIL.Image.resize((neww, newh), BILINEAR)``, then ``[:, ::-1]`` with bit 0 of flip, ``[::-1]`` with bit 1 (0 none, 1 left-right,
+    2 top-bottom, 3 both) and ``[:, :, ::-1]`` with reverse_channels, transposed to CHW.  The library checks every item (buffer sizes,
+    flip in 0..3) before it launches; a refusal raises."""
     require_cuda(src, dst, tab)
     assert src.dtype == torch.uint8 and dst.dtype == torch.uint8 and src.is_contiguous() and dst.is_contiguous()
     assert tab is None or (tab.dtype == torch.int32 and tab.is_contiguous())

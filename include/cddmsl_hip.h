@@ -432,10 +432,13 @@ int cddmsl_tta_view(const unsigned char* img, int h, int w, int newh, int neww, 
 /* the loader's ResizeShortestEdge + RandomFlip for a whole batch in ONE launch (loader_resize.hip; a launch per 32 items beyond that):
  * item i reads the uint8 image [h][w][3] (interleaved, as PIL decodes it) at byte src_off of src and writes Pillow's bilinear resize
  * to (newh, neww) -- the arithmetic of cddmsl_tta_view, bit for bit -- as planar uint8 [3][newh][neww] at byte dst_off of dst; with
- * flip column x is written to column neww - 1 - x, with reverse_channels plane c takes source channel 2 - c (INPUT.FORMAT BGR).
+ * reverse_channels plane c takes source channel 2 - c (INPUT.FORMAT BGR).  flip is a bit set: with bit 0 column x is written to
+ * column neww - 1 - x (RandomFlip horizontal), with bit 1 row y of each plane is written to row newh - 1 - y (vertical), 3 does
+ * both; a value outside 0..3 is CDDMSL_ERR_ARG.  (Before bit 1 had a meaning the kernel tested flip for truth only, so 2 happened to
+ * mirror the columns; no caller passed it.)
  * xtab / ytab: position (in int32 elements) of the axis' table in tab [tab_len], laid out lo [out] | n [out] | k [out][ks] with
  * ks = xks / yks (cddmsl_amd/resample.py); -1 for an axis whose size does not change, which is copied.  Items may share tables (an
- * image and its twin do).  The descriptors are a HOST array.  Every item is checked before the first launch: positive sizes,
+ * image and its twin do).  The descriptors are a HOST array.  Every item is checked before the first launch: positive sizes, a flip code of 0..3,
  * offset + extent inside src_bytes / dst_bytes, a table exactly where an axis changes and inside tab_len; anything else is
  * CDDMSL_ERR_ARG with nothing launched.  count == 0 succeeds with nothing launched.  Bytes of dst outside the items' extents are
  * not written. */

@@ -12,6 +12,7 @@ bench.py times the step on synthetic batches already resident in HBM; this tool 
      buckets), against the same trainer on synthetic 800x1333 batches: ms/step, samples/s, allocator state after iteration 10
      and at the end.
 
+``--crop [TYPE:A,B]`` / ``--min-size-range`` / ``--flip vertical`` pass INPUT.CROP, MIN_SIZE_TRAIN_SAMPLING "range" and RANDOM_FLIP on.
 ``--device-resize`` runs 2. and 3. with DATALOADER.DEVICE_RESIZE: the workers only decode, and the staging thread's one kernel launch
 per batch (cddmsl_resize_batch_u8) resizes, mirrors and transposes on the GPU -- the same bytes reach the model.
 
@@ -72,6 +73,10 @@ def main():
     ap.add_argument("--loader-batches", type=int, default=12)
     ap.add_argument("--device-resize", action="store_true", help="DATALOADER.DEVICE_RESIZE: resize / flip on the GPU in the staging thread")
     ap.add_argument("--skip-step", action="store_true", help="loader alone: skip the training-step measurements")
+    ap.add_argument("--crop", nargs="?", const="relative_range:0.9,0.9", default=None, metavar="TYPE:A,B",
+                    help="INPUT.CROP: RandomCrop in front of the resize, e.g. relative_range:0.9,0.9 (the default with no value) or absolute:300,400")
+    ap.add_argument("--min-size-range", action="store_true", help="INPUT.MIN_SIZE_TRAIN_SAMPLING range: any short edge in [min, max] of INPUT.MIN_SIZE_TRAIN")
+    ap.add_argument("--flip", choices=("horizontal", "vertical", "none"), default=None, help="INPUT.RANDOM_FLIP")
     args = ap.parse_args()
     import bench
     from cddmsl_amd import data, engine, synthetic
@@ -79,13 +84,21 @@ def main():
     cfg = bench.make_cfg("bf16")
     cfg.MODEL.DEVICE = "cuda:0"
     cfg.merge_from_list(["DATALOADER.DEVICE_RESIZE", bool(args.device_resize)])
+    if args.crop is not None:
+        ctype, _, csize = args.crop.partition(":")
+        size = [float(v) if ctype.startswith("relative") else int(v) for v in (csize or "0.9,0.9").split(",")]
+        cfg.merge_from_list(["INPUT.CROP.ENABLED", True, "INPUT.CROP.TYPE", ctype, "INPUT.CROP.SIZE", size])
+    if args.min_size_range:
+        cfg.merge_from_list(["INPUT.MIN_SIZE_TRAIN_SAMPLING", "range", "INPUT.MIN_SIZE_TRAIN", (min(cfg.INPUT.MIN_SIZE_TRAIN), max(cfg.INPUT.MIN_SIZE_TRAIN))])
+    if args.flip is not None:
+        cfg.merge_from_list(["INPUT.RANDOM_FLIP", args.flip])
     engine.limit_host_threads()       # as build_trainer does: the box grants ~16 CPUs, torch's default intra-op pool has one thread per logical CPU
     root = tempfile.mkdtemp(prefix="cddmsl_voc_")
     t0 = time.perf_counter()
     base = make_voc_tree(root, args.images)
     print(f"# synthetic VOC tree: {args.images} JPEG pairs (500x375 / 375x500) under {root}, written in {time.perf_counter() - t0:.1f} s")
     dicts = data.load_voc_instances(base, "trainval", VOC_CLASS_NAMES, dt_data="clipart")
-    print(f"# INPUT.MIN_SIZE_TRAIN {tuple(cfg.INPUT.MIN_SIZE_TRAIN)} max {cfg.INPUT.MAX_SIZE_TRAIN}, flip {cfg.INPUT.RANDOM_FLIP}; host: {os.cpu_count()} logical CPUs ({bench.cpu_model_name()})")
+    print(f"# INPUT.MIN_SIZE_TRAIN {tuple(cfg.INPUT.MIN_SIZE_TRAIN)} ({cfg.INPUT.MIN_SIZE_TRAIN_SAMPLING}) max {cfg.INPUT.MAX_SIZE_TRAIN}, flip {cfg.INPUT.RANDOM_FLIP}, crop {(cfg.INPUT.CROP.TYPE, tuple(cfg.INPUT.CROP.SIZE)) if cfg.INPUT.CROP.ENABLED else None}; host: {os.cpu_count()} logical CPUs ({bench.cpu_model_name()})")
     print(f"# DATALOADER.DEVICE_RESIZE {cfg.DATALOADER.DEVICE_RESIZE}")
     print("# 1. loader alone (decode 2 JPEGs + resize both + flip + batch + pin + H2D" + (" of the originals + one resize launch per batch" if args.device_resize else "")
           + "), samples/s after 2 warm-up batches")
