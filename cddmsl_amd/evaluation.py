@@ -161,7 +161,7 @@ def inference_on_dataset(model, data_loader, evaluator):
     return evaluator.evaluate()
 
 
-def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False):
+def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False, prefix=""):
     """tools/train_caption_consistency.py:143-152 (``--eval-only``): VOC-style test set under ``args.voc_root`` -> AP dict
     printed by rank 0.  Every rank evaluates its shard of the test set (``world`` has to be the process group's size: the
     evaluator merges all ranks' detections, so unsharded ranks would count every detection ``world`` times).  Returns the
@@ -176,12 +176,12 @@ def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False):
     ev = PascalVOCDetectionEvaluator(args.voc_root, args.voc_split, args.voc_year, names)
     res = inference_on_dataset(model, loader, ev)
     if rank == 0:
-        print({k: round(v, 4) for k, v in res["bbox"].items()})
+        print(prefix + str({k: round(v, 4) for k, v in res["bbox"].items()}))
     if tta_enabled(cfg):            # train_caption_consistency.py:105-118,149-150: the same set again through the TTA model
         loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
         tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, ev))
         if rank == 0:
-            print({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()})
+            print(prefix + str({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()}))
             res.update(tta)
     return res if return_results else 0
 
@@ -301,6 +301,92 @@ def coco_precision(gt_by_image, dt_by_image, num_classes):
     return prec
 
 
+# ---- the same in two halves: per-detection records (from hip.coco_match, or from coco_match_host below) -> coco_accumulate
+COCO_RECORD_FIELDS = (("score", np.float64), ("cls", np.int64), ("img", np.int64), ("rank", np.int32), ("matched", np.int64), ("ignored", np.int64))
+
+
+def empty_coco_records():
+    return {k: np.zeros(0, dtype=dt) for k, dt in COCO_RECORD_FIELDS}
+
+
+def coco_match_host(gt, dt, num_classes):
+    """``hip.coco_match``'s outputs for ONE image from the host matcher: ``gt = (xywh, area, crowd, class)``, ``dt = (xywh, score,
+    class)`` -> (rank int32 [D], matched int64 [D], ignored int64 [D]) in the detections' input order; bit ``a * T + t`` of a mask is
+    ``_coco_match``'s flag at threshold t in area range a, rank is the position in ``argsort(-score, mergesort)`` of the detection's
+    class, -1 beyond COCO_MAX_DETS (masks 0).  The no-device path, and what an image beyond the kernel's caps goes through."""
+    gb, garea, gcrowd, gcls = gt
+    db, ds, dc = dt
+    T = len(COCO_IOU_THRS)
+    rank = -np.ones(len(ds), dtype=np.int32)
+    matched, ignored = np.zeros(len(ds), dtype=np.int64), np.zeros(len(ds), dtype=np.int64)
+    for k in range(num_classes):
+        d = np.flatnonzero(dc == k)
+        if not d.size:
+            continue
+        g = gcls == k
+        kept = d[np.argsort(-ds[d], kind="mergesort")[:COCO_MAX_DETS]]
+        rank[kept] = np.arange(len(kept), dtype=np.int32)
+        for a, rng in enumerate(COCO_AREA_RNGS):
+            _, m, ig, _ = _coco_match(db[d], ds[d], gb[g], garea[g], gcrowd[g], rng)
+            bits = (np.int64(1) << (a * T + np.arange(T, dtype=np.int64)))[:, None]
+            matched[kept] |= (m * bits).sum(axis=0)
+            ignored[kept] |= (ig * bits).sum(axis=0)
+    return rank, matched, ignored
+
+
+def coco_gt_counts(gt_per_image, num_classes):
+    """non-ignored ground truth per (class, area range) -> int64 [K, A]: what ``coco_precision`` sums up as ``npig``"""
+    n = np.zeros((num_classes, len(COCO_AREA_RNGS)), dtype=np.int64)
+    for _, garea, gcrowd, gcls in gt_per_image:
+        for a, rng in enumerate(COCO_AREA_RNGS):
+            ok = ~(gcrowd | (garea < rng[0]) | (garea > rng[1])) & (gcls >= 0) & (gcls < num_classes)
+            np.add.at(n[:, a], gcls[ok], 1)
+    return n
+
+
+def merge_coco_records(parts):
+    """records of several evaluators (ranks) -> one set ordered by data-set image index, then by rank inside the image: the order in
+    which ``coco_precision`` concatenates its per-image results, so equal scores of different images fall the same way"""
+    parts = [p for p in parts if p is not None]
+    rec = {k: np.concatenate([np.asarray(p[k], dtype=dt) for p in parts] or [np.zeros(0, dtype=dt)]) for k, dt in COCO_RECORD_FIELDS}
+    order = np.lexsort((rec["rank"], rec["img"]))
+    return {k: v[order] for k, v in rec.items()}
+
+
+def coco_accumulate(rec, npig, num_classes):
+    """``COCOeval.accumulate`` on per-detection records (the second half of ``coco_precision``, vectorised; exactly equal to it):
+    ``rec`` = arrays score / cls / img / rank / matched / ignored over the KEPT detections (rank >= 0) of all images, any order;
+    ``npig`` int [K, A] from ``coco_gt_counts``.  -> precision [T, 101, K, A], -1 where a class has no non-ignored ground truth."""
+    T, R, A = len(COCO_IOU_THRS), len(COCO_REC_THRS), len(COCO_AREA_RNGS)
+    prec = -np.ones((T, R, num_classes, A))
+    base = np.lexsort((rec["rank"], rec["img"]))
+    cls = rec["cls"][base]
+    for k in range(num_classes):
+        if not npig[k].any():
+            continue
+        sel = base[cls == k]
+        sel = sel[np.argsort(-rec["score"][sel], kind="mergesort")]
+        N = len(sel)
+        mbits, ibits = rec["matched"][sel], rec["ignored"][sel]
+        for a in range(A):
+            if npig[k, a] == 0:
+                continue
+            sh = (a * T + np.arange(T, dtype=np.int64))[:, None]
+            m, ig = ((mbits[None, :] >> sh) & 1).astype(bool), ((ibits[None, :] >> sh) & 1).astype(bool)
+            tps = np.cumsum(m & ~ig, axis=1, dtype=np.float64)
+            fps = np.cumsum(~m & ~ig, axis=1, dtype=np.float64)
+            rc = tps / int(npig[k, a])
+            pr = tps / (fps + tps + np.spacing(1))
+            pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]      # precision envelope, from the right
+            for t in range(T):
+                inds = np.searchsorted(rc[t], COCO_REC_THRS, side="left")
+                q = np.zeros(R)
+                ok = inds < N
+                q[ok] = pr[t, inds[ok]]
+                prec[t, :, k, a] = q
+    return prec
+
+
 class COCODetectionEvaluator:
     """COCO-style box AP (evaluation/coco_evaluation.py:292-360 over pycocotools ``COCOeval``, iouType "bbox") in numpy, with the
     same ``reset / process / evaluate`` protocol and rank-0 gather as ``PascalVOCDetectionEvaluator``.  pycocotools is not a
@@ -314,10 +400,17 @@ class COCODetectionEvaluator:
     / medium / large (> 96^2) judge the GT by ``area`` and unmatched detections by their box area; precision is made monotone from
     the right and sampled at 101 recall points; classes without non-ignored GT are left out of the means.  Returns
     ``{"bbox": {AP, AP50, AP75, APs, APm, APl, "AP-<class>"...}}`` in percent; NaN where nothing is defined (every key when there
-    are no detections at all)."""
+    are no detections at all).
 
-    def __init__(self, dataset_dicts, class_names):
+    ``device``: a GPU device moves the matching there.  The ground truth is uploaded once; ``process`` copies nothing to the host and
+    does not synchronise -- one ``hip.coco_match`` launch per call matches the batch's detections where the model left them;
+    ``evaluate`` reads the per-detection records (score, class, rank, two 40-bit masks) back in ONE copy, gathers only those to
+    rank 0 and runs ``coco_accumulate``.  Same dictionary as without ``device``, value for value.  An image beyond the kernel's caps
+    (hip.COCO_MATCH_MAX_DETS / COCO_MATCH_MAX_GT of one class) is matched by ``coco_match_host``, never truncated."""
+
+    def __init__(self, dataset_dicts, class_names, device=None):
         self.class_names = list(class_names)
+        self.device = torch.device(device) if device is not None and torch.device(device).type != "cpu" else None
         self._gt = {}
         for d in dataset_dicts:
             anns = d.get("annotations", [])
@@ -327,12 +420,93 @@ class COCODetectionEvaluator:
             crowd = np.array([bool(a.get("iscrowd", 0)) for a in anns], dtype=bool)
             cls = np.array([a["category_id"] for a in anns], dtype=np.int64)
             self._gt[str(d["image_id"])] = (xywh, area, crowd, cls)
+        if self.device is not None:
+            from . import hip
+            self._index = {k: i for i, k in enumerate(self._gt)}      # image id -> data-set index (coco_precision's image order)
+            self._gt_list = list(self._gt.values())
+            self._gt_dev = hip.CocoGroundTruth.from_host(self._gt_list, np.minimum(COCO_IOU_THRS, 1 - 1e-10), COCO_AREA_RNGS, self.device)
         self.reset()
 
     def reset(self):
         self._predictions = {}           # image id -> (xywh [D,4], scores [D], classes [D])
+        self._batches = []               # device path: one entry per process() call, everything still on the device
+
+    def _process_device(self, inputs, outputs):
+        from . import hip
+        from ._lib import to_device_async
+        idx, boxes, scores, classes = [], [], [], []
+        for inp, out in zip(inputs, outputs):
+            i = self._index.get(str(inp["image_id"]))
+            if i is None:                # not an image of this data set: the host path never looks at it either
+                continue
+            inst = out["instances"]
+            idx.append(i)
+            boxes.append(inst.pred_boxes.tensor.detach().float().reshape(-1, 4))
+            scores.append(inst.scores.detach().float().reshape(-1))
+            classes.append(inst.pred_classes.detach().long().reshape(-1))
+        if not idx:
+            return
+        lens = [len(s) for s in scores]
+        meta = to_device_async(torch.tensor(np.concatenate([[0], np.cumsum(lens), idx]).astype(np.int64)), self.device)
+        b, s, c = torch.cat(boxes).contiguous(), torch.cat(scores).contiguous(), torch.cat(classes).contiguous()
+        rank, matched, ignored, over = hip.coco_match(b, s, c, meta[: len(idx) + 1], meta[len(idx) + 1:], self._gt_dev, len(self.class_names),
+                                                      COCO_MAX_DETS)
+        self._batches.append({"idx": idx, "lens": lens, "boxes": b, "scores": s, "cls": c, "rank": rank, "matched": matched,
+                              "ignored": ignored, "over": over})
+
+    def _device_records(self):
+        """the ONE readback -> (records of the kept detections, number of detections seen)"""
+        if not self._batches:
+            return empty_coco_records(), 0
+        rows = [torch.stack([e["scores"].view(torch.int32).long(), e["cls"], e["rank"].long(), e["matched"], e["ignored"]], dim=1).reshape(-1)
+                for e in self._batches]
+        host = torch.cat(rows + [e["over"].long() for e in self._batches]).cpu().numpy()
+        n = sum(sum(e["lens"]) for e in self._batches)
+        tab, over = host[: 5 * n].reshape(n, 5), host[5 * n:]
+        score = tab[:, 0].astype(np.int32).view(np.float32).astype(np.float64)
+        cls, rank, matched, ignored = tab[:, 1].copy(), tab[:, 2].astype(np.int32), tab[:, 3].copy(), tab[:, 4].copy()
+        idx = np.array([i for e in self._batches for i in e["idx"]], dtype=np.int64)
+        lens = np.array([l for e in self._batches for l in e["lens"]], dtype=np.int64)
+        start = np.concatenate([[0], np.cumsum(lens)])
+        img = np.repeat(idx, lens)
+        live = np.ones(n, dtype=bool)
+        last = {int(i): j for j, i in enumerate(idx)}                # an image processed twice: the later call replaces the earlier
+        for j, i in enumerate(idx):
+            if last[int(i)] != j:
+                live[start[j]: start[j + 1]] = False
+        if over.any():                                               # beyond a cap of the kernel: the host matcher, on the same values
+            j0 = 0
+            for e in self._batches:
+                nb = len(e["idx"])
+                if over[j0: j0 + nb].any():
+                    bx = e["boxes"].cpu().numpy().astype(np.float64)
+                    for j in range(j0, j0 + nb):
+                        if over[j] and last[int(idx[j])] == j:
+                            lo, hi = start[j], start[j + 1]
+                            b = bx[lo - start[j0]: hi - start[j0]]
+                            xywh = np.concatenate([b[:, :2], b[:, 2:] - b[:, :2]], axis=1)
+                            with np.errstate(invalid="ignore", divide="ignore"):        # (a 0 / 0 IoU is a NaN on purpose)
+                                rank[lo:hi], matched[lo:hi], ignored[lo:hi] = coco_match_host(self._gt_list[int(idx[j])],
+                                                                                              (xywh, score[lo:hi], cls[lo:hi]), len(self.class_names))
+                j0 += nb
+        keep = live & (rank >= 0)
+        rec = {"score": score[keep], "cls": cls[keep], "img": img[keep], "rank": rank[keep], "matched": matched[keep], "ignored": ignored[keep]}
+        return rec, int(live.sum())
+
+    def _gathered_records(self):
+        import torch.distributed as dist
+        rec, n = self._device_records()
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return merge_coco_records([rec]), n
+        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+        dist.gather_object((rec, n), parts, dst=0)
+        if dist.get_rank() != 0:
+            return None, 0
+        return merge_coco_records([p[0] for p in parts]), sum(p[1] for p in parts)
 
     def process(self, inputs, outputs):
+        if self.device is not None:
+            return self._process_device(inputs, outputs)
         for inp, out in zip(inputs, outputs):
             inst = out["instances"]
             b = inst.pred_boxes.tensor.detach().float().cpu().numpy().astype(np.float64).reshape(-1, 4)
@@ -354,16 +528,25 @@ class COCODetectionEvaluator:
         return merged
 
     def evaluate(self):
-        preds = self._gathered()
-        if preds is None:
-            return None
+        if self.device is not None:
+            rec, ndet = self._gathered_records()
+            if rec is None:
+                return None
+        else:
+            preds = self._gathered()
+            if preds is None:
+                return None
+            ndet = sum(len(p[1]) for p in preds.values())
         metrics = ("AP", "AP50", "AP75", "APs", "APm", "APl")
         res = OrderedDict()
-        if sum(len(p[1]) for p in preds.values()) == 0:
+        if ndet == 0:
             res.update({m: float("nan") for m in metrics})
             res.update({"AP-" + n: float("nan") for n in self.class_names})
             return {"bbox": res}
-        prec = coco_precision(self._gt, preds, len(self.class_names))
+        if self.device is not None:
+            prec = coco_accumulate(rec, coco_gt_counts(self._gt_list, len(self.class_names)), len(self.class_names))
+        else:
+            prec = coco_precision(self._gt, preds, len(self.class_names))
 
         def mean(p):
             p = p[p > -1]
@@ -375,32 +558,107 @@ class COCODetectionEvaluator:
         return {"bbox": res}
 
 
-def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_results=False):
-    """``--eval-only --datasets-root DIR``: every ``cfg.DATASETS.TEST`` name the catalog knows (the Cityscapes splits of
-    cddmsl_amd/cityscapes.py) -> COCO-style box AP, one printed line per set from rank 0; a name the catalog does not know
-    (e.g. ``bdd_100k_val``, which needs a COCO-json reader) is skipped with one printed line.  Returns the exit code (or
-    {name: result dict} on rank 0 with ``return_results``)."""
+def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_results=False, prefix=""):
+    """``--eval-only --datasets-root DIR``: every ``cfg.DATASETS.TEST`` name the catalog knows -- the Cityscapes splits of
+    cddmsl_amd/cityscapes.py and the COCO-json sets of cddmsl_amd/coco_json.py (``bdd_100k_val``) -> COCO-style box AP, one printed
+    line per set from rank 0 (each starting with ``prefix``); a name the catalog does not know, or a json set whose file is not
+    there, is skipped with one printed line.  The matching runs on ``cfg.MODEL.DEVICE`` (COCODetectionEvaluator's ``device``).
+    Returns the exit code (or {name: result dict} on rank 0 with ``return_results``)."""
     import torch.distributed as dist
-    from . import cityscapes
+    from . import cityscapes, coco_json
     from .data import build_detection_test_loader
     ws = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     assert world == ws, f"run_eval_only_catalog: world={world} but the process group has {ws} ranks"
     results = OrderedDict()
     for name in cfg.DATASETS.TEST:
-        if not cityscapes.is_cityscapes(name):
+        if cityscapes.is_cityscapes(name):
+            dicts, classes = cityscapes.load_cityscapes(name, datasets_root, device=cfg.MODEL.DEVICE), cityscapes.THING_CLASSES
+        elif coco_json.is_coco_json(name):
+            json_file = coco_json.coco_json_paths(name, datasets_root)[0]
+            if not os.path.exists(json_file):
+                if rank == 0:
+                    print(f"{prefix}skipping {name}: {json_file} not found")
+                continue
+            dicts, classes = coco_json.load_coco_json_split(name, datasets_root)
+            if len(classes) != num_test_classes(model, cfg):
+                raise ValueError(f"{name}: {json_file} has {len(classes)} classes but the model's detections have {num_test_classes(model, cfg)}")
+        else:
             if rank == 0:
-                print(f"skipping {name}: not in the dataset catalog")
+                print(f"{prefix}skipping {name}: not in the dataset catalog")
             continue
-        dicts = cityscapes.load_cityscapes(name, datasets_root, device=cfg.MODEL.DEVICE)
         loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
-        res = inference_on_dataset(model, loader, COCODetectionEvaluator(dicts, cityscapes.THING_CLASSES))
+        res = inference_on_dataset(model, loader, COCODetectionEvaluator(dicts, classes, device=cfg.MODEL.DEVICE))
         if rank == 0:
-            print(f"{name}: " + str({k: round(v, 4) for k, v in res["bbox"].items()}), flush=True)
+            print(f"{prefix}{name}: " + str({k: round(v, 4) for k, v in res["bbox"].items()}), flush=True)
             results[name] = res
         if tta_enabled(cfg):
             loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
-            tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, COCODetectionEvaluator(dicts, cityscapes.THING_CLASSES)))
+            tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, COCODetectionEvaluator(dicts, classes, device=cfg.MODEL.DEVICE)))
             if rank == 0:
-                print(f"{name}: " + str({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()}), flush=True)
+                print(f"{prefix}{name}: " + str({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()}), flush=True)
                 results[name].update(tta)
     return results if return_results else 0
+
+
+def flatten_results(results):
+    """{dataset: {"bbox": {"AP": v}}} -> {"dataset/bbox/AP": v}: the keys the reference's EvalHook puts into the storage"""
+    flat = OrderedDict()
+    for name, res in (results or {}).items():
+        for task, metrics in res.items():
+            for m, v in metrics.items():
+                flat[f"{name}/{task}/{m}"] = float(v)
+    return flat
+
+
+class PeriodicEval:
+    """engine/hooks.py ``EvalHook``: ``after_step(it)`` evaluates on every rank when ``(it + 1) % period == 0`` and ``after_train()``
+    once after the last iteration unless that iteration was just evaluated.  ``eval_fn(prefix)`` runs the sharded evaluation and
+    returns {dataset: results} on rank 0 (``run_eval_only_catalog`` / ``run_eval_only`` with ``return_results``); the flattened
+    values go to ``trainer.storage``.  An evaluation leaves training as it found it: ``model.training``, the model's three sampler
+    generators and torch's CPU / GPU generators are restored, the training loader is not touched, and the model's cache of the
+    shared source pass is dropped instead of being carried across."""
+
+    def __init__(self, trainer, period, eval_fn, max_iter, rank=0):
+        self.trainer, self.period, self.eval_fn, self.max_iter, self.rank = trainer, int(period), eval_fn, int(max_iter), rank
+        self.evaluated_at = []
+
+    def _generators(self):
+        m = self.trainer.model
+        gens = [g for g in (getattr(getattr(m, "proposal_generator", None), "sample_generator", None),
+                            getattr(getattr(m, "roi_heads", None), "sample_generator", None), getattr(m, "region_generator", None)) if g is not None]
+        return list({id(g): g for g in gens}.values())
+
+    def _do_eval(self, it):
+        m = self.trainer.model
+        was_training = m.training
+        gens = self._generators()
+        states = [g.get_state() for g in gens]
+        cpu_state = torch.get_rng_state()
+        cuda_state = torch.cuda.get_rng_state() if torch.cuda.is_available() else None
+        if hasattr(m, "_shared"):
+            m._shared = None
+        try:
+            results = self.eval_fn(f"iter {it}  ")
+        finally:
+            m.train(was_training)
+            if hasattr(m, "_shared"):
+                m._shared = None
+            for g, s in zip(gens, states):
+                g.set_state(s)
+            torch.set_rng_state(cpu_state)
+            if cuda_state is not None:
+                torch.cuda.set_rng_state(cuda_state)
+        self.evaluated_at.append(it)
+        if self.rank == 0 and isinstance(results, dict):
+            for k, v in flatten_results(results).items():
+                self.trainer.storage[k] = v
+        return results
+
+    def after_step(self, it):
+        if self.period > 0 and (it + 1) % self.period == 0:
+            return self._do_eval(it)
+
+    def after_train(self):
+        last = self.max_iter - 1
+        if self.period > 0 and last >= 0 and (not self.evaluated_at or self.evaluated_at[-1] != last):
+            return self._do_eval(last)

@@ -61,6 +61,7 @@ def _L():
         L.cddmsl_roi_align_backward.argtypes = [vp] * 7 + [ci] * 7 + [cf, ci, ci, ci, vp]
         L.cddmsl_nms_anyorder.argtypes = [vp] * 4 + [ci, cf, vp, vp, vp]
         L.cddmsl_soft_nms.argtypes = [vp] * 6 + [ci, ci, cf, cf, cf, ci, vp, vp, vp]
+        L.cddmsl_coco_match.argtypes = [vp] * 5 + [ci, c_long] + [vp] * 5 + [c_long, vp, ci, vp, ci, ci, ci] + [vp] * 5
         L.cddmsl_openset_logits.argtypes = [vp] * 4 + [ci] * 4 + [cf, cf, vp]
         L.cddmsl_openset_select.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, cf, cf, cf] + [vp] * 6 + [ci, vp, vp, vp]
         L.cddmsl_roi_align_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
@@ -1234,6 +1235,68 @@ def soft_nms(boxes, scores, idxs, method, sigma, iou_threshold, prune_threshold,
     check(_L().cddmsl_soft_nms(ptr(boxes), ptr(scores), ptr(idxs), ptr(keep), ptr(keep_scores), ptr(nkeep), *args, ptr(ws), ctypes.byref(nbytes),
                                stream_ptr()), "cddmsl_soft_nms")
     return keep, keep_scores, nkeep
+
+
+# cddmsl_coco_match: what one (image, class) may hold; an image beyond a cap comes back flagged in ``over`` and is matched on the host
+COCO_MATCH_MAX_DETS = 1024           # detections of one class in one image (so any image with up to 1024 detections fits)
+COCO_MATCH_MAX_GT = 256              # ground-truth boxes of one class in one image
+COCO_MATCH_MAX_KEPT = 128            # kept detections per (image, class): the ``max_dets`` argument
+
+
+class CocoGroundTruth:
+    """A data set's ground truth on the device, as cddmsl_coco_match reads it: ``xywh`` f64 [G, 4], ``area`` f64 [G], ``crowd`` u8 [G],
+    ``cls`` int64 [G] concatenated over the images, ``off`` int64 [n_images + 1]; plus the walk's constants ``thrs`` f64 [T] and
+    ``rngs`` f64 [A, 2].  Built once per evaluator from host arrays (``from_host``)."""
+
+    def __init__(self, xywh, area, crowd, cls, off, thrs, rngs):
+        require_cuda(xywh, area, crowd, cls, off, thrs, rngs)
+        G = area.numel()
+        assert xywh.dtype == area.dtype == thrs.dtype == rngs.dtype == torch.float64 and crowd.dtype == torch.uint8
+        assert cls.dtype == off.dtype == torch.int64 and tuple(xywh.shape) == (G, 4) and crowd.numel() == cls.numel() == G
+        assert off.numel() >= 1 and rngs.dim() == 2 and rngs.shape[1] == 2 and thrs.dim() == 1
+        assert all(t.is_contiguous() for t in (xywh, area, crowd, cls, off, thrs, rngs))
+        self.xywh, self.area, self.crowd, self.cls, self.off, self.thrs, self.rngs = xywh, area, crowd, cls, off, thrs, rngs
+        self.n_images = off.numel() - 1
+
+    @classmethod
+    def from_host(cls, per_image, thrs, rngs, device):
+        """``per_image``: [(xywh [g,4], area [g], crowd [g] bool, class [g])] numpy, in data-set order"""
+        import numpy as np
+        from ._lib import to_device_async
+        cat = lambda i, dt, shape: np.concatenate([np.asarray(p[i], dtype=dt).reshape(shape) for p in per_image] or [np.zeros(shape, dtype=dt)])
+        off = np.zeros(len(per_image) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(p[1]) for p in per_image])
+        up = lambda a: to_device_async(torch.from_numpy(np.ascontiguousarray(a)), device)
+        return cls(up(cat(0, np.float64, (-1, 4))), up(cat(1, np.float64, (-1,))), up(cat(2, np.uint8, (-1,))), up(cat(3, np.int64, (-1,))),
+                   up(off), up(np.asarray(thrs, dtype=np.float64)), up(np.asarray(rngs, dtype=np.float64).reshape(-1, 2)))
+
+
+@_timed("coco_match")
+def coco_match(dt_boxes, dt_scores, dt_cls, dt_off, img_idx, gt, num_classes, max_dets=100):
+    """``COCOeval.evaluateImg`` for every (image, class, area range, IoU threshold) of a batch in one launch (cddmsl_coco_match),
+    bit-identical to ``evaluation._coco_match`` per (image, class, range).  ``dt_boxes`` f32 [D, 4] XYXY, ``dt_scores`` f32 [D],
+    ``dt_cls`` int64 [D]: the batch's detections, image after image, with offsets ``dt_off`` int64 [B + 1]; ``img_idx`` int64 [B]:
+    the images' indices into ``gt`` (a ``CocoGroundTruth``).  All on the device; nothing is read back and nothing synchronises.
+    -> (rank int32 [D]: position in the stable descending-score order of the detection's (image, class), -1 when dropped;
+    matched, ignored int64 [D]: bit ``a * T + t``; over int32 [B]: 1 = the image exceeds a cap (COCO_MATCH_MAX_DETS /
+    COCO_MATCH_MAX_GT of one class), its outputs are incomplete and the caller has to match it on the host)."""
+    require_cuda(dt_boxes, dt_scores, dt_cls, dt_off, img_idx)
+    D, B = dt_scores.numel(), img_idx.numel()
+    assert dt_boxes.dtype == dt_scores.dtype == torch.float32 and dt_cls.dtype == dt_off.dtype == img_idx.dtype == torch.int64
+    assert tuple(dt_boxes.shape) == (D, 4) and dt_cls.numel() == D and dt_off.numel() == B + 1
+    assert dt_boxes.is_contiguous() and dt_scores.is_contiguous() and dt_cls.is_contiguous() and dt_off.is_contiguous() and img_idx.is_contiguous()
+    if not 1 <= max_dets <= COCO_MATCH_MAX_KEPT:
+        raise ValueError(f"coco_match: max_dets {max_dets} outside [1, {COCO_MATCH_MAX_KEPT}]")
+    dev = dt_boxes.device
+    rank = torch.empty(D, device=dev, dtype=torch.int32)
+    matched = torch.empty(D, device=dev, dtype=torch.int64)
+    ignored = torch.empty(D, device=dev, dtype=torch.int64)
+    over = torch.empty(B, device=dev, dtype=torch.int32)
+    check(_L().cddmsl_coco_match(ptr(dt_boxes), ptr(dt_scores), ptr(dt_cls), ptr(dt_off), ptr(img_idx), B, D, ptr(gt.xywh), ptr(gt.area),
+                                 ptr(gt.crowd), ptr(gt.cls), ptr(gt.off), gt.n_images, ptr(gt.thrs), gt.thrs.numel(), ptr(gt.rngs),
+                                 gt.rngs.shape[0], int(num_classes), int(max_dets), ptr(rank), ptr(matched), ptr(ignored), ptr(over),
+                                 stream_ptr()), "cddmsl_coco_match")
+    return rank, matched, ignored, over
 
 
 OPENSET_MAX_CLASSES = 16384          # cddmsl_openset_logits / _select: classes of the test vocabulary

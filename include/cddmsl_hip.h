@@ -207,6 +207,27 @@ int cddmsl_nms_anyorder(const float* boxes, const float* scores, long* keep, int
 int cddmsl_soft_nms(const float* boxes, const float* scores, const long* idxs, long* keep, float* keep_scores, int* nkeep, int K,
                     int method, float sigma, float iou_threshold, float prune_threshold, int max_keep, void* temp,
                     size_t* temp_bytes, void* stream);
+/* ---- COCO box matching (csrc/coco_match.hip): COCOeval.evaluateImg's greedy walk (pycocotools cocoeval.py, iouType "bbox", as
+ * evaluation/coco_evaluation.py drives it) for every (image, class) of a batch in ONE launch, bit-identical to the package's host
+ * matcher (cddmsl_amd/evaluation.py _coco_match + coco_box_iou) called per (image, class, area range).
+ *   detections   dt_boxes [D_total][4] f32 XYXY (16-byte aligned), dt_scores [D_total] f32, dt_cls [D_total] int64, concatenated
+ *                over the batch's B images with offsets dt_off [B + 1] int64; img_idx [B] int64 = each image's index into
+ *   ground truth gt_xywh [.][4] f64, gt_area [.] f64 (the stored area: it decides "ignored" per range), gt_crowd [.] u8, gt_cls [.]
+ *                int64, concatenated over the data set's n_images images with offsets gt_off [n_images + 1] int64
+ *   thrs [T] f64 IoU thresholds as the walk uses them (min(t, 1 - 1e-10), from the host), area_rngs [A][2] f64 (lo, hi), K classes,
+ *                max_dets kept detections per (image, class).  T * A <= 64, A <= 4, max_dets <= 128.
+ * -> rank [D_total] int32: the detection's position in the stable descending-score order of its (image, class) (NaN scores last,
+ *    equal scores by input index), -1 for a position >= max_dets or a class outside [0, K);
+ *    matched / ignored [D_total] int64: bit a * T + t = the walk's dtm / dtIg flag at threshold t in range a (0 where rank is -1);
+ *    over [B] int32: 1 when some class of the image exceeds a cap (1024 detections or 256 ground-truth boxes of one class in one
+ *    image) or its offsets are inconsistent -- the image's outputs are then incomplete and the caller matches it on the host.
+ * Arithmetic: f64, the host's operations in the host's order (boxes widened to f64 first; w = x2 - x1; IoU = inter / union with
+ * union = da + ga - inter, or da against a crowd box); `iou < best` skips, so of equal IoUs the later box wins and a NaN IoU (0 / 0)
+ * is taken.  No atomics, every output has one writer: two runs give the same bytes.  No allocation, no synchronisation. */
+int cddmsl_coco_match(const float* dt_boxes, const float* dt_scores, const long* dt_cls, const long* dt_off, const long* img_idx,
+                      int B, long D_total, const double* gt_xywh, const double* gt_area, const unsigned char* gt_crowd,
+                      const long* gt_cls, const long* gt_off, long n_images, const double* thrs, int T, const double* area_rngs,
+                      int A, int K, int max_dets, int* rank, long* matched, long* ignored, int* over, void* stream);
 /* ---- open-vocabulary inference (csrc/openset.hip): the test_cls_score branch of FastRCNNOutputLayers.forward, predict_probs,
  * the RPN-objectness product and fast_rcnn_inference_single_image up to its NMS (roi_heads/fast_rcnn.py:546-565, 793-810, 706-710,
  * 155-180).  Everything f32; no atomics: two runs give the same bits.

@@ -9,7 +9,8 @@ One process per GPU (engine/launch.py:67-80): with --num-gpus > 1 this script re
 paired-batch generator; ``--voc-root <VOCdevkit/VOC2007> --dt-data <twin dir>`` switches to the real paired VOC pipeline
 (cddmsl_amd/data.py), ``--eval-only --voc-root ...`` runs inference + Pascal VOC AP (cddmsl_amd/evaluation.py),
 ``--datasets-root DIR`` does the same for the Cityscapes / Foggy Cityscapes splits of the AdverseWeather config (paired training
-loader; COCO-style box AP on every known DATASETS.TEST name; cddmsl_amd/cityscapes.py), and
+loader; COCO-style box AP on every known DATASETS.TEST name, ``bdd_100k_val`` from its COCO json included; cddmsl_amd/cityscapes.py,
+cddmsl_amd/coco_json.py), ``TEST.EVAL_PERIOD`` repeats that evaluation during training whenever a test set is given, and
 ``MODEL.WEIGHTS`` / ``--resume`` / ``MODEL.PRE_TRAINED_RCLIP_PATH`` go through cddmsl_amd/checkpoint.py.
 """
 import argparse
@@ -52,6 +53,25 @@ def setup(args):
         cfg.merge_from_file(args.config_file)
     cfg.merge_from_list(args.opts or [])
     return cfg
+
+
+def build_eval_hook(tr, cfg, args, rank, world, max_iter):
+    """hooks.EvalHook (engine/defaults.py:433-447): with TEST.EVAL_PERIOD > 0 and a test set on disk -- ``--datasets-root`` (every
+    known DATASETS.TEST name), or ``--voc-root`` with the ``--voc-split`` split -- all ranks evaluate their shard every EVAL_PERIOD
+    iterations and once after the last one; rank 0 prints the usual lines behind "iter N" and keeps the values in ``tr.storage``.
+    None otherwise: the synthetic loader has no test set."""
+    from cddmsl_amd import evaluation
+    period = int(cfg.TEST.get("EVAL_PERIOD", 0))
+    if period <= 0:
+        return None
+    if args.datasets_root and not (args.voc_root and args.dt_data):
+        fn = lambda prefix: evaluation.run_eval_only_catalog(tr.model, cfg, args.datasets_root, rank, world, return_results=True, prefix=prefix)
+    elif args.voc_root and os.path.exists(os.path.join(args.voc_root, "ImageSets", "Main", args.voc_split + ".txt")):
+        name = cfg.DATASETS.TEST[0] if cfg.DATASETS.TEST else "voc_" + args.voc_split
+        fn = lambda prefix: {name: evaluation.run_eval_only(tr.model, cfg, args, rank, world, return_results=True, prefix=prefix)}
+    else:
+        return None
+    return evaluation.PeriodicEval(tr, period, fn, max_iter, rank)
 
 
 def main(args):
@@ -99,12 +119,17 @@ def main(args):
         tr._data_loader_iter = iter(tr.data_loader)
     max_iter = args.max_iter or cfg.SOLVER.MAX_ITER
     period = cfg.SOLVER.get("CHECKPOINT_PERIOD", 0)
+    eval_hook = build_eval_hook(tr, cfg, args, rank, world, max_iter)        # hooks.EvalHook: TEST.EVAL_PERIOD, when a test set is given
     for it in range(tr.iter, max_iter):
         tr.run_step()
+        if eval_hook is not None:
+            eval_hook.after_step(it)
         if rank == 0 and tr.metrics_period and it % tr.metrics_period == 0:
             print(f"iter {it}  " + "  ".join(f"{k}: {v:.4f}" for k, v in sorted(tr.storage.items())), flush=True)
         if rank == 0 and period and (it + 1) % period == 0:                   # hooks.PeriodicCheckpointer
             ckpt.save(f"model_{it:07d}", iteration=it)
+    if eval_hook is not None:
+        eval_hook.after_train()
     if rank == 0 and period:
         ckpt.save("model_final", iteration=max_iter - 1)
 
