@@ -1,0 +1,568 @@
+"""The training graph written plainly, for tests/test_graph_ref_host.py and tests/test_gpu_graph_exact.py; not a conftest, no tests.
+
+Every function here is a few torch operations (F.conv2d, F.avg_pool2d, relu, softmax, matmul) on NHWC activations and the same
+[Cout, Cin, KH, KW] parameters the nodes of cddmsl_amd/layers.py take, in whatever dtype its inputs have (float64 for the reference,
+float32 for the f32 limit).  Every gradient comes from torch.autograd: nothing below is derived by hand, so an error in a hand-written
+backward pass of layers.py cannot be shared by this file.
+
+Two options, on every function:
+  round_bf16   a model of bf16 noise: the inputs, the weights and the result of every convolution, pooling, ReLU, softmax and matrix
+               product (the token tensor and the mean pool's result as well) are rounded to bf16, and so are their gradients on
+               the way back; an affine or a sum in front of a ReLU is not rounded on its own.  The nodes fuse more than that.
+  drop=<name>  removes exactly ONE term (DROPS), through detach() or a straight-through pair (the forward value of one
+               expression, the gradient of another): what a wiring error in a node would compute.  The host test shows that every
+               such error moves a compared tensor by at least ten times its limit.
+
+The second half builds the inputs of a case of tests/graph_exact_cases.py (``make_inputs``), runs the plain module on them
+(``reference``) and derives the two limits of every compared tensor from the plain module's own float32 and rounded runs
+(``prepared``): nothing here looks at a result of the nodes."""
+import torch
+import torch.nn.functional as F
+
+import exact_roi as XR
+
+BF = torch.bfloat16
+F64 = torch.float64
+
+DROPS = ("conv_residual_grad", "conv_relu_mask", "conv_bias_grad", "block_down_path_dx", "block_pool_quarter", "block_mask_between",
+         "block_o2_mask", "block_scale_in_wgrad", "block_scale_in_dgrad", "roi_down_path_dfeat", "roi_extra_in_w1_grad",
+         "roi_dextra_pooled_path", "roi_bias_before_pool", "attn_mean_token_share", "attn_query_path", "attn_pos_grad_masked",
+         "attn_softmax_scale_bwd")
+
+F32_FACTOR, F32_FLOOR, F32_CAP = 8.0, 1e-6, 1e-4
+BF16_FACTOR, BF16_FLOOR, BF16_CAP = 4.0, 2.0 ** -8, 3e-2
+
+
+class _RoundBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        return t.to(BF).to(t.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(BF).to(g.dtype)
+
+
+def _r(t, on):
+    return _RoundBf16.apply(t) if on and t is not None else t
+
+
+def _grad_of(fwd, bwd):
+    """the value of ``fwd`` with the gradient of ``bwd``"""
+    return bwd + (fwd - bwd).detach()
+
+
+def _c(x, w, stride=1, pad=0):
+    if w.dim() == 2:
+        w = w[:, :, None, None]
+    return F.conv2d(x.permute(0, 3, 1, 2), w, stride=stride, padding=pad).permute(0, 2, 3, 1)
+
+
+def _avg(x, k):
+    """AvgPool2d(k) of an NHWC map: floor, as the reference's Bottleneck"""
+    return F.avg_pool2d(x.permute(0, 3, 1, 2), k).permute(0, 2, 3, 1) if k > 1 else x
+
+
+def _relu(z, straight):
+    return _grad_of(torch.relu(z), z) if straight else torch.relu(z)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the plain modules
+def conv(x, w, b=None, stride=1, pad=0, relu=False, residual=None, round_bf16=False, drop=None):
+    """relu?(conv(x, w) + b + residual); a 2-D ``w`` [N, K] is a linear layer over the last axis"""
+    rb = round_bf16
+    x, w, b, residual = _r(x, rb), _r(w, rb), _r(b, rb), _r(residual, rb)
+    z = _r(_c(x, w, stride, pad), rb)
+    if b is not None:
+        z = z + (b.detach() if drop == "conv_bias_grad" else b)
+    if residual is not None:
+        z = z + (residual.detach() if drop == "conv_residual_grad" else residual)
+    return _r(_relu(z, drop == "conv_relu_mask") if relu else z, rb)
+
+
+def fused_heads(x, heads, round_bf16=False, drop=None):
+    """heads: [(w, b)]: every head's 1x1 convolution of x, concatenated and zero-padded to a multiple of 8 columns"""
+    ys = [conv(x, w, b, round_bf16=round_bf16, drop=drop) for w, b in heads]
+    n = sum(y.shape[-1] for y in ys)
+    ys.append(torch.zeros(*x.shape[:-1], -n % 8, dtype=x.dtype))
+    return torch.cat(ys, dim=-1)
+
+
+def frozen_mlp(x, w1, b1, w2, b2, residual, round_bf16=False, drop=None):
+    """residual + W2 relu(W1 x + b1) + b2 on rows x [M, K]"""
+    M = x.shape[0]
+    h = conv(x.view(1, 1, M, -1), w1, b1, relu=True, round_bf16=round_bf16, drop=drop)
+    return conv(h, w2, b2, residual=residual.view(1, 1, M, -1), round_bf16=round_bf16, drop=drop).view(M, -1)
+
+
+def bottleneck(x, w, bn, stride, round_bf16=False, drop=None, last=True, parts=None):
+    """One Bottleneck in the literal order: conv1, affine, ReLU; conv2 3x3, affine, ReLU; AvgPool2d(stride); conv3, affine; plus the
+    identity or AvgPool2d -> conv -> affine; ReLU.  w = (w1, w2, w3, wd or None), bn = four (scale, bias).  -> (out, the pre-ReLU sum).
+    ``parts`` (roi_stage's drops): "c1" replaces conv1's result, "x_down" the downsample path's input, "idn" the path's result."""
+    rb = round_bf16
+    parts = parts or {}
+    (s1, b1), (s2, b2), (s3, b3), bnd = bn
+    w1, w2, w3, wd = (_r(v, rb) for v in w)
+    x = _r(x, rb)
+    c1 = parts["c1"] if "c1" in parts else _c(x, w1)
+    o1 = _r(torch.relu(_r(c1, rb) * s1 + b1), rb)
+    o2 = _r(_relu(_r(_c(o1, w2, pad=1), rb) * s2 + b2, drop == "block_o2_mask"), rb)
+    p2 = _r(_avg(o2, stride), rb)
+    c3 = _c(p2, w3) * s3
+    if drop == "block_scale_in_wgrad":
+        c3 = _grad_of(c3, _c(p2, w3.detach()) * s3 + _c(p2.detach(), w3))
+    elif drop == "block_scale_in_dgrad":
+        c3 = _grad_of(c3, _c(p2.detach(), w3) * s3 + _c(p2, w3.detach()))
+    z3 = _r(c3, rb) + b3
+    xd = parts.get("x_down", x)
+    if drop == "block_down_path_dx":
+        xd = xd.detach()
+    if "idn" in parts:
+        idn = parts["idn"]
+    elif wd is not None:
+        px = _avg(xd, stride)
+        if drop == "block_pool_quarter" and stride > 1:
+            px = _grad_of(px, px * float(stride * stride))
+        idn = _r(_c(_r(px, rb), wd), rb) * bnd[0] + bnd[1]
+    else:
+        idn = xd
+    pre = z3 + idn
+    return _r(_relu(pre, drop == "block_mask_between" and not last), rb), pre
+
+
+def stage(x, blocks, round_bf16=False, drop=None, parts=None):
+    """blocks: [dict(w, bn, stride)] -> (output, the last block's pre-ReLU sum)"""
+    pre = None
+    for i, b in enumerate(blocks):
+        x, pre = bottleneck(x, b["w"], b["bn"], b["stride"], round_bf16, drop, i + 1 == len(blocks), parts if i == 0 else None)
+    return x, pre
+
+
+def roi_crops(feat, rois, out_size, scale, sr):
+    """aligned RoIAlign of feat [N, H, W, C] from the separable float64 weight tables of tests/exact_roi.py: linear in feat, so
+    autograd differentiates it.  rois [K, 5] f32, grouped by image."""
+    N, H, W, _ = feat.shape
+    geo = XR.geometry(rois, H, W, out_size, out_size, scale, sr, True)
+    Ty, Tx, b = geo["y"]["T"].to(feat.dtype), geo["x"]["T"].to(feat.dtype), geo["b"]
+    assert bool((b[1:] >= b[:-1]).all()) and int(b.min()) >= 0 and int(b.max()) < N
+    per_image = []
+    for n in range(N):
+        ks = torch.nonzero(b == n).reshape(-1)
+        if ks.numel():
+            per_image.append(XR._pool(Ty[ks], Tx[ks], feat[n]))
+    return torch.cat(per_image)
+
+
+def roi_stage(feat, rois, blocks, extra=None, out_size=14, scale=1.0 / 16, sr=0, round_bf16=False, drop=None):
+    """stage(cat([roi_crops(feat), extra])): the literal order of the reference's RoI head, no convolution in front of the pooling"""
+    rb = round_bf16
+    feat, extra = _r(feat, rb), _r(extra, rb)
+    crop = lambda t: _r(roi_crops(t, rois, out_size, scale, sr), rb)
+    join = lambda a, e: a if e is None else torch.cat([a, e])
+    crops = crop(feat)
+    x = join(crops, extra)
+    b0, parts = blocks[0], {}
+    w1, wd = _r(b0["w"][0], rb), _r(b0["w"][3], rb)
+    if drop == "roi_down_path_dfeat":
+        parts["x_down"] = join(crop(feat.detach()), extra)
+    elif drop == "roi_dextra_pooled_path" and extra is not None:
+        parts["x_down"] = join(crops, extra.detach())
+    elif drop == "roi_extra_in_w1_grad" and extra is not None:
+        parts["c1"] = torch.cat([_c(crops, w1), _c(extra, w1.detach())])
+    elif drop == "roi_bias_before_pool":
+        sd, bd = b0["bn"][3]
+        idn = _avg(crop(_c(feat, wd) * sd + bd), b0["stride"])         # the affine on the map: samples outside it lose their bias
+        if extra is not None:
+            idn = torch.cat([idn, _c(_avg(extra, b0["stride"]), wd) * sd + bd])
+        parts["idn"] = idn
+    return stage(x, blocks, rb, drop, parts)
+
+
+def attnpool(x, p, heads, premask=False, round_bf16=False, drop=None):
+    """AttentionPool2d the long way: tokens = cat(mean, pixels) + pos; q, k, v projected for ALL tokens; softmax(q k^T / sqrt(D)); row
+    0; c_proj.  x [K, h, w, C]; p: dict pos [h w + 1, C], q_w q_b k_w k_b v_w v_b c_w c_b.  ``premask``: x is a ReLU output whose
+    producer expects its gradient masked by x > 0: the map passes through a ReLU here (the value is unchanged)."""
+    rb = round_bf16
+    K, h, w, C = x.shape
+    D = C // heads
+    p = {k: _r(v, rb) for k, v in p.items()}
+    x = _r(x, rb)
+    pix = (torch.relu(x) if premask else x).reshape(K, h * w, C)
+    mean = pix.mean(1, keepdim=True)
+    if drop == "attn_mean_token_share":
+        mean = mean.detach()
+    pos = p["pos"].unsqueeze(0)
+    if drop == "attn_pos_grad_masked" and premask:
+        m = torch.cat([torch.ones(K, 1, C, dtype=x.dtype), (pix > 0).to(x.dtype)], dim=1)
+        pos = pos.detach() + (pos - pos.detach()) * m
+    tok = _r(torch.cat([mean, pix], dim=1) + pos, rb)
+    lin = lambda t, n: _r(torch.matmul(t, p[n + "_w"].t()) + p[n + "_b"], rb)
+    split = lambda t: t.reshape(K, -1, heads, D).transpose(1, 2)                   # [K, heads, T, D]
+    q, k, v = split(lin(tok.detach() if drop == "attn_query_path" else tok, "q")), split(lin(tok, "k")), split(lin(tok, "v"))
+    s = _r(torch.matmul(q, k.transpose(2, 3)), rb)
+    s = _grad_of(s * D ** -0.5, s) if drop == "attn_softmax_scale_bwd" else s * D ** -0.5
+    o = _r(torch.matmul(_r(torch.softmax(s, dim=-1), rb), v), rb)                  # [K, heads, T, D]
+    o0 = o[:, :, 0].reshape(K, C)
+    return _r(torch.matmul(o0, p["c_w"].t()) + p["c_b"], rb)
+
+
+def mean_pool(x, round_bf16=False, drop=None):
+    return _r(_r(x, round_bf16).mean((1, 2)), round_bf16)
+
+
+# ---------------------------------------------------------------------------------------------------------------- inputs of a case
+def _bf(t):
+    """values a bf16 tensor holds, as float32: both dtypes of a case and every reference run see these exact numbers"""
+    return t.to(BF).to(torch.float32)
+
+
+ROIS = [[1, 24.0, 20.0, 120.0, 100.0],      # inside the 192 x 160 image (a 12 x 10 map at 1/16)
+        [1, -30.0, -20.0, 70.0, 90.0],      # over the left and the top border
+        [1, 100.0, 60.0, 230.0, 200.0],     # over the right and the bottom border
+        [1, 50.0, 50.0, 56.0, 58.0],        # 0.375 x 0.5 map pixels: smaller than a bin
+        [1, 0.0, 0.0, 192.0, 160.0],        # the whole map
+        [1, 40.0, 100.0, 150.0, 190.0]]     # over the bottom border alone
+ROI_START = [0, 0, 6]                       # image 0 has no RoI
+GATE = 0.25
+MARGIN = {"gated": 2.0 ** -6, "natural": 2.0 ** -18}
+
+
+def _side_bias(z, g, masks, first_sign=1.0):
+    """for pre-ReLU values z [..., C] without their bias -> (bias, the smallest |z + b| / (|z| + |b|) it leaves).  "gated": channel c's
+    values all land on one side of zero, a quarter of their range away from it, the side alternating by channel; "natural":
+    N(0, 0.3^2), as tests/test_gpu_three_passes.py draws it."""
+    C = z.shape[-1]
+    flat = z.reshape(-1, C)
+    if masks == "natural":
+        b = _bf(torch.randn(C, generator=g) * 0.3).to(z.dtype)
+    else:
+        lo, hi = flat.min(0).values, flat.max(0).values
+        up = torch.where(torch.arange(C) % 2 == 0, first_sign, -first_sign) > 0
+        b = _bf(torch.where(up, -lo, -hi) + torch.where(up, 1.0, -1.0) * (GATE * (hi - lo) + 2.0 ** -6 * (hi.abs() + lo.abs()))).to(z.dtype)
+    return b, float(((flat + b).abs() / (flat.abs() + b.abs())).min())
+
+
+def _make_blocks(g, cin, planes, strides, x, masks="gated"):
+    """Bottleneck parameters as tests/test_gpu_three_passes.py ``_blocks`` draws them (weights N(0, 1 / fan-in), scales in [0.5, 1.5)),
+    the first block with a downsample convolution -> (blocks, the stage's output, the smallest margin of its ReLUs).
+
+    The metric is max |error| / max |reference|, and one flipped ReLU mask bit is one whole term of a sum: a few per cent of a
+    gradient's maximum.  bf16 noise upstream moves a pre-ReLU value z = sum of terms by a few 2^-9 of sum |terms|, so among some
+    10^4 Gaussian values around zero a few flip at every seed, in the nodes and in the rounded model alike and at different
+    elements; no limit under the 3e-2 cap survives that, and it says nothing about the wiring.  So the cases that run in both
+    dtypes are "gated": the FrozenBN biases put all of a channel's pre-ReLU values on one side of zero, a quarter of their range
+    away (every |z| is then >= MARGIN["gated"] = 2^-6 of |scaled convolution| + |bias| + |identity|: eight half-ulps of bf16 at the
+    size of its terms), the side alternating by channel, conv2's the other way round than conv1's: half of all activations are exact
+    zeros, the masks of o1, o2 and the output differ, and a mask taken from the wrong tensor or dropped moves the gradients.
+    What a gated case cannot see is a mask read at the wrong PIXEL.  The "natural" cases (f32 only, where the noise is 2^-24 and
+    MARGIN["natural"] = 2^-18 is met by redrawing) keep N(0, 0.3^2) biases and masks that vary from pixel to pixel."""
+    x = x.to(F64)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    cw = lambda co, ci, k: _bf(rn(co, ci, k, k) * (ci * k * k) ** -0.5)
+    sc = lambda c: _bf(torch.rand(c, generator=g) + 0.5)
+    blocks, margin = [], 1.0
+    for bi, stride in enumerate(strides):
+        w = [cw(planes, cin, 1), cw(planes, planes, 3), cw(4 * planes, planes, 1), cw(4 * planes, cin, 1) if bi == 0 else None]
+        s = [sc(planes), sc(planes), sc(4 * planes), sc(4 * planes) if bi == 0 else None]
+        d = [None if v is None else v.to(F64) for v in w]
+        z1 = _c(x, d[0]) * s[0]
+        b1, m1 = _side_bias(z1, g, masks)
+        o1 = torch.relu(z1 + b1)
+        z2 = _c(o1, d[1], pad=1) * s[1]
+        b2, m2 = _side_bias(z2, g, masks, -1.0)
+        p2 = _avg(torch.relu(z2 + b2), stride)
+        z3 = _c(p2, d[2]) * s[2]
+        idn = _c(_avg(x, stride), d[3]) * s[3] if bi == 0 else x
+        # (the downsample path's bias: of the size of the values it is added to -- b3 below takes up its mean -- so that a bias that
+        # got lost with the weight of a RoI's samples outside the map, drop "roi_bias_before_pool", shows in the output)
+        bd = _bf(rn(4 * planes) * 2.0 * float((z3 + idn).std())) if bi == 0 else None
+        idn = idn + bd if bi == 0 else idn
+        b3, _ = _side_bias(z3 + idn, g, masks)
+        m3 = float(((z3 + idn + b3).abs() / (z3.abs() + idn.abs() + b3.abs())).min())
+        x = torch.relu(z3 + b3 + idn)
+        margin = min(margin, m1, m2, m3)
+        f32 = lambda v: v.to(torch.float32)
+        blocks.append(dict(w=w, bn=[(s[0], f32(b1)), (s[1], f32(b2)), (s[2], f32(b3)), (s[3], bd) if bi == 0 else None], stride=stride))
+        cin = 4 * planes
+    return blocks, x, margin
+
+
+def _attn_params(g, C, out, P):
+    rn = lambda *s: torch.randn(*s, generator=g)
+    p = dict(pos=_bf(rn(P + 1, C) * 0.5))
+    for n, o in (("q", C), ("k", C), ("v", C), ("c", out)):
+        p[n + "_w"], p[n + "_b"] = _bf(rn(o, C) * C ** -0.5), _bf(rn(o) * 0.1)
+    return p
+
+
+def _attract(p, x, heads, share):
+    """k_proj.weight += beta * (per head) qhat (x) that: a rank-one term that sends the mean token's direction ``that`` to the query's
+    direction ``qhat`` in every head, beta such that the mean token draws ``share`` of the attention on average (x [K, h, w, C] float64,
+    the pool's input).  A softmax over 50 tokens of N(0, 1) scores gives the mean token 1/50, and its share of the map's gradient (a
+    49th of its own) is a few per cent of the pixels' own: drop "attn_mean_token_share" would move dx by about twice its bf16 limit."""
+    K, h, w, C = x.shape
+    D = C // heads
+    pix = x.reshape(K, h * w, C)
+    tok = torch.cat([pix.mean(1, keepdim=True), pix], 1) + p["pos"].to(F64)
+    kw = p["k_w"].to(F64)
+    q0 = (tok[:, 0] @ p["q_w"].to(F64).t() + p["q_b"].to(F64)).reshape(K, 1, heads, D)
+    qhat = F.normalize(q0.mean(0).reshape(heads, D), dim=1)
+    that = F.normalize(tok[:, 0].mean(0), dim=0)
+    rank1 = (qhat.reshape(C, 1) * that.reshape(1, C))
+
+    def p0(beta):
+        k = (tok @ (kw + beta * rank1).t()).reshape(K, -1, heads, D)
+        return float(torch.softmax((q0 * k).sum(-1) * D ** -0.5, dim=1)[:, 0].mean())
+    lo, hi = 0.0, 1.0
+    while p0(hi) < share and hi < 1024:
+        hi *= 2
+    for _ in range(30):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if p0(mid) < share else (lo, mid)
+    p["k_w"] = _bf(kw + hi * rank1)
+
+
+def make_inputs(case, attempt=0):
+    """-> dict of CPU float32 tensors holding bf16 values (blocks: the list ``stage`` takes; p: attnpool's dict), drawn from the case's
+    seed + 1000 * attempt; "gy" is the gradient the output receives; "margin": the smallest margin of the plain module's ReLUs."""
+    inp, margin = _draw(case, torch.Generator().manual_seed(case["seed"] + 1000 * attempt))
+    inp["margin"], inp["attempt"] = margin, attempt
+    return inp
+
+
+def _draw(case, g):
+    rn = lambda *s: torch.randn(*s, generator=g)
+    k, masks = case["kind"], case.get("masks", "gated")
+    inp, margin = {}, 1.0
+    if k == "conv":
+        ws = tuple(case["w"])
+        fan = ws[1] * (ws[2] * ws[3] if len(ws) == 4 else 1)
+        inp["x"] = _bf(rn(*case["x"]))
+        inp["w"] = _bf(rn(*ws) * fan ** -0.5)
+        y = conv(inp["x"] if len(ws) == 4 else inp["x"].view(1, 1, *case["x"]), inp["w"], stride=case["stride"], pad=case["pad"])
+        if case["bias"]:
+            inp["b"] = _bf(rn(ws[0]) * 0.3)
+            if case["relu"]:
+                b, margin = _side_bias(y.to(F64), g, masks)
+                inp["b"] = b.to(torch.float32)
+        yshape = y.shape if len(ws) == 4 else y.shape[2:]
+        if case["residual"]:
+            inp["res"] = _bf(rn(*yshape))
+        inp["gy"] = _bf(rn(*yshape))
+    elif k == "heads":
+        inp["x"] = _bf(rn(*case["x"]))
+        C = case["x"][-1]
+        for i, n in enumerate(case["widths"]):
+            inp[f"w{i}"] = _bf(rn(n, C, 1, 1) * C ** -0.5) if case["w4d"] else _bf(rn(n, C) * C ** -0.5)
+            inp[f"b{i}"] = _bf(rn(n) * 0.3)
+        inp["gy"] = _bf(rn(*case["x"][:-1], (sum(case["widths"]) + 7) // 8 * 8))
+    elif k == "mlp":
+        M, K, Hd = case["rows"], case["width"], case["hidden"]
+        inp.update(x=_bf(rn(M, K)), w1=_bf(rn(Hd, K) * K ** -0.5), w2=_bf(rn(K, Hd) * Hd ** -0.5), b2=_bf(rn(K) * 0.3), res=_bf(rn(M, K)), gy=_bf(rn(M, K)))
+        b1, margin = _side_bias(inp["x"].to(F64) @ inp["w1"].to(F64).t(), g, masks)
+        inp["b1"] = b1.to(torch.float32)
+    elif k in ("stage", "halves"):
+        inp["x"] = _bf(rn(*case["x"]).clamp_min(0))
+        if k == "halves":
+            inp["xb"] = _bf(rn(*case["x"]).clamp_min(0))
+        both = torch.cat([inp["x"], inp["xb"]]) if k == "halves" else inp["x"]
+        inp["blocks"], y, margin = _make_blocks(g, case["x"][-1], case["planes"], case["strides"], both, masks)
+        inp["gy"] = _bf(rn(*y.shape))
+    elif k == "roi":
+        inp["feat"] = _bf(rn(*case["feat"]).clamp_min(0))
+        inp["rois"] = torch.tensor(ROIS, dtype=torch.float32)
+        C = case["feat"][-1]
+        if case["extra"] != "none":
+            inp["extra"] = _bf(rn(2, 14, 14, C).clamp_min(0) * 0.7)
+        x0 = roi_crops(inp["feat"].to(F64), inp["rois"], 14, 1.0 / 16, 0)
+        x0 = torch.cat([x0, inp["extra"].to(F64)]) if "extra" in inp else x0
+        inp["blocks"], y, margin = _make_blocks(g, C, case["planes"], case["strides"], x0, masks)
+        inp["gy"] = _bf(rn(*y.shape))
+    elif k == "attn":
+        K_, h, w, C = case["x"]
+        if case["stage"]:
+            inp["x"] = _bf(rn(*case["stage"]["x"]).clamp_min(0))
+            inp["blocks"], y, margin = _make_blocks(g, case["stage"]["x"][-1], case["stage"]["planes"], case["stage"]["strides"], inp["x"], masks)
+        else:
+            inp["x"] = _bf(rn(*case["x"]).clamp_min(0)) if case["premask"] else _bf(rn(*case["x"]))
+        inp["p"] = _attn_params(g, C, case["out"], h * w)
+        if case["stage"]:
+            # The pool's input is the stage's output, not N(0, 1), and not exact: it is rounded on the way, by 2^-9 of values whose
+            # channel mean is several times their spread, and the query path (softmax backward: dp - sum p dp) sees that error
+            # against the tokens' spread alone.  The positional embedding is exact, so it carries most of a token's spread here (five
+            # times the other cases' share); the projections are scaled to tokens of that size.
+            size = 5.0 * float(y.pow(2).mean().sqrt())
+            inp["p"].update(pos=_bf(inp["p"]["pos"] * size), **{n: _bf(inp["p"][n] / size) for n in ("q_w", "k_w", "v_w")})
+        if case.get("mean_share"):
+            _attract(inp["p"], inp["x"].to(F64), case["heads"], case["mean_share"])
+        inp["gy"] = _bf(rn(K_, case["out"]))
+    elif k == "meanpool":
+        inp["x"] = _bf(rn(*case["x"]))
+        inp["gy"] = _bf(rn(case["x"][0], case["x"][-1]))
+    else:
+        raise KeyError(k)
+    return inp, margin
+
+
+def compared(case):
+    """names of the tensors a case compares: "y", the gradient of an input as "d<name>", of a parameter under its own name"""
+    k = case["kind"]
+    blk = lambda strides: [f"b{bi}.w{wi}" for bi in range(len(strides)) for wi in range(4) if wi < 3 or bi == 0]
+    ap = ["pos", "q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "c_w", "c_b"]
+    if k == "conv":
+        return ["y"] + ["dx"] * case["x_grad"] + ["dres"] * bool(case["residual"]) + (["w"] + ["b"] * case["bias"]) * case["train_w"]
+    if k == "heads":
+        return ["y", "dx"] + [f"{n}{i}" for i in range(len(case["widths"])) for n in "wb"]
+    if k == "mlp":
+        return ["y", "dx", "dres"]
+    if k == "stage":
+        return ["y"] + ["dx"] * case["x_grad"] + blk(case["strides"])
+    if k == "halves":
+        return ["y", "dx", "dxb"] + blk(case["strides"])
+    if k == "roi":
+        return ["y"] + ["dfeat"] * case["feat_grad"] + ["dextra"] * (case["extra"] == "grad") + blk(case["strides"])
+    if k == "attn":
+        return ["y"] + ["dx"] * case["x_grad"] + ap * (not case["frozen"]) + (blk(case["stage"]["strides"]) if case["stage"] else [])
+    if k == "meanpool":
+        return ["y", "dx"]
+    raise KeyError(k)
+
+
+def drops_for(case):
+    """the ``drop`` names that remove a term this case has"""
+    k = case["kind"]
+    if k == "conv":
+        return ["conv_residual_grad"] * bool(case["residual"]) + ["conv_relu_mask"] * case["relu"] + ["conv_bias_grad"] * (case["bias"] and case["train_w"])
+    if k == "mlp":
+        return ["conv_residual_grad", "conv_relu_mask"]
+    if k in ("stage", "halves", "roi") or (k == "attn" and case["stage"]):
+        strides = case["stage"]["strides"] if k == "attn" else case["strides"]
+        x_grad = case["feat_grad"] if k == "roi" else case.get("x_grad", True)
+        d = ["block_o2_mask", "block_scale_in_wgrad", "block_scale_in_dgrad"] + ["block_mask_between"] * (len(strides) > 1)
+        if k != "roi":
+            d += ["block_down_path_dx"] * x_grad + ["block_pool_quarter"] * (x_grad and strides[0] > 1)
+        else:
+            d += ["roi_bias_before_pool"] + ["roi_down_path_dfeat"] * x_grad + ["roi_extra_in_w1_grad"] * (case["extra"] != "none") \
+                + ["roi_dextra_pooled_path"] * (case["extra"] == "grad")
+        return d + (["attn_softmax_scale_bwd"] if k == "attn" else [])
+    if k == "attn":
+        # (the query path reaches the map only through the mean token's share; where no parameter gradient is compared it is that term)
+        return ["attn_softmax_scale_bwd"] + ["attn_mean_token_share"] * case["x_grad"] + ["attn_query_path"] * (case["x_grad"] and not case["frozen"]) \
+            + ["attn_pos_grad_masked"] * (case["premask"] and not case["frozen"])
+    return []
+
+
+def drop_dtypes(case, drop):
+    """the dtypes in whose limit a drop must show ten times over: those the case runs in -- but "attn_mean_token_share" in bf16 only
+    where the case's data let the mean token draw most of the attention (``mean_share``: a frozen pool, which compares the output
+    and dx alone).  With N(0, 1) scores that token gets 1/50 of the attention and hands a 49th of its gradient to each pixel: 2 to 4
+    times dx's bf16 limit, which bf16 cannot tell from noise; drawing the attention to it puts the trainable pool's query-path
+    gradients (q_proj, k_proj: a softmax backward that cancels) above the 3e-2 cap at every draw tried.  f32 sees it 10^3 times over."""
+    if drop == "attn_mean_token_share" and not case.get("mean_share"):
+        return ("f32",)
+    return case["dtypes"]
+
+
+def reference(case, inp, dtype=F64, round_bf16=False, drop=None):
+    """the plain module on the case's inputs -> {name: tensor} over ``compared(case)``; a gradient autograd never produced (its one
+    term dropped) is zero"""
+    k = case["kind"]
+    kw = dict(round_bf16=round_bf16, drop=drop)
+    leaves = {}
+
+    def leaf(name, t, grad=True):
+        v = t.to(dtype).clone().requires_grad_(grad)
+        if grad:
+            leaves[name] = v
+        return v
+
+    def blocks_of(bl, train=True):
+        out = []
+        for bi, b in enumerate(bl):
+            w = [None if v is None else leaf(f"b{bi}.w{wi}", v, train) for wi, v in enumerate(b["w"])]
+            out.append(dict(w=w, bn=[None if v is None else (v[0].to(dtype), v[1].to(dtype)) for v in b["bn"]], stride=b["stride"]))
+        return out
+    target = None
+    if k == "conv":
+        x = leaf("dx", inp["x"], case["x_grad"])
+        w = leaf("w", inp["w"], case["train_w"])
+        b = leaf("b", inp["b"], case["train_w"]) if case["bias"] else None
+        res = leaf("dres", inp["res"]) if case["residual"] else None
+        if len(case["w"]) == 2:
+            M = x.shape[0]
+            y = conv(x.view(1, 1, M, -1), w, b, relu=case["relu"], residual=None if res is None else res.view(1, 1, M, -1), **kw).view(M, -1)
+        else:
+            y = conv(x, w, b, case["stride"], case["pad"], case["relu"], res, **kw)
+    elif k == "heads":
+        x = leaf("dx", inp["x"])
+        y = fused_heads(x, [(leaf(f"w{i}", inp[f"w{i}"]), leaf(f"b{i}", inp[f"b{i}"])) for i in range(len(case["widths"]))], **kw)
+    elif k == "mlp":
+        c = lambda n: inp[n].to(dtype)
+        y = frozen_mlp(leaf("dx", inp["x"]), c("w1"), c("b1"), c("w2"), c("b2"), leaf("dres", inp["res"]), **kw)
+    elif k == "stage":
+        y, pre = stage(leaf("dx", inp["x"], case["x_grad"]), blocks_of(inp["blocks"]), **kw)
+        target = pre if case["premasked"] else y
+    elif k == "halves":
+        bl = blocks_of(inp["blocks"])
+        y = torch.cat([stage(leaf("dx", inp["x"]), bl, **kw)[0], stage(leaf("dxb", inp["xb"]), bl, **kw)[0]])
+    elif k == "roi":
+        extra = leaf("dextra", inp["extra"], case["extra"] == "grad") if "extra" in inp else None
+        y, _ = roi_stage(leaf("dfeat", inp["feat"], case["feat_grad"]), inp["rois"], blocks_of(inp["blocks"]), extra, **kw)
+    elif k == "attn":
+        x = leaf("dx", inp["x"], case["x_grad"])
+        p = {n: leaf(n, v, not case["frozen"]) for n, v in inp["p"].items()}
+        if case["stage"]:
+            x, _ = stage(x, blocks_of(inp["blocks"]), **kw)
+        y = attnpool(x, p, case["heads"], case["premask"], **kw)
+    elif k == "meanpool":
+        y = mean_pool(leaf("dx", inp["x"]), **kw)
+    (y if target is None else target).backward(inp["gy"].to(dtype))
+    out = {"y": y.detach()}
+    for n in compared(case)[1:]:
+        out[n] = leaves[n].grad if leaves[n].grad is not None else torch.zeros_like(leaves[n])
+    return {n: v.to(F64) for n, v in out.items()}
+
+
+def rel_err(got, ref):
+    """max |got - ref| / max |ref|, the metric of tests/test_gpu_e2e.py and tests/test_gpu_golden.py; ``ref`` must not be all zero"""
+    ref = ref.to(F64)
+    return float((got.detach().to("cpu", F64).reshape(ref.shape) - ref).abs().max()) / float(ref.abs().max())
+
+
+_cache = {}
+ATTEMPTS = 12
+
+
+def prepared(case):
+    """-> (inputs, float64 reference, {name: (f32 limit, bf16 limit)}), once per case.  The draw: the first of seed, seed + 1000, ...
+    whose ReLUs have their margin (``_make_blocks``) and whose limits are under their caps -- the bf16 cap of 3e-2 is 4 times
+    3.8 half-ulps of bf16 at the tensor's largest element, and a Bottleneck's output alone is rounded three times on the way (conv3,
+    the downsample path, the sum), so about one draw in three lies above it; both are properties of the plain module alone.  If
+    no draw qualifies the last one is returned, and the host test fails on its caps.  f32: 8 times the error of the plain module run
+    in float32 on the CPU (the GPU sums in other orders), floor 1e-6.  bf16: 4 times the error of the plain module with round_bf16
+    (the nodes round at fewer places), floor 2^-8.  A tensor whose reference is exactly zero (k_proj.bias) has no limit: it must be
+    exactly zero."""
+    for attempt in range(ATTEMPTS if case["name"] not in _cache else 0):
+        inp = make_inputs(case, attempt)
+        if inp["margin"] < MARGIN[case.get("masks", "gated")]:
+            continue
+        ref = reference(case, inp)
+        threads = torch.get_num_threads()
+        torch.set_num_threads(1)          # (float32 sums in an order that does not depend on how many cores the machine has)
+        try:
+            r32 = reference(case, inp, dtype=torch.float32)
+        finally:
+            torch.set_num_threads(threads)
+        rbf = reference(case, inp, round_bf16=True)
+        lim = {}
+        for n, v in ref.items():
+            if n == "k_b":
+                assert float(v.abs().max()) <= 1e-12 * float(ref["q_b"].abs().max())      # (float64 roundoff of an exact zero)
+                lim[n] = None
+            else:
+                lim[n] = (max(F32_FACTOR * rel_err(r32[n], v), F32_FLOOR), max(BF16_FACTOR * rel_err(rbf[n], v), BF16_FLOOR))
+        _cache[case["name"]] = (inp, ref, lim)
+        if all(v is None or (v[0] <= F32_CAP and (v[1] <= BF16_CAP or "bf16" not in case["dtypes"])) for v in lim.values()):
+            break
+    assert case["name"] in _cache, f"{case['name']}: no draw with the ReLU margin"
+    return _cache[case["name"]]
