@@ -2,8 +2,10 @@
 
 ``PascalVOCDetectionEvaluator`` keeps the reference's protocol: ``reset()``, ``process(inputs, outputs)`` per batch,
 ``evaluate()`` on every rank (predictions are gathered to rank 0) returning
-``{"bbox": {"AP", "AP50", "AP75", "AP50-<class>"...}}`` with AP in percent: VOC07 11-point AP for year 2007, area under
-the monotone precision envelope otherwise, averaged over IoU thresholds 0.50:0.05:0.95 for "AP".
+``{"bbox": {"AP", "AP50", "AP75", "AP50-<class>"..., "AP50-present", "AP-present"}}`` with AP in percent: VOC07 11-point AP for
+year 2007, area under the monotone precision envelope otherwise, averaged over IoU thresholds 0.50:0.05:0.95 for "AP"; the two
+"-present" keys are the AP50 / AP means over the classes that have a non-difficult ground-truth box in the set.  With ``device``
+the matching runs on the GPU (cddmsl_voc_match) and the dictionary is the same, value for value.
 
 Details that decide the numbers and are therefore kept exactly:
 * a detection is serialised the way the reference writes its result files -- score to 3 decimals, box to 1 decimal, with
@@ -82,20 +84,172 @@ def class_ap(image_ids, confidence, boxes, gt_by_image, ovthresh, use_07_metric)
     return average_precision(rec, prec, use_07_metric)
 
 
+VOC_IOU_THRS = tuple(range(50, 100, 5))              # percent; the walk compares with t / 100.0
+
+
+def voc_round_boxes(boxes):
+    """f32 XYXY [D, 4] -> f64 [D, 4]: what the reference's result line ``{xmin:.1f} {ymin:.1f} {xmax:.1f} {ymax:.1f}`` (with + 1 on
+    xmin / ymin, an f32 addition) reads back as -- ``float(f"{x0 + 1:.1f}")`` without the text.  An f32 times 10 is exact in f64,
+    Python's formatting rounds the exact value half-even like ``rint``, and the division is the nearest double, which is what
+    ``float("...")`` returns.  cddmsl_voc_match does the same per detection."""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    out = np.empty(b.shape, dtype=np.float64)
+    out[:, :2] = np.rint((b[:, :2] + np.float32(1.0)).astype(np.float64) * 10.0) / 10.0
+    out[:, 2:] = np.rint(b[:, 2:].astype(np.float64) * 10.0) / 10.0
+    return out
+
+
+def voc_round_scores(scores):
+    """f32 [D] -> f64 [D]: ``float(f"{s:.3f}")`` without the text (see ``voc_round_boxes``)"""
+    return np.rint(np.asarray(scores, dtype=np.float32).astype(np.float64) * 1000.0) / 1000.0
+
+
+def voc_accumulate(tp_bits, fp_bits, npos, use_07_metric, num_thrs=len(VOC_IOU_THRS)):
+    """The second half of ``class_ap`` for all thresholds of one class: ``tp_bits`` / ``fp_bits`` [n] hold the walk's flags of the
+    class's detections IN RANK ORDER (bit t = threshold t) -> [AP at threshold t].  Cumulative sums of 0 / 1 flags are exact and
+    ``rec`` / ``prec`` / ``average_precision`` are ``class_ap``'s expressions, so the values are equal to its, not close."""
+    sh = np.arange(num_thrs, dtype=np.int64)[:, None]
+    tp = np.cumsum(((np.asarray(tp_bits).astype(np.int64)[None, :] >> sh) & 1).astype(np.float64), axis=1)
+    fp = np.cumsum(((np.asarray(fp_bits).astype(np.int64)[None, :] >> sh) & 1).astype(np.float64), axis=1)
+    rec = tp / float(npos) if npos else tp * np.nan
+    prec = tp / np.maximum(tp + fp, np.finfo(np.float64).eps)
+    return [average_precision(rec[t], prec[t], use_07_metric) for t in range(num_thrs)]
+
+
+def voc_segments(cls, img, conf, class_ids, n_images):
+    """How ``class_ap`` visits the gathered detections, as cddmsl_voc_match wants it: per class of ``class_ids`` the rank order
+    ``np.argsort(-conf)`` over the class's detections in processing order (the same call on the same values as ``class_ap``'s, so
+    equal rounded scores fall the same way), then a stable partition of that order by image.
+    -> (ranked {class: detection indices in rank order}, perm int64 [P], seg_off int64 [S + 1], seg_gt int64 [S] = class * n_images +
+    image index)."""
+    ranked, perm, seg_len, seg_gt = {}, [], [], []
+    for cid in class_ids:
+        sel = np.flatnonzero(cls == cid)
+        r = sel[np.argsort(-np.ascontiguousarray(conf[sel], dtype=np.float64))]
+        ranked[cid] = r
+        if not r.size:
+            continue
+        seg = r[np.argsort(img[r], kind="stable")]
+        im = img[seg]
+        starts = np.flatnonzero(np.concatenate([[True], im[1:] != im[:-1]]))
+        perm.append(seg)
+        seg_len.append(np.diff(np.concatenate([starts, [len(seg)]])))
+        seg_gt.append(cid * n_images + im[starts])
+    cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
+    seg_off = np.concatenate([[0], np.cumsum(cat(seg_len))]).astype(np.int64)
+    return ranked, cat(perm), seg_off, cat(seg_gt)
+
+
+def merge_voc_records(parts):
+    """the ranks' (boxes, scores, classes, image indices) -> one set, in rank order and inside a rank in processing order: the order
+    ``merged[c].extend(lines)`` gives the host path's per-class lists"""
+    parts = [p for p in parts if p is not None]
+    return tuple(np.concatenate([np.asarray(p[k]) for p in parts]) for k in range(4))
+
+
 class PascalVOCDetectionEvaluator:
-    def __init__(self, dirname, split, year, class_names=VOC_CLASS_NAMES, target_classnames=None):
+    """``device``: a GPU device moves the matching there (cddmsl_voc_match).  ``process`` keeps each call's detections on the
+    device -- no copy to the host, no synchronisation; ``evaluate`` reads them back in ONE copy per rank, gathers the arrays to
+    rank 0 in rank order and processing order (the order the host path's per-class lists have), sorts per class on the host with
+    ``class_ap``'s own call, matches every (class, image) at all ten thresholds in ONE launch and accumulates with
+    ``voc_accumulate``.  Same dictionary as without ``device``, value for value.  The ground truth is parsed once per evaluator."""
+
+    def __init__(self, dirname, split, year, class_names=VOC_CLASS_NAMES, target_classnames=None, device=None):
         assert year in (2007, 2012), year
         self.anno = os.path.join(dirname, "Annotations", "{}.xml")
         self.image_set = os.path.join(dirname, "ImageSets", "Main", split + ".txt")
         self.class_names = list(class_names)
         self.target_classnames = list(target_classnames) if target_classnames is not None else list(class_names)
         self.is_2007 = year == 2007
+        self.device = torch.device(device) if device is not None and torch.device(device).type != "cpu" else None
+        self._gt, self._gt_dev = None, None
         self.reset()
 
     def reset(self):
         self._predictions = defaultdict(list)        # class id -> [(image_id, score, xmin, ymin, xmax, ymax)] as written
+        self._batches = []                           # device path: (image index, [n, 6] int32 rows still on the device) per image
+
+    def _ground_truth(self):
+        """-> (image names, per class {image name: (bbox [G,4] float, difficult [G] bool)}), parsed once"""
+        if self._gt is None:
+            with open(self.image_set) as f:
+                image_names = [l.strip() for l in f.readlines()]
+            recs = {n: read_voc_objects(self.anno.format(n)) for n in image_names}
+            per_class = []
+            for cname in self.class_names:
+                gt = {}
+                for n in image_names:
+                    objs = [o for o in recs[n] if o["name"] == cname]
+                    gt[n] = (np.array([o["bbox"] for o in objs], dtype=float).reshape(-1, 4), np.array([o["difficult"] for o in objs], dtype=bool))
+                per_class.append(gt)
+            self._gt = (image_names, per_class)
+        return self._gt
+
+    def _device_ground_truth(self):
+        """-> (image id -> index in the image-set file's order, hip.VocGroundTruth), uploaded once"""
+        if self._gt_dev is None:
+            from . import hip
+            image_names, per_class = self._ground_truth()
+            rows = [gt[n] for gt in per_class for n in image_names]             # row = class * n_images + image index
+            self._gt_dev = ({n: i for i, n in enumerate(image_names)},
+                            hip.VocGroundTruth.from_host(rows, [t / 100.0 for t in VOC_IOU_THRS], self.device))
+        return self._gt_dev
+
+    def _process_device(self, inputs, outputs):
+        index = self._device_ground_truth()[0]
+        for inp, out in zip(inputs, outputs):
+            i = index[str(inp["image_id"])]          # an image outside the set: KeyError (the host path raises it in evaluate)
+            inst = out["instances"]
+            b, s, c = inst.pred_boxes.tensor.detach(), inst.scores.detach(), inst.pred_classes.detach()
+            if b.dtype != torch.float32 or s.dtype != torch.float32:
+                raise TypeError(f"PascalVOCDetectionEvaluator(device=...): detections must be f32, got boxes {b.dtype}, scores {s.dtype}")
+            b, s, c = (t.to(self.device, non_blocking=True) for t in (b, s, c))
+            rows = torch.cat([b.reshape(-1, 4).view(torch.int32), s.reshape(-1, 1).view(torch.int32), c.reshape(-1, 1).to(torch.int32)], dim=1)
+            self._batches.append((i, rows))
+
+    def _device_records(self):
+        """the ONE readback -> (boxes f32 [n,4], scores f32 [n], classes int64 [n], image indices int64 [n]) in processing order"""
+        if not self._batches:
+            return np.zeros((0, 4), dtype=np.float32), np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        tab = torch.cat([r for _, r in self._batches]).cpu().numpy()
+        img = np.repeat(np.array([i for i, _ in self._batches], dtype=np.int64), [len(r) for _, r in self._batches])
+        return (np.ascontiguousarray(tab[:, :4]).view(np.float32), np.ascontiguousarray(tab[:, 4]).view(np.float32),
+                tab[:, 5].astype(np.int64), img)
+
+    def _gathered_records(self):
+        import torch.distributed as dist
+        rec = self._device_records()
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return rec
+        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+        dist.gather_object(rec, parts, dst=0)
+        if dist.get_rank() != 0:
+            return None
+        return merge_voc_records(parts)
+
+    def _match_device(self, rec, class_ids):
+        """rank 0: one upload, ONE launch for all classes and thresholds, one readback -> {class: (tp bits, fp bits) in rank order}"""
+        from . import hip
+        from ._lib import to_device_async
+        boxes, scores, cls, img = rec
+        n_images = len(self._ground_truth()[0])
+        ranked, perm, seg_off, seg_gt = voc_segments(cls, img, voc_round_scores(scores), class_ids, n_images)
+        D, P, S = len(boxes), len(perm), len(seg_gt)
+        if P == 0:
+            return {c: (np.zeros(0, dtype=np.uint16), np.zeros(0, dtype=np.uint16)) for c in class_ids}
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+        buf = to_device_async(torch.from_numpy(np.concatenate([boxes.reshape(-1).view(np.int64), perm, seg_off, seg_gt])), self.device)
+        tp, fp, bad = hip.voc_match(buf[: 2 * D].view(torch.float32).view(D, 4), buf[2 * D: 2 * D + P], buf[2 * D + P: 2 * D + P + S + 1],
+                                    buf[2 * D + P + S + 1:], self._device_ground_truth()[1])
+        host = torch.cat([tp.to(torch.int32), fp.to(torch.int32), bad]).cpu().numpy()
+        if host[2 * D:].any():
+            raise RuntimeError("cddmsl_voc_match refused a segment the evaluator built: inconsistent offsets")
+        tp, fp = (host[:D] & 0xFFFF).astype(np.uint16), (host[D: 2 * D] & 0xFFFF).astype(np.uint16)
+        return {c: (tp[r], fp[r]) for c, r in ranked.items()}
 
     def process(self, inputs, outputs):
+        if self.device is not None:
+            return self._process_device(inputs, outputs)
         for inp, out in zip(inputs, outputs):
             inst = out["instances"]
             boxes = inst.pred_boxes.tensor.detach().cpu().numpy()
@@ -121,31 +275,46 @@ class PascalVOCDetectionEvaluator:
         return merged
 
     def evaluate(self):
+        if self.device is not None:
+            rec = self._gathered_records()
+            return None if rec is None else self.evaluate_records(rec)
         preds = self._gathered()
-        if preds is None:
-            return None
-        with open(self.image_set) as f:
-            image_names = [l.strip() for l in f.readlines()]
-        recs = {n: read_voc_objects(self.anno.format(n)) for n in image_names}
-        aps = defaultdict(list)
-        for cid, cname in enumerate(self.class_names):
-            if cname not in self.target_classnames:
+        return None if preds is None else self._evaluate(preds, None)
+
+    def evaluate_records(self, rec):
+        """the device path's rank-0 half on gathered records (``_device_records`` of one rank, or ``merge_voc_records`` of several)"""
+        return self._evaluate(None, rec)
+
+    def _evaluate(self, preds, rec):
+        _, per_class = self._ground_truth()
+        class_ids = [cid for cid, cname in enumerate(self.class_names) if cname in self.target_classnames]
+        if rec is not None:
+            flags = self._match_device(rec, class_ids)
+        aps, npos = defaultdict(list), []
+        for cid in class_ids:
+            gt = per_class[cid]
+            npos.append(sum(int((~d).sum()) for _, d in gt.values()))
+            if rec is not None:
+                for thresh, ap in zip(VOC_IOU_THRS, voc_accumulate(*flags[cid], npos[-1], self.is_2007)):
+                    aps[thresh].append(ap * 100)
                 continue
-            gt = {}
-            for n in image_names:
-                objs = [o for o in recs[n] if o["name"] == cname]
-                gt[n] = (np.array([o["bbox"] for o in objs], dtype=float).reshape(-1, 4), np.array([o["difficult"] for o in objs], dtype=bool))
             lines = preds.get(cid, [])
             ids = [l[0] for l in lines]
             conf = np.array([l[1] for l in lines], dtype=float)
             bbs = np.array([l[2:] for l in lines], dtype=float).reshape(-1, 4)
-            for thresh in range(50, 100, 5):
+            for thresh in VOC_IOU_THRS:
                 aps[thresh].append(class_ap(ids, conf, bbs, gt, thresh / 100.0, self.is_2007) * 100)
         mean = {t: float(np.mean(v)) for t, v in aps.items()}
         ret = OrderedDict()
         ret["bbox"] = {"AP": float(np.mean(list(mean.values()))), "AP50": mean[50], "AP75": mean[75]}
         for i, name in enumerate(self.target_classnames):
             ret["bbox"]["AP50-" + name] = aps[50][i]
+        # the same means over the classes the set annotates (at least one non-difficult box): Watercolor and Comic annotate 6 of the
+        # 20 classes, and with the 2012 metric a class without positives is a NaN that the means above keep, as the reference does
+        present = [i for i, n in enumerate(npos) if n > 0]
+        over = {t: float(np.mean([v[i] for i in present])) if present else float("nan") for t, v in aps.items()}
+        ret["bbox"]["AP50-present"] = over[50]
+        ret["bbox"]["AP-present"] = float(np.mean(list(over.values())))
         return ret
 
 
@@ -558,21 +727,40 @@ class COCODetectionEvaluator:
         return {"bbox": res}
 
 
+_VOC_EVALUATORS = {}            # (name, datasets root, device) -> PascalVOCDetectionEvaluator of run_eval_only_catalog
+
+
 def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_results=False, prefix=""):
     """``--eval-only --datasets-root DIR``: every ``cfg.DATASETS.TEST`` name the catalog knows -- the Cityscapes splits of
-    cddmsl_amd/cityscapes.py and the COCO-json sets of cddmsl_amd/coco_json.py (``bdd_100k_val``) -> COCO-style box AP, one printed
-    line per set from rank 0 (each starting with ``prefix``); a name the catalog does not know, or a json set whose file is not
-    there, is skipped with one printed line.  The matching runs on ``cfg.MODEL.DEVICE`` (COCODetectionEvaluator's ``device``).
+    cddmsl_amd/cityscapes.py and the COCO-json sets of cddmsl_amd/coco_json.py (``bdd_100k_val``) -> COCO-style box AP; the VOC
+    family of cddmsl_amd/voc_catalog.py (``voc_2007_test``, ``Clipart1k_test`` ...) -> Pascal VOC AP with the set's year's metric.
+    One printed line per set from rank 0 (each starting with ``prefix``); a name the catalog does not know, or a set whose json /
+    image-set file is not there, is skipped with one printed line.  The matching runs on ``cfg.MODEL.DEVICE`` (the evaluators' ``device``).
     Returns the exit code (or {name: result dict} on rank 0 with ``return_results``)."""
     import torch.distributed as dist
-    from . import cityscapes, coco_json
+    from . import cityscapes, coco_json, voc_catalog
     from .data import build_detection_test_loader
     ws = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     assert world == ws, f"run_eval_only_catalog: world={world} but the process group has {ws} ranks"
     results = OrderedDict()
     for name in cfg.DATASETS.TEST:
+        voc = None
         if cityscapes.is_cityscapes(name):
             dicts, classes = cityscapes.load_cityscapes(name, datasets_root, device=cfg.MODEL.DEVICE), cityscapes.THING_CLASSES
+        elif voc_catalog.is_voc_family(name):
+            set_file = voc_catalog.image_set_file(name, datasets_root)
+            if not os.path.exists(set_file):
+                if rank == 0:
+                    print(f"{prefix}skipping {name}: {set_file} not found")
+                continue
+            if num_test_classes(model, cfg) != len(VOC_CLASS_NAMES):
+                raise ValueError(f"{name}: a VOC-family set has {len(VOC_CLASS_NAMES)} classes but the model's detections have {num_test_classes(model, cfg)}")
+            dicts, classes = voc_catalog.load_voc_family(name, datasets_root), VOC_CLASS_NAMES
+            key = (name, os.path.abspath(datasets_root), str(cfg.MODEL.DEVICE))
+            if key not in _VOC_EVALUATORS:          # kept like the catalog's dicts: a periodic evaluation parses and uploads the ground truth once
+                dirname, split, year, _ = voc_catalog.voc_entry(name, datasets_root)
+                _VOC_EVALUATORS[key] = PascalVOCDetectionEvaluator(dirname, split, year, VOC_CLASS_NAMES, device=cfg.MODEL.DEVICE)
+            voc = _VOC_EVALUATORS[key]
         elif coco_json.is_coco_json(name):
             json_file = coco_json.coco_json_paths(name, datasets_root)[0]
             if not os.path.exists(json_file):
@@ -587,13 +775,14 @@ def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_res
                 print(f"{prefix}skipping {name}: not in the dataset catalog")
             continue
         loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
-        res = inference_on_dataset(model, loader, COCODetectionEvaluator(dicts, classes, device=cfg.MODEL.DEVICE))
+        new_evaluator = (lambda: voc) if voc is not None else (lambda: COCODetectionEvaluator(dicts, classes, device=cfg.MODEL.DEVICE))
+        res = inference_on_dataset(model, loader, new_evaluator())
         if rank == 0:
             print(f"{prefix}{name}: " + str({k: round(v, 4) for k, v in res["bbox"].items()}), flush=True)
             results[name] = res
         if tta_enabled(cfg):
             loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
-            tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, COCODetectionEvaluator(dicts, classes, device=cfg.MODEL.DEVICE)))
+            tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, new_evaluator()))
             if rank == 0:
                 print(f"{prefix}{name}: " + str({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()}), flush=True)
                 results[name].update(tta)

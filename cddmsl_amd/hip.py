@@ -62,6 +62,7 @@ def _L():
         L.cddmsl_nms_anyorder.argtypes = [vp] * 4 + [ci, cf, vp, vp, vp]
         L.cddmsl_soft_nms.argtypes = [vp] * 6 + [ci, ci, cf, cf, cf, ci, vp, vp, vp]
         L.cddmsl_coco_match.argtypes = [vp] * 5 + [ci, c_long] + [vp] * 5 + [c_long, vp, ci, vp, ci, ci, ci] + [vp] * 5
+        L.cddmsl_voc_match.argtypes = [vp, c_long, vp, c_long, vp, vp, c_long, vp, vp, vp, c_long, c_long, vp, ci] + [vp] * 5
         L.cddmsl_openset_logits.argtypes = [vp] * 4 + [ci] * 4 + [cf, cf, vp]
         L.cddmsl_openset_select.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, cf, cf, cf] + [vp] * 6 + [ci, vp, vp, vp]
         L.cddmsl_roi_align_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
@@ -1297,6 +1298,65 @@ def coco_match(dt_boxes, dt_scores, dt_cls, dt_off, img_idx, gt, num_classes, ma
                                  gt.rngs.shape[0], int(num_classes), int(max_dets), ptr(rank), ptr(matched), ptr(ignored), ptr(over),
                                  stream_ptr()), "cddmsl_coco_match")
     return rank, matched, ignored, over
+
+
+VOC_MATCH_MAX_THRS = 16              # cddmsl_voc_match: IoU thresholds per launch (one bit each in the u16 masks)
+
+
+class VocGroundTruth:
+    """A VOC test set's ground truth on the device, as cddmsl_voc_match reads it: ``boxes`` f64 [G, 4] (the 1-based integers of the
+    XML), ``difficult`` u8 [G], ``off`` int64 [R + 1] over the R = classes * images rows (row = class * n_images + image index), and
+    the thresholds ``thrs`` f64 [T] as the host compares them.  Built once per evaluator (``from_host``)."""
+
+    def __init__(self, boxes, difficult, off, thrs):
+        require_cuda(boxes, difficult, off, thrs)
+        G = difficult.numel()
+        assert boxes.dtype == thrs.dtype == torch.float64 and difficult.dtype == torch.uint8 and off.dtype == torch.int64
+        assert tuple(boxes.shape) == (G, 4) and off.dim() == 1 and off.numel() >= 1 and thrs.dim() == 1
+        assert 1 <= thrs.numel() <= VOC_MATCH_MAX_THRS, f"voc_match: {thrs.numel()} thresholds outside [1, {VOC_MATCH_MAX_THRS}]"
+        assert all(t.is_contiguous() for t in (boxes, difficult, off, thrs))
+        self.boxes, self.difficult, self.off, self.thrs = boxes, difficult, off, thrs
+        self.n_rows, self.n_boxes = off.numel() - 1, G
+
+    @classmethod
+    def from_host(cls, rows, thrs, device):
+        """``rows``: [(bbox [g, 4], difficult [g])] numpy, one per (class, image) in row order"""
+        import numpy as np
+        from ._lib import to_device_async
+        boxes = np.concatenate([np.asarray(b, dtype=np.float64).reshape(-1, 4) for b, _ in rows] or [np.zeros((0, 4))])
+        diff = np.concatenate([np.asarray(d).astype(np.uint8).reshape(-1) for _, d in rows] or [np.zeros(0, dtype=np.uint8)])
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(d) for _, d in rows])
+        up = lambda a: to_device_async(torch.from_numpy(np.ascontiguousarray(a)), device)
+        return cls(up(boxes), up(diff), up(off), up(np.asarray(thrs, dtype=np.float64)))
+
+
+@_timed("voc_match")
+def voc_match(boxes, perm, seg_off, seg_gt, gt):
+    """``evaluation.class_ap``'s greedy walk for every (class, image) segment at every threshold of ``gt.thrs`` in one launch
+    (cddmsl_voc_match), bit-identical to it.  ``boxes`` f32 [D, 4] XYXY as the model left them (the kernel rounds them the way the
+    reference's result lines do), ``perm`` int64 [P]: detection indices segment by segment, inside a segment in ``class_ap``'s
+    visiting order, each detection at most once; ``seg_off`` int64 [S + 1]; ``seg_gt`` int64 [S]: the segments' rows in ``gt`` (a
+    ``VocGroundTruth``), each row at most once.  All on the device; nothing is read back and nothing synchronises.
+    -> (tp, fp: int16 [D] holding the u16 masks, bit t = the flag at ``gt.thrs[t]``; bad int32 [S]: 1 = the segment's offsets or
+    entries were out of range and skipped)."""
+    require_cuda(boxes, perm, seg_off, seg_gt)
+    D, S = boxes.shape[0], seg_gt.numel()
+    if boxes.dtype != torch.float32:
+        raise TypeError(f"voc_match: boxes are {boxes.dtype}, the kernel reads f32")
+    assert perm.dtype == seg_off.dtype == seg_gt.dtype == torch.int64 and tuple(boxes.shape) == (D, 4) and seg_off.numel() == S + 1
+    assert perm.dim() == seg_off.dim() == seg_gt.dim() == 1
+    assert boxes.is_contiguous() and perm.is_contiguous() and seg_off.is_contiguous() and seg_gt.is_contiguous()
+    if S >= 2 ** 31:
+        raise ValueError(f"voc_match: {S} segments in one launch (the grid holds 2^31 - 1)")
+    dev = boxes.device
+    flags = torch.empty((2, D), device=dev, dtype=torch.int16)
+    bad = torch.empty(S, device=dev, dtype=torch.int32)
+    ws = workspace("voc_match", max(2 * gt.n_boxes, 1), dev)          # the claimed bits: one u16 per ground-truth box
+    check(_L().cddmsl_voc_match(ptr(boxes), D, ptr(perm), perm.numel(), ptr(seg_off), ptr(seg_gt), S, ptr(gt.boxes), ptr(gt.difficult), ptr(gt.off),
+                                gt.n_rows, gt.n_boxes, ptr(gt.thrs), gt.thrs.numel(), ptr(flags[0]), ptr(flags[1]), ptr(bad), ptr(ws),
+                                stream_ptr()), "cddmsl_voc_match")
+    return flags[0], flags[1], bad
 
 
 OPENSET_MAX_CLASSES = 16384          # cddmsl_openset_logits / _select: classes of the test vocabulary

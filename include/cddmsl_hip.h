@@ -228,6 +228,29 @@ int cddmsl_coco_match(const float* dt_boxes, const float* dt_scores, const long*
                       int B, long D_total, const double* gt_xywh, const double* gt_area, const unsigned char* gt_crowd,
                       const long* gt_cls, const long* gt_off, long n_images, const double* thrs, int T, const double* area_rngs,
                       int A, int K, int max_dets, int* rank, long* matched, long* ignored, int* over, void* stream);
+/* ---- Pascal VOC matching (csrc/voc_match.hip): the devkit's greedy walk (pascal_voc_evaluation.py voc_eval, restated by
+ * cddmsl_amd/evaluation.py class_ap) for every (class, image) of a test set at T IoU thresholds in ONE launch, bit-identical to
+ * class_ap called per (class, threshold) on detections that went through the reference's result-file text lines.
+ *   detections   boxes [D][4] f32 XYXY as the model left them (16-byte aligned).  The kernel applies the text round trip itself:
+ *                xmin = rint(double(x0 + 1.0f) * 10.0) / 10.0 (the + 1 in f32), xmax = rint(double(x1) * 10.0) / 10.0, y likewise.
+ *   segments     perm [P] int64 lists detection indices segment by segment, a segment = one (class, image), inside it in the order
+ *                class_ap visits them (argsort(-rounded score) of the class, from the host); seg_off [S + 1] int64 offsets into
+ *                perm; seg_gt [S] int64 each segment's row of the ground-truth CSR.  perm lists a detection at most once and
+ *                seg_gt a row at most once.
+ *   ground truth gt_boxes [G][4] f64 (the 1-based integers of the XML), gt_difficult [G] u8, gt_off [R + 1] int64, R rows.
+ *   thrs [T] f64, T <= 16, as the host compares them (t / 100.0 computed there).
+ * -> tp / fp [D] u16: bit t = class_ap's tp / fp flag of the detection at thrs[t] (both 0: matched a difficult box, or listed by no
+ *    segment); bad [S] int32: 1 when the segment's offsets or one of its perm entries are out of range (such entries are skipped,
+ *    nothing is read or written out of bounds), else 0.
+ * Arithmetic: f64, one IEEE operation per host operation in the host's order (built with contraction off): iw = max(min(g.x2, b.x2)
+ * - max(g.x1, b.x1) + 1, 0), union = (b area) + (g area) - inter left to right, ov = inter / union; numpy's minimum / maximum NaN
+ * conventions; argmax = the first maximum, a NaN counts as the maximum; `best > thr` strict.  No cap on boxes or detections per
+ * segment.  temp: 2 * G bytes of scratch from the caller (the claimed bits, one u16 per box), 2-byte aligned; zeroed by the call.
+ * No atomics, every output has one writer: two runs give the same bytes.  No allocation, no synchronisation.
+ * CDDMSL_ERR_ARG, nothing written: a negative count, T outside 1..16, S >= 2^31, a missing or misaligned pointer. */
+int cddmsl_voc_match(const float* boxes, long D, const long* perm, long P, const long* seg_off, const long* seg_gt, long S,
+                     const double* gt_boxes, const unsigned char* gt_difficult, const long* gt_off, long R, long G, const double* thrs,
+                     int T, unsigned short* tp, unsigned short* fp, int* bad, void* temp, void* stream);
 /* ---- open-vocabulary inference (csrc/openset.hip): the test_cls_score branch of FastRCNNOutputLayers.forward, predict_probs,
  * the RPN-objectness product and fast_rcnn_inference_single_image up to its NMS (roi_heads/fast_rcnn.py:546-565, 793-810, 706-710,
  * 155-180).  Everything f32; no atomics: two runs give the same bits.

@@ -10,7 +10,9 @@ paired-batch generator; ``--voc-root <VOCdevkit/VOC2007> --dt-data <twin dir>`` 
 (cddmsl_amd/data.py), ``--eval-only --voc-root ...`` runs inference + Pascal VOC AP (cddmsl_amd/evaluation.py),
 ``--datasets-root DIR`` does the same for the Cityscapes / Foggy Cityscapes splits of the AdverseWeather config (paired training
 loader; COCO-style box AP on every known DATASETS.TEST name, ``bdd_100k_val`` from its COCO json included; cddmsl_amd/cityscapes.py,
-cddmsl_amd/coco_json.py), ``TEST.EVAL_PERIOD`` repeats that evaluation during training whenever a test set is given, and
+cddmsl_amd/coco_json.py) and for the VOC family of the VOC config (cddmsl_amd/voc_catalog.py: every VOC-family DATASETS.TRAIN name
+chained into one paired loader, Pascal VOC AP on ``voc_2007_test`` / ``Clipart1k_test`` / ``Watercolor_test`` / ``Comic_test`` by name;
+``--voc-root`` with ``--dt-data`` keeps precedence), ``TEST.EVAL_PERIOD`` repeats that evaluation during training whenever a test set is given, and
 ``MODEL.WEIGHTS`` / ``--resume`` / ``MODEL.PRE_TRAINED_RCLIP_PATH`` go through cddmsl_amd/checkpoint.py.
 """
 import argparse
@@ -40,8 +42,9 @@ def default_argument_parser():
                                                  "with --voc-root, train on the real paired loader instead of synthetic batches")
     p.add_argument("--voc-year", type=int, default=2007)
     p.add_argument("--datasets-root", default="", metavar="DIR",
-                   help="directory holding cityscapes/{leftImg8bit,leftImg8bit_foggy,gtFine} (Detectron2's DETECTRON2_DATASETS): "
-                        "a Cityscapes DATASETS.TRAIN[0] trains on the real paired loader, --eval-only scores every known DATASETS.TEST name")
+                   help="directory holding cityscapes/{leftImg8bit,leftImg8bit_foggy,gtFine} and / or VOC2007, VOC2012, dt_clipart, clipart, "
+                        "watercolor, comic (Detectron2's DETECTRON2_DATASETS): a Cityscapes DATASETS.TRAIN[0] or VOC-family DATASETS.TRAIN "
+                        "names train on the real paired loader, --eval-only scores every known DATASETS.TEST name")
     p.add_argument("opts", default=None, nargs=argparse.REMAINDER)
     return p
 
@@ -76,7 +79,7 @@ def build_eval_hook(tr, cfg, args, rank, world, max_iter):
 
 def main(args):
     import torch
-    from cddmsl_amd import cityscapes, engine, synthetic
+    from cddmsl_amd import cityscapes, engine, synthetic, voc_catalog
     rank, world = engine.init_distributed()
     from cddmsl_amd.config import auto_scale_workers
     cfg = auto_scale_workers(setup(args), world)                              # engine/defaults.py:374
@@ -108,6 +111,11 @@ def main(args):
         from cddmsl_amd import data
         from cddmsl_amd.evaluation import VOC_CLASS_NAMES
         dicts = data.load_voc_instances(args.voc_root, "trainval", VOC_CLASS_NAMES[: cfg.MODEL.ROI_HEADS.NUM_CLASSES], dt_data=args.dt_data)
+        tr.data_loader = data.build_detection_train_loader(cfg, dicts, per_rank, rank, world, cfg.MODEL.DEVICE)
+        tr._data_loader_iter = iter(tr.data_loader)
+    elif args.datasets_root and cfg.DATASETS.TRAIN and any(voc_catalog.is_voc_family(n) for n in cfg.DATASETS.TRAIN):
+        from cddmsl_amd import data      # the VOC family (configs/VOC-Experiments): every DATASETS.TRAIN name, chained in the order named
+        dicts = voc_catalog.load_train_sets(cfg.DATASETS.TRAIN, args.datasets_root, cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS)
         tr.data_loader = data.build_detection_train_loader(cfg, dicts, per_rank, rank, world, cfg.MODEL.DEVICE)
         tr._data_loader_iter = iter(tr.data_loader)
     elif args.datasets_root and cfg.DATASETS.TRAIN and cityscapes.is_cityscapes(cfg.DATASETS.TRAIN[0]):
