@@ -89,9 +89,9 @@ def test_conv_wgrad_fp8_is_the_f32_product_of_the_dequantised_operands(case):
     err = (out.double() - want).abs().max().item()
     ref = want.abs().max().item()
     # f32 accumulation across MFMAs, split sums in a different order -- and the MFMA's own 64-term dot product: single products are
-    # exact (subnormals included, probed one element at a time), but inside one instruction a product ~2^-12 below the row's largest is
-    # cut short (measured on the (1, 5, 3) case: 9 % of the sums, the ones holding a subnormal factor, are off by up to 1.7e-3 = 2^-9.2
-    # with products up to ~10) -- a property of v_mfma_scale_f32_32x32x64_f8f6f4, the same in the forward kernel
+    # exact, but inside one v_mfma_scale_f32_32x32x64_f8f6f4 what lies far below the largest product is cut short: measured per
+    # instruction by tools/mfma_f8_probe.hip and bounded per element by T_MFMA in tests/exact_fp8.py (tests/test_gpu_fp8_exact.py
+    # holds this kernel to that bound; the max-norm tolerance below stays as the coarse check it was)
     pmax = float(_deq(x8).abs().max() * _deq(d8).abs().max() * scale.max())
     assert err <= 2e-5 * ref + 2e-4 * pmax, (case, err, ref, pmax)
 
@@ -245,7 +245,8 @@ def test_fp8_quantisation_records_non_finite_inputs():
         bad[77] = float("nan")
         bad[99] = float("inf")
         y8 = hip.quantize_fp8(bad, s2.scale, s2.amax)
-        assert int(y8[77]) in (0x7e, 0xfe, 0x7f, 0xff) or True      # (whatever the saturated byte is, the RECORD is what matters)
+        # (the saturated bytes: NaN -> the code of -448, +Inf -> the code of +448; pinned for every emitter in tests/test_gpu_fp8_exact.py)
+        assert int(y8[77]) == 0xfe and int(y8[99]) == 0x7e
         assert bool(torch.isfinite(s1.amax.max())) and not bool(torch.isfinite(s2.amax.max()))
         before = float(s2.scale)
         sc.roll()

@@ -4,7 +4,10 @@ tools/shape_profile.py): a recording shim around ``hip.conv_fwd``, ``hip.conv_wg
 ``hip.gemm_tn_batched`` notes each call's entry point, full geometry, epilogue flags and the kernel the library picked
 (``cddmsl_last_kernel``).  Writes tests/golden/bench_gemm_launches.json, which tests/test_gpu_gemm_exact.py replays in plan-only mode
 (dispatch still picks the recorded kernel) and tests/test_exact_bound_host.py checks against the exact-product case table.
-A change of dispatch or of the step's shapes must re-record it.  usage: python tools/record_gemm_launches.py [--batches 16 32] [--out F]"""
+A change of dispatch or of the step's shapes must re-record it.  usage: python tools/record_gemm_launches.py [--batches 16 32] [--out F]
+With ``--dtype fp8`` the shim also notes ``hip.conv_fwd_fp8``, ``hip.conv_wgrad_fp8`` and ``hip.fp8_dot_nt``, keeps only those and the
+``hip.conv_fwd`` calls that write an e4m3 second output (``emit8``), and writes tests/golden/bench_fp8_launches.json (the case table of
+tests/fp8_exact_cases.py is checked against it by tests/test_fp8_bound_host.py); the bf16 file is not touched."""
 import argparse
 import json
 import os
@@ -15,6 +18,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "bench_gemm_launches.json")
+OUT_FP8 = os.path.join(ROOT, "tests", "golden", "bench_fp8_launches.json")
 
 
 def _dt(t):
@@ -24,7 +28,8 @@ def _dt(t):
 class Recorder:
     def __init__(self, hip):
         self.hip, self.on, self.calls, self.batch = hip, False, {}, 0
-        self.orig = {n: getattr(hip, n) for n in ("conv_fwd", "conv_wgrad", "gemm_nt_batched", "gemm_tn_batched")}
+        self.orig = {n: getattr(hip, n) for n in ("conv_fwd", "conv_wgrad", "gemm_nt_batched", "gemm_tn_batched",
+                                                     "conv_fwd_fp8", "conv_wgrad_fp8", "fp8_dot_nt")}
         for n in self.orig:
             setattr(hip, n, self._wrap(n))
 
@@ -32,11 +37,12 @@ class Recorder:
         for n, f in self.orig.items():
             setattr(self.hip, n, f)
 
-    def _note(self, entry, geom, flags, nbytes):
-        kid = int(self.hip._L().cddmsl_last_kernel())
+    def _note(self, entry, geom, flags, nbytes, kid=None):
+        # (kid given: an entry point with one kernel behind it; fp8_dot_nt does not go through the conv / GEMM dispatch: 0)
+        kid = int(self.hip._L().cddmsl_last_kernel()) if kid is None else kid
         key = json.dumps([self.batch, entry, geom, flags, kid], sort_keys=True)
         d = self.calls.setdefault(key, {"images": self.batch, "entry": entry, "geometry": geom, "epilogue": flags, "kernel_id": kid,
-                                        "kernel": self.hip._CONV_KERNEL.get(kid, "?"), "launches": 0, "max_operand_bytes": 0})
+                                        "kernel": self.hip._CONV_KERNEL.get(kid, "k_fp8_dot_nt" if entry == "fp8_dot_nt" else "?"), "launches": 0, "max_operand_bytes": 0})
         d["launches"] += 1
         d["max_operand_bytes"] = max(d["max_operand_bytes"], int(nbytes))
 
@@ -85,6 +91,35 @@ class Recorder:
                           max(a.numel() * a.element_size(), b.numel() * b.element_size()))
             return r
 
+        def conv_fwd_fp8(x8, w8, scale=None, bias=None, residual=None, relu=False, relu_mask=None, pad=0, out_f32=False, emit8=None):
+            y = f(x8, w8, scale, bias, residual, relu, relu_mask, pad, out_f32, emit8)
+            if rec.on:
+                N, H, W, Cin = x8.shape
+                Cout, KH, KW, _ = w8.shape
+                rec._note("conv_fwd_fp8", dict(N=N, H=H, W=W, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=1, pad=pad, pool=False, ldy=Cout,
+                                               dtype="e4m3"),
+                          dict(scale=scale is not None, bias=bias is not None, residual=None if residual is None else _dt(residual),
+                               relu=bool(relu), relu_mask=relu_mask is not None, out_f32=bool(out_f32), emit8=emit8 is not None),
+                          max(x8.numel(), y.numel() * y.element_size()), kid=10)
+            return y
+
+        def conv_wgrad_fp8(x8, dy8, w_shape, scale, pad=0, out=None):
+            r = f(x8, dy8, w_shape, scale, pad, out)
+            if rec.on:
+                N, H, W, Cin = x8.shape
+                Cout, KH, KW, _ = w_shape
+                rec._note("conv_wgrad_fp8", dict(N=N, H=H, W=W, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=1, pad=pad, pool=False, ldd=Cout,
+                                                 dtype="e4m3"),
+                          dict(scale=scale is not None, accumulate=out is not None), max(x8.numel(), dy8.numel()), kid=12)
+            return r
+
+        def fp8_dot_nt(a8, b8, alpha=None):
+            r = f(a8, b8, alpha)
+            if rec.on:
+                rec._note("fp8_dot_nt", dict(R=a8.shape[0], N=b8.shape[0], K=a8.shape[1], ldc=b8.shape[0], dtype="e4m3"),
+                          dict(alpha=alpha is not None), a8.numel(), kid=0)
+            return r
+
         return locals()[name]
 
 
@@ -92,8 +127,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 32])
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    fp8 = args.dtype == "fp8"
+    args.out = args.out or (OUT_FP8 if fp8 else OUT)
     import bench
     from cddmsl_amd import engine, hip, synthetic
     rec = Recorder(hip)
@@ -113,7 +150,8 @@ def main():
         del tr
         torch.cuda.empty_cache()
     rec.restore()
-    entries = sorted(rec.calls.values(), key=lambda d: (d["images"], d["entry"], d["kernel_id"], json.dumps(d["geometry"], sort_keys=True),
+    calls = [d for d in rec.calls.values() if not fp8 or d["geometry"]["dtype"] == "e4m3" or d["epilogue"].get("emit8")]
+    entries = sorted(calls, key=lambda d: (d["images"], d["entry"], d["kernel_id"], json.dumps(d["geometry"], sort_keys=True),
                                                         json.dumps(d["epilogue"], sort_keys=True)))
     doc = {"about": "distinct GEMM / convolution launches of one bench-shaped training step (tools/record_gemm_launches.py)",
            "dtype": args.dtype, "images": args.batches, "entries": entries}
