@@ -89,7 +89,9 @@ def test_preprocess(dtype, tol):
     assert (out[..., :3].float().cpu().permute(0, 3, 1, 2) - ref).abs().max() < tol * 3
     assert (out[..., 3:] == 0).all()
     ref2 = om.preprocess_image_train(cfg, [{"image": i} for i in imgs], "image")
-    # torchvision Resize is un-vendored: bicubic definition = ATen upsample_bicubic2d(align_corners=False) ("parity unpinned")
+    # the bicubic definition is ATen upsample_bicubic2d(align_corners=False): tests/test_preprocess_ref_host.py pins the kernel's formula
+    # to it in float64 and tests/test_gpu_preprocess_exact.py the kernel to the formula bit for bit; torchvision's Resize wrapper
+    # still cannot be imported here, so that the wrapper adds nothing to the ATen call is read from its source, not tested
     imgs2 = [torch.randint(0, 256, (3, 260, 300), generator=g, dtype=torch.uint8), torch.randint(0, 256, (3, 250, 330), generator=g, dtype=torch.uint8)]
     ref2 = om.preprocess_image_train(cfg, [{"image": i} for i in imgs2], "image")
     out2 = hip.preprocess224([i.cuda() for i in imgs2], 260, 330, cfg.pixel_mean, cfg.pixel_std, dtype)

@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 GOLD = os.path.join(ROOT, "tests", "golden", "ref_text_encoder.npz")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 DEV = "cuda:0"
-EPS_BF16 = 2.0 ** -8
 
 
 @pytest.fixture(scope="module")
@@ -24,23 +24,7 @@ def gold():
     return np.load(GOLD, allow_pickle=False)
 
 
-def attn_ref(qkv, n, t, heads):
-    """float64 causal attention of the bf16 operands: [n*t, W]"""
-    W = qkv.shape[1] // 3
-    q, k, v = qkv.double().view(n, t, 3, heads, 64).permute(2, 0, 3, 1, 4)
-    mask = torch.full((t, t), float("-inf"), dtype=torch.float64, device=qkv.device).triu(1)
-    p = torch.softmax(q @ k.transpose(-1, -2) * 0.125 + mask, dim=-1)
-    return (p @ v).permute(0, 2, 1, 3).reshape(n * t, W), v
-
-
-def check_attn_bound(got, ref, v, n, t, heads):
-    """P is rounded to bf16 before P V (relative 2^-9 per weight, at most 2^-9 max_j |v_j| per output) and the output is rounded to
-    bf16 (2^-9 |o|): |got - ref| <= 2^-8 (|ref| + max_{j <= i} |v_j|), twice that sum"""
-    vmax = v.abs().cummax(dim=2).values                                  # [n, heads, t, 64]: max over keys j <= i, per channel
-    vmax = vmax.amax(dim=-1, keepdim=True).expand(-1, -1, -1, 64).permute(0, 2, 1, 3).reshape(n * t, heads * 64)
-    err = (got.double() - ref).abs()
-    bound = EPS_BF16 * (ref.abs() + vmax) + 1e-6
-    assert bool((err <= bound).all()), (float((err / bound).max()), t, heads)
+from exact_text import attn_ref, check_attn_bound  # noqa: E402  (the float64 reference and the bound, shared with test_gpu_text_exact.py)
 
 
 @pytest.mark.parametrize("heads,n", [(8, 3), (10, 5)])
