@@ -118,6 +118,13 @@ def _L():
         L.cddmsl_lm_head_topk.argtypes = [vp] * 7 + [c_long] + [ci] * 4 + [vp]
         L.cddmsl_beam_step.argtypes = [vp] * 15 + [ci] * 5 + [vp]
         L.cddmsl_decode_attn_beam.argtypes = [vp] * 7 + [ci] * 9 + [cf, ci, vp]
+        L.cddmsl_attn_causal_bwd.argtypes = [vp] * 3 + [ci] * 6 + [cf, ci, vp]
+        L.cddmsl_gelu_new_bwd.argtypes = [vp] * 3 + [c_long, ci, vp]
+        L.cddmsl_token_ce_fwd.argtypes = [vp, ci, vp, c_long, ci, c_long, vp, vp, vp, vp]
+        L.cddmsl_token_ce_bwd.argtypes = [vp, ci, vp, vp, cf, vp, c_long, ci, c_long, ci, vp]
+        L.cddmsl_layernorm_bwd_params_workspace.argtypes = [c_long, ci]
+        L.cddmsl_layernorm_bwd_params.argtypes = [vp] * 7 + [c_long, c_long, ci, ci, ci, vp]
+        L.cddmsl_adamw_step.argtypes = [vp] * 5 + [ci] + [cf] * 5 + [c_long, vp]
         _sigs_done = True
     return L
 
@@ -1987,3 +1994,122 @@ def meanpool_bwd(dy, P, dtype):
     dx = torch.empty((K, P, C), device=dy.device, dtype=dtype)
     check(_L().cddmsl_meanpool_bwd(ptr(dy.contiguous().float()), ptr(dx), K, P, C, DT[dtype], stream_ptr()), "cddmsl_meanpool_bwd")
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ ClipCap mapper training
+def _rows_view(x, what):
+    """(ld, cols) of a 2-D bf16 / f32 tensor whose rows may be the leading columns of a wider buffer"""
+    assert x.dim() == 2 and (x.shape[1] == 1 or x.stride(1) == 1) and x.stride(0) >= x.shape[1], f"{what}: rows of unit-stride columns"
+    return x.stride(0), x.shape[1]
+
+
+@_timed("k_attn_causal_bwd")
+def attn_causal_bwd(qkv, do, t, heads, scale, out=None):
+    """Backward of ``attn_causal_fwd``: qkv [n*t, 3W] bf16 (row stride >= 3W), do [n*t, W] bf16 (row stride >= W) -> dqkv
+    (dq | dk | dv, qkv's row stride; ``out`` to write into a given buffer)."""
+    require_cuda(qkv, do, out)
+    ldqkv, W3 = _rows_view(qkv, "qkv")
+    ldo, W = _rows_view(do, "do")
+    assert qkv.dtype == do.dtype == torch.bfloat16 and W3 == 3 * W and W % heads == 0 and qkv.shape[0] == do.shape[0] and qkv.shape[0] % t == 0
+    if out is None:
+        out = torch.empty_strided(qkv.shape, qkv.stride(), device=qkv.device, dtype=qkv.dtype) if ldqkv != W3 else torch.empty_like(qkv)
+    assert out.dtype == qkv.dtype and out.shape == qkv.shape and out.stride() == qkv.stride(), "dqkv takes qkv's layout"
+    check(_L().cddmsl_attn_causal_bwd(ptr(qkv), ptr(do), ptr(out), qkv.shape[0] // t, t, heads, W // heads, ldqkv, ldo, float(scale), 0,
+                                      stream_ptr()), "cddmsl_attn_causal_bwd")
+    return out
+
+
+@_timed("gelu_new_bwd")
+def gelu_new_bwd(x_pre, dy):
+    """dx = dy * gelu_new'(x_pre): x_pre is the c_fc output from before the activation (bf16 or f32, contiguous)"""
+    require_cuda(x_pre, dy)
+    assert x_pre.is_contiguous() and dy.is_contiguous() and x_pre.dtype == dy.dtype and x_pre.shape == dy.shape
+    dx = torch.empty_like(x_pre)
+    check(_L().cddmsl_gelu_new_bwd(ptr(x_pre), ptr(dy), ptr(dx), x_pre.numel(), _dt(x_pre), stream_ptr()), "cddmsl_gelu_new_bwd")
+    return dx
+
+
+@_timed("k_token_ce_fwd")
+def token_ce_fwd(logits, target, V=None, ignore_index=0):
+    """F.cross_entropy(logits[:, :V], target, ignore_index=...) for f32 logits [R, ld] (ld % 8 == 0; columns >= V are padding).
+    -> (loss, lse [R], count): loss a 0-dim f32 tensor, the mean over the ``count`` rows whose target is not ``ignore_index``.
+    Raises ``ValueError`` when no row counts (one readback of the count: the division is the host's)."""
+    require_cuda(logits, target)
+    ld, cols = _rows_view(logits, "logits")
+    V = cols if V is None else V
+    R = logits.shape[0]
+    assert logits.dtype == torch.float32 and target.dtype == torch.int64 and target.is_contiguous() and target.numel() == R and 0 < V <= cols
+    lse = torch.empty(R, device=logits.device, dtype=torch.float32)
+    row = torch.empty(R, device=logits.device, dtype=torch.float32)
+    sc = torch.zeros(2, device=logits.device, dtype=torch.float32)
+    check(_L().cddmsl_token_ce_fwd(ptr(logits), ld, ptr(target), R, V, ignore_index, ptr(lse), ptr(row), ptr(sc), stream_ptr()),
+          "cddmsl_token_ce_fwd")
+    count = int(sc[1].item())
+    if count == 0:
+        raise ValueError("token_ce: every target equals ignore_index, the mean over no rows is undefined")
+    return sc[0] / count, lse, count
+
+
+@_timed("k_token_ce_bwd")
+def token_ce_bwd(logits, target, lse, gscale, V=None, ignore_index=0, out_dtype=torch.float32, inplace=False):
+    """d loss / d logits = (softmax - onehot) * gscale on the rows that count, zero on ignored rows and padding columns.
+    ``gscale`` = upstream gradient / count, a float.  ``inplace`` (f32 only) writes over ``logits``."""
+    require_cuda(logits, target, lse)
+    ld, cols = _rows_view(logits, "logits")
+    V = cols if V is None else V
+    R = logits.shape[0]
+    assert logits.dtype == lse.dtype == torch.float32 and target.dtype == torch.int64 and target.is_contiguous() and lse.is_contiguous()
+    assert target.numel() == R and lse.numel() == R and 0 < V <= cols
+    # the kernel walks whole rows of ld columns (the padding is read and discarded, written as zero): the last row's must exist
+    assert (logits.storage_offset() + R * ld) * 4 <= logits.untyped_storage().nbytes(), "logits: the last row is shorter than ld"
+    if inplace:
+        assert out_dtype == torch.float32, "only an f32 gradient can overwrite the f32 logits"
+        d = logits
+    else:
+        # (whole rows of ld columns: the kernel zeroes the padding columns too)
+        d = torch.empty((R, ld), device=logits.device, dtype=out_dtype)[:, :cols]
+    check(_L().cddmsl_token_ce_bwd(ptr(logits), ld, ptr(target), ptr(lse), float(gscale), ptr(d), R, V, ignore_index, DT[out_dtype],
+                                   stream_ptr()), "cddmsl_token_ce_bwd")
+    return d
+
+
+@_timed("layernorm_bwd_params")
+def layernorm_bwd_params(dy, x, mean, rstd, dgamma=None, dbeta=None):
+    """The LayerNorm affine gradients: dgamma = sum_r dy (x - mean) rstd, dbeta = sum_r dy, f32 [D].  Given ``dgamma`` / ``dbeta``
+    (both), the sums are ADDED to them in place."""
+    require_cuda(dy, x, mean, rstd, dgamma, dbeta)
+    R, D = x.shape
+    dy = dy.contiguous()
+    assert x.dtype == mean.dtype == rstd.dtype == torch.float32 and x.is_contiguous() and mean.is_contiguous() and rstd.is_contiguous()
+    assert dy.shape == x.shape and mean.numel() == R and rstd.numel() == R and (dgamma is None) == (dbeta is None)
+    acc = 0 if dgamma is None else 1
+    if dgamma is None:
+        dgamma, dbeta = torch.empty(D, device=x.device, dtype=torch.float32), torch.empty(D, device=x.device, dtype=torch.float32)
+    assert dgamma.dtype == dbeta.dtype == torch.float32 and dgamma.is_contiguous() and dbeta.is_contiguous() and dgamma.numel() == dbeta.numel() == D
+    L = _L()
+    need = L.cddmsl_layernorm_bwd_params_workspace(R, D)
+    if need < 0:
+        raise ValueError(f"layernorm_bwd_params: R={R}, D={D} is outside the contract")
+    ws = workspace("ln_params", need, x.device)
+    check(L.cddmsl_layernorm_bwd_params(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), R, D, acc,
+                                        _dt(dy), stream_ptr()), "cddmsl_layernorm_bwd_params")
+    return dgamma, dbeta
+
+
+@_timed("adamw_step")
+def adamw_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step):
+    """torch.optim.AdamW (amsgrad off) over a list of f32 tensors in one launch family; ``step`` >= 1 is the step being taken."""
+    n = len(params)
+    if n == 0:
+        return
+    require_cuda(*params, *grads, *exp_avg, *exp_avg_sq)
+    assert len(grads) == n and len(exp_avg) == n and len(exp_avg_sq) == n and step >= 1
+    for p, g, m, v in zip(params, grads, exp_avg, exp_avg_sq):
+        assert p.dtype == g.dtype == m.dtype == v.dtype == torch.float32
+        assert same_layout(p, g) and same_layout(p, m) and same_layout(p, v), "param/grad/moments must share a memory layout"
+    P = (c_void_p * n)(*[p.data_ptr() for p in params])
+    G = (c_void_p * n)(*[g.data_ptr() for g in grads])
+    M = (c_void_p * n)(*[m.data_ptr() for m in exp_avg])
+    Vv = (c_void_p * n)(*[v.data_ptr() for v in exp_avg_sq])
+    S = (c_long * n)(*[p.numel() for p in params])
+    check(_L().cddmsl_adamw_step(P, G, M, Vv, S, n, lr, beta1, beta2, eps, weight_decay, int(step), stream_ptr()), "cddmsl_adamw_step")

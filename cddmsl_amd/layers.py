@@ -23,6 +23,11 @@ def bump_weight_version():
     _STEP[0] += 1
 
 
+def weight_version():
+    """the optimizer-step counter: the optimizers write parameters through raw pointers, so a tensor's ``_version`` does not see a step"""
+    return _STEP[0]
+
+
 _LOAD_GEN = [0]  # bumped whenever a state dict is loaded into a module of this package: caches of DERIVED tensors (folded
 #                  FrozenBN affines, padded stem weights, block-parameter tuples) key on it; caches of prepared parameter
 #                  copies additionally key on the parameter's ``_version`` (load_state_dict copies in place: same data_ptr)
@@ -1236,23 +1241,39 @@ def contrastive_loss(a, b):
     return ContrastiveFn.apply(a, b)
 
 
+def _ln_param_grads(ctx, dy, x, mean, rstd):
+    """(dgamma, dbeta) of a LayerNorm node, each only where that affine requires grad (a frozen affine: (None, None), no launch)"""
+    if dy is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+        return None, None
+    dg, db = hip.layernorm_bwd_params(dy, x, mean, rstd)
+    return (dg if ctx.needs_input_grad[1] else None), (db if ctx.needs_input_grad[2] else None)
+
+
+def _affine(p):
+    """a LayerNorm affine as a node input: itself where it is being trained, detached (no gradient, as before) where frozen"""
+    return p if p.requires_grad else p.detach()
+
+
 class LayerNormFn(torch.autograd.Function):
-    """Frozen-affine LayerNorm of the mapper: f32 residual stream in, compute-dtype GEMM operand out (clipcap.py:97-100)."""
+    """LayerNorm of the mapper: f32 residual stream in, compute-dtype GEMM operand out (clipcap.py:97-100).  The affine gradients
+    are formed only where the affine requires grad (mapper training); with a frozen affine the node returns what it always did."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, out_dtype):
-        y, mean, rstd = hip.layernorm_fwd(x.contiguous(), gamma, beta, out_dtype)
+    def forward(ctx, x, gamma, beta, out_dtype, eps=1e-5):
+        y, mean, rstd = hip.layernorm_fwd(x.contiguous(), gamma, beta, out_dtype, eps)
         ctx.save_for_backward(x, gamma, mean, rstd)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, mean, rstd = ctx.saved_tensors
-        return hip.layernorm_bwd(dy, x.contiguous(), gamma, mean, rstd), None, None, None
+        x = x.contiguous()
+        dg, db = _ln_param_grads(ctx, dy, x, mean, rstd)
+        return hip.layernorm_bwd(dy, x, gamma, mean, rstd), dg, db, None, None
 
 
-def layer_norm(x2d, gamma, beta, out_dtype):
-    return LayerNormFn.apply(x2d, gamma.detach(), beta.detach(), out_dtype)
+def layer_norm(x2d, gamma, beta, out_dtype, eps=1e-5):
+    return LayerNormFn.apply(x2d, _affine(gamma), _affine(beta), out_dtype, eps)
 
 
 class LayerNormSkipFn(torch.autograd.Function):
@@ -1261,9 +1282,9 @@ class LayerNormSkipFn(torch.autograd.Function):
     into the skip gradient) instead of the LN backward plus autograd's separate accumulation add."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, out_dtype):
+    def forward(ctx, x, gamma, beta, out_dtype, eps=1e-5):
         x = x.contiguous()
-        y, mean, rstd = hip.layernorm_fwd(x, gamma, beta, out_dtype)
+        y, mean, rstd = hip.layernorm_fwd(x, gamma, beta, out_dtype, eps)
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.emit = out_dtype == torch.bfloat16
         return y, x.view_as(x)
@@ -1271,28 +1292,30 @@ class LayerNormSkipFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dskip):
         x, gamma, mean, rstd = ctx.saved_tensors
+        # the affine gradients, only where the affine is being trained (mapper training); (None, None) and no launch otherwise
+        dg, db = _ln_param_grads(ctx, dy, x, mean, rstd)
         # bf16 compute: the kernel also writes the bf16 copy of the gradient it returns, for the sublayer below (``bf16_of``)
         emit = ctx.emit and os.environ.get("CDDMSL_LN_EMIT_BF16", "1") != "0"
         if dskip is None:
             if emit and dy is not None:
                 dx, dxb = hip.layernorm_bwd(dy, x, gamma, mean, rstd, emit_bf16=True)
                 _register_bf16(dx, dxb)
-                return dx, None, None, None
-            return hip.layernorm_bwd(dy, x, gamma, mean, rstd), None, None, None
+                return dx, dg, db, None, None
+            return hip.layernorm_bwd(dy, x, gamma, mean, rstd), dg, db, None, None
         # In place on the incoming skip gradient: its only other consumer is the sublayer branch hanging off the same residual
         # add, and that branch has necessarily run already (its result is the ``dy`` in hand).
         acc = dskip.contiguous()
         if dy is None:
-            return acc, None, None, None
+            return acc, None, None, None, None
         if emit:
             dx, dxb = hip.layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=acc, emit_bf16=True)
             _register_bf16(dx, dxb)
-            return dx, None, None, None
-        return hip.layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=acc), None, None, None
+            return dx, dg, db, None, None
+        return hip.layernorm_bwd(dy, x, gamma, mean, rstd, accumulate_into=acc), dg, db, None, None
 
 
-def layer_norm_skip(x2d, gamma, beta, out_dtype):
-    return LayerNormSkipFn.apply(x2d, gamma.detach(), beta.detach(), out_dtype)
+def layer_norm_skip(x2d, gamma, beta, out_dtype, eps=1e-5):
+    return LayerNormSkipFn.apply(x2d, _affine(gamma), _affine(beta), out_dtype, eps)
 
 
 class FocalCEFn(torch.autograd.Function):
@@ -1531,3 +1554,106 @@ def token_position_embed(ids, wte, wpe, pos, out=None):
 def prefix_position_embed(prefix, wpe):
     """prefix [n, P, W] f32 -> [n*P, W] f32 = prefix + wpe[0..P-1]"""
     return hip.pos_embed(wpe, 0, prefix.shape[1], src=prefix.contiguous())
+
+
+# ------------------------------------------------------------------------------------------------
+# Training the ClipCap mapper against the frozen GPT-2 (modeling/gpt2.py ``caption_loss``, clipcap_train.py): the causal stack with
+# input gradients, the vocabulary-sized cross-entropy, and the hand-back of the mapper's fused q | kv weight gradient.
+# ------------------------------------------------------------------------------------------------
+class CausalAttnFn(torch.autograd.Function):
+    """``causal_attention`` as an autograd node: the backward recomputes the probabilities from q, k and hands back one
+    [n*t, 3W] gradient (dq | dk | dv), so the in-projection's input gradient is one GEMM."""
+
+    @staticmethod
+    def forward(ctx, qkv, t, heads, scale):
+        qkv = qkv.contiguous()
+        ctx.save_for_backward(qkv)
+        ctx.cfg = (t, heads, scale)
+        return hip.attn_causal_fwd(qkv, t, heads, scale)
+
+    @staticmethod
+    def backward(ctx, do):
+        (qkv,) = ctx.saved_tensors
+        t, heads, scale = ctx.cfg
+        return hip.attn_causal_bwd(qkv, do.contiguous(), t, heads, scale), None, None, None
+
+
+def causal_attention_grad(qkv, t, heads, scale):
+    """``causal_attention`` with an input gradient (bf16)"""
+    return CausalAttnFn.apply(qkv, t, heads, scale)
+
+
+class GeluNewFn(torch.autograd.Function):
+    """GPT-2's tanh GELU out of place: the c_fc output from before the activation is what the backward needs, so it is kept and
+    the activation runs in place on a copy."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return hip.gelu_new_(x.clone())
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return hip.gelu_new_bwd(x, dy.contiguous())
+
+
+def gelu_new(x):
+    return GeluNewFn.apply(x)
+
+
+class LmHeadCEFn(torch.autograd.Function):
+    """mean token cross-entropy of the tied LM head as ONE node: logits [R, Vp] f32 = y @ wte_p^T (wte_p = wte with zero rows up to
+    Vp, a multiple of 8: the GEMMs' row alignment), loss = F.cross_entropy(logits[:, :V], target, ignore_index).  The backward writes
+    d logits straight in the GEMM operand's dtype (in place over the logits on the f32 path) and runs the input-gradient GEMM; the
+    frozen table gets no gradient.  Raises ``ValueError`` when every target is ignored."""
+
+    @staticmethod
+    def forward(ctx, y, pw, target, V, ignore_index):
+        T = y.dtype
+        wf, _ = pw.get(T, need_dgrad=True)
+        M, K = y.shape
+        logits = hip.conv_fwd(y.contiguous().view(1, 1, M, K), wf, out_f32=True).view(M, -1)
+        loss, lse, count = hip.token_ce_fwd(logits, target, V, ignore_index)
+        ctx.pw, ctx.cfg = pw, (V, ignore_index, count, T)
+        ctx.save_for_backward(logits, target, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, lse = ctx.saved_tensors
+        V, ignore_index, count, T = ctx.cfg
+        M = logits.shape[0]
+        d = hip.token_ce_bwd(logits, target, lse, float(g) / count, V, ignore_index, out_dtype=T, inplace=(T == torch.float32))
+        _, wd = ctx.pw.get(T, need_dgrad=True)
+        return hip.conv_fwd(d.view(1, 1, M, -1), wd).view(M, -1), None, None, None, None
+
+
+def lm_head_cross_entropy(y, pw, target, V, ignore_index=0):
+    return LmHeadCEFn.apply(y, pw, target.contiguous(), V, ignore_index)
+
+
+class QkvGradHandBackFn(torch.autograd.Function):
+    """Identity on the input of the mapper's fused q | kv projection while it is trained.  The projection's weight-gradient GEMM
+    accumulates into the FUSED [3 dim, dim] weight's buffer; this node sits below the projection, so its backward runs right after
+    that GEMM and moves the two row blocks into ``to_queries.weight.grad`` / ``to_keys_values.weight.grad`` (and clears the buffer)."""
+
+    @staticmethod
+    def forward(ctx, x, fused, wq, wkv):
+        ctx.ws = (fused, wq, wkv)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        fused, wq, wkv = ctx.ws
+        if fused.grad is not None:
+            d = wq.shape[0]
+            _grad_buf(wq).add_(fused.grad[:d])
+            _grad_buf(wkv).add_(fused.grad[d:])
+            fused.grad.zero_()
+        return g, None, None, None
+
+
+def qkv_grad_hand_back(x, fused, wq, wkv):
+    return QkvGradHandBackFn.apply(x, fused, wq, wkv)

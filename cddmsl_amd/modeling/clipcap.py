@@ -1,4 +1,5 @@
-"""ClipCap vision-to-language mapper (frozen) -- detectron2/modeling/backbone/clipcap/clipcap.py:39-163,714-719.
+"""ClipCap vision-to-language mapper (frozen in the detector's training step; trainable for ClipCap's own training, ``trainable=True``) --
+detectron2/modeling/backbone/clipcap/clipcap.py:39-163,714-719.
 
 Only ``TransformerMapper`` is built here (``ClipCaptionModel.clip_project``, engine/train_loop.py:281-288): training never
 runs GPT-2.  Captioning (tools/gen_captions.py) builds it from the same ClipCap file's ``gpt.*`` entries: modeling/gpt2.py.
@@ -20,11 +21,15 @@ class _Lin(nn.Module):
         self.weight = nn.Parameter(torch.empty(o, i))
         self.bias = nn.Parameter(torch.empty(o)) if bias else None
         self._pw = None
+        self.trainable = False      # set by TransformerMapper(trainable=True): weight and bias gradients, per-step weight copies
+
+    def prepared(self):
+        if self._pw is None or self._pw.param is not self.weight or self._pw.frozen == self.trainable:
+            self._pw = layers.PreparedWeight(self.weight, None, frozen=not self.trainable)
+        return self._pw
 
     def forward(self, x2d, relu=False, out_f32=True, residual=None):
-        if self._pw is None or self._pw.param is not self.weight:
-            self._pw = layers.PreparedWeight(self.weight, None, frozen=True)
-        return layers.linear(x2d, self._pw, self.bias, relu=relu, out_f32=out_f32, train_w=False, residual=residual)
+        return layers.linear(x2d, self.prepared(), self.bias, relu=relu, out_f32=out_f32, train_w=self.trainable, residual=residual)
 
 
 class MlpTransformer(nn.Module):
@@ -33,11 +38,11 @@ class MlpTransformer(nn.Module):
         self.fc1, self.fc2 = _Lin(in_dim, h_dim), _Lin(h_dim, in_dim)
 
     def forward(self, y, residual):
-        """y [M, in_dim] bf16, residual [M, in_dim] f32 -> residual + fc2(relu(fc1(y))) f32 (frozen weights)"""
-        for lin in (self.fc1, self.fc2):
-            if lin._pw is None or lin._pw.param is not lin.weight:
-                lin._pw = layers.PreparedWeight(lin.weight, None, frozen=True)
-        return layers.frozen_mlp(y, self.fc1._pw, self.fc1.bias, self.fc2._pw, self.fc2.bias, residual)
+        """y [M, in_dim] bf16, residual [M, in_dim] f32 -> residual + fc2(relu(fc1(y))) f32.  Frozen weights: one node
+        (``frozen_mlp``); trained: its twin out of two trainable linears (weight and bias gradients, same epilogues)."""
+        if self.fc1.trainable:
+            return self.fc2(self.fc1(y, relu=True, out_f32=False), residual=residual)
+        return layers.frozen_mlp(y, self.fc1.prepared(), self.fc1.bias, self.fc2.prepared(), self.fc2.bias, residual)
 
 
 class MultiHeadAttention(nn.Module):
@@ -48,16 +53,33 @@ class MultiHeadAttention(nn.Module):
         self.to_queries = _Lin(dim, dim, bias)
         self.to_keys_values = _Lin(dim, dim * 2, bias)
         self.project = _Lin(dim, dim)
-        self._qkv = None          # (key, fused frozen weight [3 dim, dim], its PreparedWeight)
+        self._qkv = None          # (key, fused weight [3 dim, dim], its PreparedWeight)
 
     def qkv_weight(self):
-        """to_queries and to_keys_values (bias-free, frozen) as ONE [3 dim, dim] GEMM operand, rebuilt when either changes"""
+        """to_queries and to_keys_values (bias-free) as ONE [3 dim, dim] GEMM operand, rebuilt when either changes.  While they are
+        trained the fused copy is a trainable weight of its own whose gradient ``qkv_project`` hands back to the two."""
         wq, wkv = self.to_queries.weight, self.to_keys_values.weight
-        key = (wq.data_ptr(), wq._version, wkv.data_ptr(), wkv._version)
+        train = self.to_queries.trainable
+        # (while trained the key also carries the optimizer-step counter: the step kernels write through raw pointers, unseen by _version)
+        key = (wq.data_ptr(), wq._version, wkv.data_ptr(), wkv._version, train, layers.weight_version() if train else 0)
         if self._qkv is None or self._qkv[0] != key:
-            w = torch.nn.Parameter(torch.cat([wq.detach(), wkv.detach()], dim=0), requires_grad=False)
-            self._qkv = (key, w, layers.PreparedWeight(w, None, frozen=True))
+            if train and self._qkv is not None and self._qkv[0][4] and self._qkv[1].shape[0] == wq.shape[0] + wkv.shape[0]:
+                w = self._qkv[1]                      # an optimizer step: same buffers, new values
+                with torch.no_grad():
+                    torch.cat([wq.detach(), wkv.detach()], dim=0, out=w)
+                self._qkv = (key, w, self._qkv[2])
+            else:
+                w = torch.nn.Parameter(torch.cat([wq.detach(), wkv.detach()], dim=0), requires_grad=train)
+                self._qkv = (key, w, layers.PreparedWeight(w, None, frozen=not train))
         return self._qkv[2]
+
+    def qkv_project(self, y):
+        """y [M, dim] -> q | k | v [M, 3 dim] in y's dtype: one projection GEMM on the fused weight"""
+        pw = self.qkv_weight()
+        if not self.to_queries.trainable:
+            return layers.linear(y, pw, None, out_f32=False, train_w=False)
+        y = layers.qkv_grad_hand_back(y, pw.param, self.to_queries.weight, self.to_keys_values.weight)
+        return layers.linear(y, pw, None, out_f32=False, train_w=True)
 
 
 class TransformerLayer(nn.Module):
@@ -77,14 +99,20 @@ class Transformer(nn.Module):
 
 class TransformerMapper(nn.Module):
     def __init__(self, dim_clip=1024, dim_embedding=768, prefix_length=40, clip_length=40, num_layers=8,
-                 compute_dtype=torch.bfloat16):
+                 compute_dtype=torch.bfloat16, trainable=False):
+        """``trainable=False`` (what the detector's training step uses): every parameter frozen, input gradients only.
+        ``trainable=True`` (ClipCap's own training, clipcap_train.py): the parameters require grad, the linears form weight and bias
+        gradients, ``prefix_const`` and the LayerNorm affines receive theirs."""
         super().__init__()
-        self.clip_length, self.dim, self.compute_dtype = clip_length, dim_embedding, compute_dtype
+        self.clip_length, self.dim, self.compute_dtype, self.trainable = clip_length, dim_embedding, compute_dtype, bool(trainable)
         self.transformer = Transformer(dim_embedding, 8, num_layers)
         self.linear = _Lin(dim_clip, clip_length * dim_embedding)
         self.prefix_const = nn.Parameter(torch.randn(prefix_length, dim_embedding))
         for p in self.parameters():
-            p.requires_grad = False
+            p.requires_grad = self.trainable
+        for m in self.modules():
+            if isinstance(m, _Lin):
+                m.trainable = self.trainable
 
     def forward(self, x, last_only=False):
         """x [N, dim_clip] f32 -> [N, prefix_length, dim] f32   (clipcap.py:151-155).
@@ -108,7 +136,7 @@ class TransformerMapper(nn.Module):
                 # LayerNorm hands back its input for the residual add so that the backward accumulates in one kernel
                 y, hs = layers.layer_norm_skip(h.view(n * t, d), lyr.norm1.weight, lyr.norm1.bias, T)
                 if a.to_queries.bias is None and a.to_keys_values.bias is None:
-                    qkv = layers.linear(y, a.qkv_weight(), None, out_f32=False, train_w=False)     # one projection GEMM
+                    qkv = a.qkv_project(y)                                                         # one projection GEMM
                     o = layers.small_attention_qkv(qkv, t, H, a.scale)
                 else:
                     o = layers.small_attention(a.to_queries(y, out_f32=False), a.to_keys_values(y, out_f32=False), t, H, a.scale)

@@ -243,6 +243,74 @@ class GPT2Decoder(FrozenCausalStack):
         if logits is not None:
             logits.append(lg)
 
+    # ---------------------------------------------------------------- training the mapper against the frozen decoder
+    _train = None
+
+    def _train_weights(self):
+        """the frozen linears as ``layers.PreparedWeight`` (forward and input-gradient copies in the compute dtype) plus the LM head's
+        table, ``wte`` with zero rows up to a multiple of 8 (the GEMMs' row alignment); rebuilt when a parameter or the dtype changes"""
+        key = (self.compute_dtype, tuple((p.data_ptr(), p._version) for p in self.parameters()))
+        if self._train is None or self._train[0] != key:
+            pw = lambda m: layers.PreparedWeight(m.weight, None, frozen=True)
+            V, E = self.wte.weight.shape
+            head = torch.zeros((V + 7) // 8 * 8, E, device=self.wte.weight.device, dtype=torch.float32)
+            head[:V] = self.wte.weight.detach()
+            self._train = (key, [(pw(b.attn.c_attn), pw(b.attn.c_proj), pw(b.mlp.c_fc), pw(b.mlp.c_proj)) for b in self.h],
+                           layers.PreparedWeight(head, None, frozen=True))
+        return self._train[1], self._train[2]
+
+    def caption_loss(self, prefix_embeds, tokens):
+        """ClipCap's training loss (clipcap.py ``ClipCaptionModel.forward`` + ``train``): prefix_embeds [n, P, n_embd] f32 (the
+        mapper's output, the only input that gets a gradient) and tokens [n, L] int64 (0 where padded) -> the mean cross-entropy of
+        predicting tokens[:, j] from row P - 1 + j, over the tokens that are not 0, as a 0-dim f32 tensor.
+
+        The input is ``cat(prefix, wte[tokens]) + wpe[0 .. P+L)`` through the frozen blocks and ``ln_f``; the LM head runs for rows
+        P-1 .. P+L-2 only: the reference's ``logits[:, prefix_length - 1:-1]`` against ``tokens.flatten()`` with ``ignore_index=0``.
+        Token id 0 is both the pad and a real token ("!"); it stays ignored wherever it stands, as in the reference.
+
+        The reference also passes an ``attention_mask`` that hides the pads.  Pads sit at the tail of a caption, and under the
+        causal mask a row sees only the rows before it, so no row that is scored (each predicts a real token, hence stands before
+        every pad) ever sees one: the mask changes nothing at the scored rows and is not formed here.
+
+        P + L <= 128 (the fused attention kernels' limit).  bf16 path: attention forward and backward on the fused causal kernels;
+        exact-f32 path (``compute_dtype=torch.float32``): attention on torch f32 ops, everything else on the same kernels.
+        Raises ``ValueError`` when every token is 0."""
+        require_cuda(self.wte.weight)
+        dev, T = self.wte.weight.device, self.compute_dtype
+        n, P, E = prefix_embeds.shape
+        L = tokens.shape[1]
+        t = P + L
+        assert E == self.n_embd and tokens.shape[0] == n and tokens.dtype == torch.int64 and P >= 1 and L >= 1
+        if t > min(self.n_positions, 128):
+            raise ValueError(f"prefix {P} + {L} tokens exceeds {min(self.n_positions, 128)} positions")
+        if int(tokens.min()) < 0 or int(tokens.max()) >= self.vocab_size:
+            raise ValueError("token ids outside [0, vocab_size)")
+        Pm = self._prepared()
+        blocks, head = self._train_weights()
+        H, scale = self.heads, HEAD_DIM ** -0.5
+        tokens = tokens.to(dev)
+        x = torch.cat((prefix_embeds.to(dev, torch.float32), self.wte.weight.detach()[tokens]), dim=1) + Pm.wpe[:t]
+        x = x.view(n * t, E)
+        mask = None
+        for B, (w_qkv, w_out, w_fc, w_proj) in zip(Pm.layers, blocks):
+            y, xs = layers.layer_norm_skip(x, B.ln1_w, B.ln1_b, T, self.eps)
+            qkv = layers.linear(y, w_qkv, B.b_qkv, train_w=False)
+            if T == torch.bfloat16:
+                o = layers.causal_attention_grad(qkv, t, H, scale)
+            else:
+                if mask is None:
+                    mask = torch.full((t, t), float("-inf"), device=dev).triu_(1)
+                q, k, v = qkv.view(n, t, 3, H, HEAD_DIM).permute(2, 0, 3, 1, 4)
+                att = torch.softmax((q @ k.transpose(-1, -2)) * scale + mask, dim=-1)
+                o = (att @ v).permute(0, 2, 1, 3).reshape(n * t, E).contiguous()
+            x = layers.linear(o, w_out, B.b_out, out_f32=True, train_w=False, residual=xs)
+            y, xs = layers.layer_norm_skip(x, B.ln2_w, B.ln2_b, T, self.eps)
+            h = layers.gelu_new(layers.linear(y, w_fc, B.b_fc, train_w=False))
+            x = layers.linear(h, w_proj, B.b_proj, out_f32=True, train_w=False, residual=xs)
+        rows = x.view(n, t, E)[:, P - 1:t - 1].reshape(n * L, E)
+        y = layers.layer_norm(rows, Pm.ln_w, Pm.ln_b, T, self.eps)
+        return layers.lm_head_cross_entropy(y, head, tokens.reshape(n * L), self.vocab_size, 0)
+
 
     # ---------------------------------------------------------------- beam search
     @torch.no_grad()

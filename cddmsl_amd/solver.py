@@ -181,6 +181,74 @@ class ClippedSGD:
         return lr
 
 
+def linear_warmup_schedule(step, warmup, total):
+    """transformers' ``get_linear_schedule_with_warmup`` (ClipCap's train.py): the factor on the base lr at scheduler step ``step``:
+    a linear ramp 0 -> 1 over ``warmup`` steps, then linear 1 -> 0 at ``total``, never below 0."""
+    if step < warmup:
+        return float(step) / float(max(1, warmup))
+    return max(0.0, float(total - step) / float(max(1, total - warmup)))
+
+
+class AdamW:
+    """torch.optim.AdamW (amsgrad off) over a list of f32 parameters as ONE multi-tensor HIP launch family (``hip.adamw_step``).
+    The state carries torch's names: per parameter ``exp_avg``, ``exp_avg_sq`` and ``step``.  Parameters whose ``grad`` is None are
+    skipped, as torch skips them.  ``lr`` is an attribute: the training loop sets it from its schedule before each step."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        self.params = [p for p in params if p.requires_grad]
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.state = {}
+
+    def zero_grad(self):
+        for p in self.params:
+            if p.grad is not None:
+                p.grad.zero_()
+
+    def _state(self, p):
+        s = self.state.get(id(p))
+        if s is None:
+            s = self.state[id(p)] = {"step": 0, "exp_avg": torch.zeros_like(p, memory_format=torch.preserve_format),
+                                     "exp_avg_sq": torch.zeros_like(p, memory_format=torch.preserve_format)}
+        return s
+
+    def step(self):
+        layers.take_touched()
+        ps = [p for p in self.params if p.grad is not None]
+        by_step = {}
+        for p in ps:                                   # (one launch family per step count: they differ only after a late first gradient)
+            s = self._state(p)
+            s["step"] += 1
+            by_step.setdefault(s["step"], []).append(p)
+        with torch.no_grad():
+            for k, group in by_step.items():
+                hip.adamw_step([p.data for p in group], [p.grad for p in group], [self.state[id(p)]["exp_avg"] for p in group],
+                               [self.state[id(p)]["exp_avg_sq"] for p in group], self.lr, self.betas[0], self.betas[1], self.eps,
+                               self.weight_decay, k)
+        layers.bump_weight_version()   # prepared (cast / transposed) weights are stale now
+        return self.lr
+
+    def state_dict(self):
+        """torch.optim's layout: ``state`` keyed by the parameter's index, ``param_groups`` with the hyper-parameters"""
+        state = {}
+        for i, p in enumerate(self.params):
+            s = self.state.get(id(p))
+            if s is not None:
+                state[i] = {"step": int(s["step"]), "exp_avg": s["exp_avg"].detach().cpu(), "exp_avg_sq": s["exp_avg_sq"].detach().cpu()}
+        return {"state": state, "param_groups": [{"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
+                                                  "params": list(range(len(self.params)))}]}
+
+    def load_state_dict(self, sd):
+        g = sd["param_groups"][0]
+        assert len(g["params"]) == len(self.params), "optimizer state for another parameter list"
+        self.lr, self.betas, self.eps, self.weight_decay = float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"])
+        self.state = {}
+        for i, s in sd["state"].items():
+            p = self.params[int(i)]
+            self.state[id(p)] = {"step": int(s["step"]),
+                                 "exp_avg": s["exp_avg"].to(p.device, torch.float32).clone(memory_format=torch.preserve_format),
+                                 "exp_avg_sq": s["exp_avg_sq"].to(p.device, torch.float32).clone(memory_format=torch.preserve_format)}
+
+
 def build_optimizer(cfg, model):
     s = cfg.SOLVER
     groups = get_default_optimizer_params(model, base_lr=s.BASE_LR, weight_decay=s.WEIGHT_DECAY, weight_decay_norm=s.WEIGHT_DECAY_NORM,

@@ -526,6 +526,39 @@ int cddmsl_sgd_step_groups(float** params, const float** grads, float** moms, co
                            int count, float* norm_ws, float momentum, int nesterov, int clip_mode, float clip_value, int first_step,
                            void* stream);
 
+/* ---- Training the ClipCap mapper against the frozen GPT-2 (the reference's clipcap.py: ClipCaptionModel.forward, train with
+ * --only_prefix).  No floating-point atomics: reductions have a fixed order, one call gives the same bits twice.
+ * attn_causal_bwd: backward of attn_causal_fwd, same layouts and contract (bf16, dh == 64, t <= 128, ld % 8 == 0, 16-byte
+ *              aligned): qkv [nseq*t][ldqkv] (q | k | v), dout [nseq*t][ldo] -> dqkv [nseq*t][ldqkv] (dq | dk | dv).  The
+ *              probabilities are recomputed from q, k.  All three blocks are written in full; columns >= 3*heads*dh are not touched.
+ * gelu_new_bwd: dx = dy * gelu_new'(x_pre), x_pre the value from before the activation; any numel, 16-byte aligned pointers.
+ * token_ce_fwd: logits [R][ld] f32, classes are columns < V <= ld (the rest is padding, never read as a class), ld % 8 == 0,
+ *              target [R] int64.  lse [R], row_loss [R] (0 on rows whose target is ignore_index; NaN where a target that is not
+ *              ignore_index lies outside [0, V)), sum_count[0] = sum of row_loss, sum_count[1] = number of rows that count.
+ *              The mean is sum / count, the caller's division (count may be 0).
+ * token_ce_bwd: dlogits [R][ld] (dtype_out 0: bf16, 1: f32) = (softmax - onehot) * gscale on rows that count and columns < V,
+ *              zero elsewhere.  With dtype_out 1 dlogits may be logits.
+ * layernorm_bwd_params: dgamma [D] = sum_r dy (x - mean) rstd, dbeta [D] = sum_r dy, what cddmsl_layernorm_bwd leaves out;
+ *              dy [R][D] in `dtype`, x f32; accumulate 1 adds to dgamma / dbeta.  ws holds the per-chunk partial sums,
+ *              ws_bytes >= cddmsl_layernorm_bwd_params_workspace(R, D) (-1 outside the contract).
+ * adamw_step:  torch.optim.AdamW (amsgrad off) over `count` f32 tensors, host pointer arrays as in sgd_step_groups; step >= 1 is
+ *              the step being taken (bias corrections 1 - beta^step).  Per element:
+ *                p *= 1 - lr wd;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g g;
+ *                p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *              A NaN gradient element makes that element of m, v and p NaN, as torch does; other tensors are unaffected. */
+int cddmsl_attn_causal_bwd(const void* qkv, const void* dout, void* dqkv, int nseq, int t, int heads, int dh, int ldqkv, int ldo,
+                           float scale, int dtype, void* stream);
+int cddmsl_gelu_new_bwd(const void* x_pre, const void* dy, void* dx, long numel, int dtype, void* stream);
+int cddmsl_token_ce_fwd(const float* logits, int ld, const long* target, long R, int V, long ignore_index, float* lse, float* row_loss,
+                        float* sum_count, void* stream);
+int cddmsl_token_ce_bwd(const float* logits, int ld, const long* target, const float* lse, float gscale, void* dlogits, long R, int V,
+                        long ignore_index, int dtype_out, void* stream);
+int cddmsl_layernorm_bwd_params_workspace(long R, int D);
+int cddmsl_layernorm_bwd_params(const void* dy, const float* x, const float* mean, const float* rstd, float* dgamma, float* dbeta,
+                                float* ws, long ws_bytes, long R, int D, int accumulate, int dtype, void* stream);
+int cddmsl_adamw_step(float** params, const float** grads, float** exp_avg, float** exp_avg_sq, const long* sizes, int count, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, long step, void* stream);
+
 /* ---- Cityscapes instance boxes (input side, not the training step) -------------------------------------------------------
  * replaces the per-id `inst_image == instance_id` + np.nonzero loop of data/datasets/cityscapes.py:501-540 (from_json=False).
  * maps [B][H][W] instance ids, dtype 0 = uint16, 1 = int32.  For every map b, one record per id in [24, 34000) that occurs in it,
