@@ -7,11 +7,13 @@ stream handle the kernels are enqueued on.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (must be imported first: it loads the HIP runtime the library binds to)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcddmsl_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_hip.h")
 
 _lib = None
 
@@ -20,8 +22,61 @@ class HipLibraryError(RuntimeError):
     pass
 
 
+_BY_VALUE = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}
+
+
+def _statements(header_text):
+    """The header's ``;``-terminated statements: comments, preprocessor lines and the ``extern "C"`` braces stripped."""
+    text = re.sub(r"/\*.*?\*/", " ", header_text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', " ", text, flags=re.M)
+    return [" ".join(s.split()) for s in text.split(";") if s.strip()]
+
+
+def header_signatures(header_text):
+    """``{name: [ctypes type per parameter]}`` for every function the header declares.  Deliberately small and strict: a
+    declaration is ``int cddmsl_<name>(<params>);``, a parameter is a pointer (any ``*``: ``c_void_p``, which takes ``ptr(t)``,
+    None, ``byref`` and ctypes arrays alike) or a by-value ``int`` / ``long`` / ``float``.  Anything else raises."""
+    sigs = {}
+    for st in _statements(header_text):
+        if "(" not in st:                           # no function: the members and the closing line of the struct typedef
+            continue
+        m = re.fullmatch(r"(.*?)\b(cddmsl_\w+) ?\((.*)\)", st)
+        if m is None:
+            raise HipLibraryError(f"include/cddmsl_hip.h: cannot parse the declaration `{st}`")
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if ret != "int":
+            raise HipLibraryError(f"include/cddmsl_hip.h: {name} returns `{ret}`; every entry point returns int")
+        argtypes = []
+        for p in ([] if params == "void" else params.split(",")):
+            if "*" in p:
+                argtypes.append(ctypes.c_void_p)
+                continue
+            words = [w for w in p.split() if w != "const"]
+            if len(words) != 2 or words[0] not in _BY_VALUE:
+                raise HipLibraryError(f"include/cddmsl_hip.h: {name}: parameter `{p.strip()}` is neither a pointer nor a "
+                                      "by-value int / long / float")
+            argtypes.append(_BY_VALUE[words[0]])
+        sigs[name] = argtypes
+    return sigs
+
+
+def header_struct(header_text, name):
+    """``[(member, ctypes type)]`` of ``typedef struct <name> { ... } <name>;`` in declaration order (int / long members only)."""
+    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), re.sub(r"/\*.*?\*/", " ", header_text, flags=re.S), flags=re.S)
+    if m is None:
+        raise HipLibraryError(f"include/cddmsl_hip.h: no struct {name}")
+    fields = []
+    for st in (s.split() for s in m.group(1).split(";") if s.strip()):
+        if st[0] not in ("int", "long"):
+            raise HipLibraryError(f"include/cddmsl_hip.h: struct {name}: unknown member type in `{' '.join(st)}`")
+        fields += [(w.strip(","), _BY_VALUE[st[0]]) for w in st[1:]]
+    return fields
+
+
 def lib():
-    """Return the loaded library, loading it on first use.  Raises if it is not built."""
+    """Return the loaded library, loading it on first use, every entry point typed from include/cddmsl_hip.h.  Raises if the
+    library is not built or lacks a function the header declares; exports the header does not declare are left untyped."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -29,7 +84,15 @@ def lib():
                 f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  cddmsl_amd has no fallback path."
             )
-        _lib = ctypes.CDLL(LIB_PATH)
+        L = ctypes.CDLL(LIB_PATH)
+        with open(HEADER_PATH) as f:
+            sigs = header_signatures(f.read())
+        for name, argtypes in sigs.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise HipLibraryError(f"{LIB_PATH} is stale: it does not export {name}, which include/cddmsl_hip.h declares; rebuild it")
+            fn.restype, fn.argtypes = ctypes.c_int, argtypes
+        _lib = L
     return _lib
 
 

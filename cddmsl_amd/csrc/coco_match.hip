@@ -19,7 +19,6 @@
 // detections.  An (image, class) beyond a cap sets over[b] = 1 and writes nothing: the caller matches that image on the host, it
 // is never truncated.  rank is pre-set to -1 and the masks to 0, so a detection no wave owns (class outside [0, K)) is dropped.
 #include "common.h"
-#include "cddmsl_hip.h"
 
 namespace {
 

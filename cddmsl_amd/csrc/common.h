@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cddmsl_hip.h"   // every translation unit includes this file: the compiler checks each entry point's definition against its declaration
 
 #define CDDMSL_OK 0
 #define CDDMSL_ERR_ARG 1

@@ -12,7 +12,6 @@
 // the mirrored column range and a group's bytes read the tile's columns backwards; with the row mirror output row y is written to
 // row newh - 1 - y, and since the aligned-group / byte-edge split is taken from the row's destination ADDRESS, only the row index
 // changes.  Plain vector stores only.
-#include "cddmsl_hip.h"
 #include "resample.h"
 
 namespace {

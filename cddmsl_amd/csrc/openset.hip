@@ -27,7 +27,6 @@
 //   k_os_write   entries in (row, class) order -- mask.nonzero()'s -- through a wave ballot and a prefix popcount; each entry
 //                carries its row, class, score and the clipped box of that class.  Entries at or beyond cap are not written.
 #include "gemm_common.h"
-#include "cddmsl_hip.h"
 
 namespace {
 

@@ -27,7 +27,6 @@
 // off, division is correctly rounded); linear and hard contain no transcendental and are defined bit for bit, gaussian up to
 // expf's documented 1 ulp.  Scores must be finite (a -inf or NaN score is never picked).
 #include "common.h"
-#include "cddmsl_hip.h"
 #include <climits>
 #include <cstring>
 #include <rocprim/rocprim.hpp>

@@ -20,7 +20,6 @@
 // There is NO cap on boxes or detections per segment.  No atomics: tp / fp of a detection, the claimed bits of a ground-truth row and
 // bad[s] each have one writer (lane 0 of the segment's wave, provided perm lists a detection once and seg_gt a row once).
 #include "common.h"
-#include "cddmsl_hip.h"
 
 namespace {
 

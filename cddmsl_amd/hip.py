@@ -14,119 +14,7 @@ from ._lib import check, lib, ptr, require_cuda, stream_ptr
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
-_sigs_done = False
-
-
-def _L():
-    global _sigs_done
-    L = lib()
-    if not _sigs_done:
-        vp, ci, cf = c_void_p, c_int, c_float
-        L.cddmsl_last_kernel.argtypes = []
-        L.cddmsl_plan_only.argtypes = [ci]
-        L.cddmsl_conv_fwd.argtypes = [vp] * 7 + [ci] * 16 + [vp]
-        L.cddmsl_bottleneck64_ok.argtypes = [ci] * 4
-        L.cddmsl_bottleneck64_fwd.argtypes = [vp] * 17 + [ci] * 4 + [vp]
-        L.cddmsl_conv_wgrad.argtypes = [vp] * 4 + [ci] * 12 + [vp]
-        L.cddmsl_set_workspace.argtypes = [vp, c_long]
-        L.cddmsl_weight_prep.argtypes = [vp] * 4 + [ci] * 5 + [vp]
-        L.cddmsl_weight_prep_multi.argtypes = [vp, ci, ci, vp]
-        L.cddmsl_preprocess.argtypes = [vp, vp] + [ci] * 6 + [vp, vp, ci, ci, vp]
-        L.cddmsl_maxpool3s2_fwd.argtypes = [vp, vp] + [ci] * 5 + [vp]
-        L.cddmsl_upsample_zero2.argtypes = [vp] * 4 + [ci] * 5 + [vp]
-        L.cddmsl_meanpool_fwd.argtypes = [vp, vp, c_long, ci, ci, ci, vp]
-        L.cddmsl_meanpool_bwd.argtypes = [vp, vp, c_long, ci, ci, ci, vp]
-        L.cddmsl_preprocess224.argtypes = [vp, vp] + [ci] * 11 + [vp, vp, ci, vp]
-        L.cddmsl_preprocess_batch.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, vp]
-        L.cddmsl_preprocess224_batch.argtypes = [vp, vp, vp, ci, vp] + [ci] * 8 + [vp, vp, ci, vp]
-        L.cddmsl_tta_view.argtypes = [vp] + [ci] * 4 + [vp, vp, vp, ci] * 2 + [vp, ci, ci, ci] * 2 + [ci, vp, vp, ci, ci, vp]
-        L.cddmsl_resize_batch_u8.argtypes = [vp, c_long, vp, c_long, vp, c_long, vp, ci, vp]
-        L.cddmsl_avgpool2_fwd.argtypes = [vp, vp] + [ci] * 5 + [vp]
-        L.cddmsl_avgpool2_bwd.argtypes = [vp] * 4 + [ci] * 5 + [vp]
-        L.cddmsl_avgpool2_bwd_q8.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 4
-        L.cddmsl_avgpool2_fwd_bits.argtypes = [vp] * 3 + [ci] * 5 + [vp]
-        L.cddmsl_avgpool2_bwd_bits.argtypes = [vp] * 3 + [ci] * 5 + [vp]
-        L.cddmsl_conv3x3_pool_fwd.argtypes = [vp] * 6 + [ci] * 7 + [vp]
-        L.cddmsl_attn_tokens_fwd.argtypes = [vp] * 3 + [ci] * 5 + [vp]
-        L.cddmsl_attn_tokens_bwd.argtypes = [vp] * 4 + [ci] * 5 + [vp]
-        L.cddmsl_attnpool_softmax_fwd.argtypes = [vp] * 3 + [c_long, ci, ci, ci, cf, ci, vp]
-        L.cddmsl_attnpool_softmax_bwd.argtypes = [vp] * 4 + [c_long, ci, ci, ci, cf, ci, vp]
-        L.cddmsl_gemm_nt_batched.argtypes = [vp] * 4 + [ci] * 7 + [c_long] * 3 + [ci, ci, vp]
-        L.cddmsl_gemm_tn_batched.argtypes = [vp] * 3 + [ci] * 7 + [c_long] * 3 + [ci, ci, vp]
-        L.cddmsl_relu_bwd.argtypes = [vp, vp, vp, c_long, ci, ci, vp]
-        L.cddmsl_colsum.argtypes = [vp, vp, c_long, ci, ci, ci, vp]
-        L.cddmsl_sgd_clip_step.argtypes = [vp] * 4 + [ci, vp] + [cf] * 4 + [ci, vp]
-        L.cddmsl_sgd_step_groups.argtypes = [vp] * 6 + [ci, vp, cf, ci, ci, cf, ci, vp]
-        L.cddmsl_roi_align_forward.argtypes = [vp] * 5 + [ci] * 7 + [cf, ci, ci, ci, vp]
-        L.cddmsl_roi_align_backward.argtypes = [vp] * 7 + [ci] * 7 + [cf, ci, ci, ci, vp]
-        L.cddmsl_nms_anyorder.argtypes = [vp] * 4 + [ci, cf, vp, vp, vp]
-        L.cddmsl_soft_nms.argtypes = [vp] * 6 + [ci, ci, cf, cf, cf, ci, vp, vp, vp]
-        L.cddmsl_coco_match.argtypes = [vp] * 5 + [ci, c_long] + [vp] * 5 + [c_long, vp, ci, vp, ci, ci, ci] + [vp] * 5
-        L.cddmsl_voc_match.argtypes = [vp, c_long, vp, c_long, vp, vp, c_long, vp, vp, vp, c_long, c_long, vp, ci] + [vp] * 5
-        L.cddmsl_openset_logits.argtypes = [vp] * 4 + [ci] * 4 + [cf, cf, vp]
-        L.cddmsl_openset_select.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, cf, cf, cf] + [vp] * 6 + [ci, vp, vp, vp]
-        L.cddmsl_roi_align_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
-        L.cddmsl_roi_align_backward_nchw_anyorder.argtypes = [vp] * 3 + [ci] * 7 + [cf, ci, ci, ci, vp, vp, vp]
-        L.cddmsl_quantize_fp8.argtypes = [vp] * 4 + [c_long, ci, vp]
-        L.cddmsl_conv_fwd_fp8.argtypes = [vp] * 7 + [ci] * 10 + [vp] * 4
-        L.cddmsl_conv_wgrad_fp8_ok.argtypes = [ci] * 6
-        L.cddmsl_conv_wgrad_fp8.argtypes = [vp] * 4 + [ci] * 9 + [vp]
-        L.cddmsl_conv_fwd_q8.argtypes = [vp] * 7 + [ci] * 10 + [vp] * 4
-        L.cddmsl_fp8_dot_nt.argtypes = [vp] * 4 + [ci] * 4 + [vp]
-        L.cddmsl_roi_align_forward_affine.argtypes = [vp] * 6 + [ci] * 8 + [cf, ci, ci, ci] + [vp] * 4
-        L.cddmsl_roi_align_backward_pooled.argtypes = [vp] * 7 + [ci] * 7 + [cf, ci, ci, ci, vp]
-        L.cddmsl_anchors.argtypes = [vp, vp, ci, ci, ci, cf, cf, vp]
-        L.cddmsl_sort_desc.argtypes = [vp] * 5 + [ci, ci, vp, vp, vp]
-        L.cddmsl_rpn_decode.argtypes = [vp] * 6 + [ci] * 5 + [cf] * 8 + [vp]
-        L.cddmsl_nms.argtypes = [vp] * 5 + [ci, ci, cf, ci, vp]
-        L.cddmsl_iou_match.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, cf, cf, ci, ci, ci, ci, vp]
-        L.cddmsl_iou_match_batched.argtypes = [vp] * 7 + [ci] * 5 + [cf, cf] + [ci] * 4 + [vp]
-        L.cddmsl_l2norm_fwd.argtypes = [vp, vp, vp, c_long, ci, cf, vp]
-        L.cddmsl_l2norm_bwd.argtypes = [vp, vp, vp, vp, c_long, ci, vp]
-        L.cddmsl_cosine_logits_fwd.argtypes = [vp] * 4 + [c_long, ci, ci, cf, cf, vp]
-        L.cddmsl_cosine_logits_bwd.argtypes = [vp] * 5 + [c_long, ci, ci, cf, ci, vp]
-        L.cddmsl_layernorm_fwd.argtypes = [vp] * 6 + [c_long, ci, cf, ci, vp]
-        L.cddmsl_layernorm_bwd.argtypes = [vp] * 6 + [c_long, ci, ci, ci, vp]
-        L.cddmsl_layernorm_bwd_emit.argtypes = [vp] * 7 + [c_long, ci, ci, ci, ctypes.POINTER(ci), vp]
-        L.cddmsl_focal_ce_fwd.argtypes = [vp] * 4 + [c_long, ci, cf, ci, cf, vp]
-        L.cddmsl_focal_ce_bwd.argtypes = [vp] * 5 + [c_long, ci, cf, ci, cf, vp]
-        L.cddmsl_attn_small_fwd.argtypes = [vp] * 4 + [ci] * 8 + [cf, ci, vp]
-        L.cddmsl_attn_small_bwd.argtypes = [vp] * 7 + [ci] * 8 + [cf, ci, vp]
-        L.cddmsl_attn_tokens_fwd_mask.argtypes = [vp] * 4 + [ci] * 5 + [vp]
-        L.cddmsl_attnpool_dx.argtypes = [vp] * 6 + [ci] * 6 + [vp]
-        L.cddmsl_rpn_losses.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, c_long, cf, cf, cf, cf, cf, vp, vp, vp, vp, vp]
-        L.cddmsl_box_l1.argtypes = [vp, ci, vp, ci, vp, vp, vp, cf, cf, cf, cf, cf, vp, vp, vp, vp]
-        L.cddmsl_rpn_losses_reg.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, c_long, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp, vp, vp, vp]
-        L.cddmsl_box_reg_loss.argtypes = [vp, ci, vp, ci, vp, vp, vp, cf, cf, cf, cf, cf, ci, cf, cf, vp, vp, vp, vp]
-        L.cddmsl_attn_last_fwd.argtypes = [vp] * 4 + [ci] * 8 + [cf, ci, vp]
-        L.cddmsl_attn_last_bwd.argtypes = [vp] * 6 + [ci] * 8 + [cf, ci, vp]
-        L.cddmsl_contrastive_fwd.argtypes = [vp] * 4 + [ci, ci, vp]
-        L.cddmsl_contrastive_bwd.argtypes = [vp] * 5 + [ci, ci, vp]
-        L.cddmsl_instance_boxes.argtypes = [vp] + [ci] * 4 + [vp, ci, vp, vp, vp, vp]
-        L.cddmsl_text_embed.argtypes = [vp] * 4 + [c_long, ci, ci, ci, ci, vp]
-        L.cddmsl_attn_causal_fwd.argtypes = [vp, vp] + [ci] * 6 + [cf, ci, vp]
-        L.cddmsl_quick_gelu.argtypes = [vp, c_long, ci, vp]
-        L.cddmsl_text_pool.argtypes = [vp] * 5 + [c_long, ci, ci, ci, cf, ci, vp]
-        L.cddmsl_skinny_gemm_workspace.argtypes = [ci] * 3
-        L.cddmsl_skinny_gemm.argtypes = [vp] * 6 + [c_long] + [ci] * 4 + [vp]
-        L.cddmsl_lm_head_workspace.argtypes = [ci, ci]
-        L.cddmsl_lm_head_argmax.argtypes = [vp, vp, vp, ci, vp, vp, c_long, ci, ci, ci, vp]
-        L.cddmsl_decode_attn.argtypes = [vp] * 4 + [ci] * 6 + [cf, ci, vp]
-        L.cddmsl_pos_embed.argtypes = [vp, ci] + [vp] * 4 + [c_long] + [ci] * 6 + [vp]
-        L.cddmsl_gelu_new.argtypes = [vp, c_long, ci, vp]
-        L.cddmsl_lm_head_topk_workspace.argtypes = [ci, ci]
-        L.cddmsl_lm_head_topk.argtypes = [vp] * 7 + [c_long] + [ci] * 4 + [vp]
-        L.cddmsl_beam_step.argtypes = [vp] * 15 + [ci] * 5 + [vp]
-        L.cddmsl_decode_attn_beam.argtypes = [vp] * 7 + [ci] * 9 + [cf, ci, vp]
-        L.cddmsl_attn_causal_bwd.argtypes = [vp] * 3 + [ci] * 6 + [cf, ci, vp]
-        L.cddmsl_gelu_new_bwd.argtypes = [vp] * 3 + [c_long, ci, vp]
-        L.cddmsl_token_ce_fwd.argtypes = [vp, ci, vp, c_long, ci, c_long, vp, vp, vp, vp]
-        L.cddmsl_token_ce_bwd.argtypes = [vp, ci, vp, vp, cf, vp, c_long, ci, c_long, ci, vp]
-        L.cddmsl_layernorm_bwd_params_workspace.argtypes = [c_long, ci]
-        L.cddmsl_layernorm_bwd_params.argtypes = [vp] * 7 + [c_long, c_long, ci, ci, ci, vp]
-        L.cddmsl_adamw_step.argtypes = [vp] * 5 + [ci] + [cf] * 5 + [c_long, vp]
-        _sigs_done = True
-    return L
+_L = lib      # the loaded library, every entry point typed from include/cddmsl_hip.h (_lib.py)
 
 
 class _Profiler:
@@ -1090,11 +978,8 @@ def roi_align_nchw(input, rois, output_size, spatial_scale, sampling_ratio, alig
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
     K = rois.shape[0]
     out = torch.zeros((K, C, ph, pw), device=input.device, dtype=input.dtype)
-    nbytes = ctypes.c_size_t(0)
-    args = (N, C, H, W, K, ph, pw, spatial_scale, sampling_ratio, int(aligned), _dt(input))
-    check(_L().cddmsl_roi_align_nchw_anyorder(ptr(input), ptr(rois), ptr(out), *args, None, ctypes.byref(nbytes), stream_ptr()), "cddmsl_roi_align_nchw_anyorder(size)")
-    ws = workspace("roi_nchw", max(nbytes.value, 1), input.device)
-    check(_L().cddmsl_roi_align_nchw_anyorder(ptr(input), ptr(rois), ptr(out), *args, ptr(ws), ctypes.byref(nbytes), stream_ptr()), "cddmsl_roi_align_nchw_anyorder")
+    _with_temp(_L().cddmsl_roi_align_nchw_anyorder, "cddmsl_roi_align_nchw_anyorder", "roi_nchw", input.device, ptr(input), ptr(rois), ptr(out),
+               N, C, H, W, K, ph, pw, spatial_scale, sampling_ratio, int(aligned), _dt(input))
     return out
 
 
@@ -1105,11 +990,8 @@ def roi_align_backward_nchw(grad, rois, input_shape, spatial_scale, sampling_rat
     N, C, H, W = input_shape
     K, _, ph, pw = grad.shape
     dx = torch.zeros(tuple(input_shape), device=grad.device, dtype=grad.dtype)
-    nbytes = ctypes.c_size_t(0)
-    args = (N, C, H, W, K, ph, pw, spatial_scale, sampling_ratio, int(aligned), _dt(grad))
-    check(_L().cddmsl_roi_align_backward_nchw_anyorder(ptr(grad), ptr(rois), ptr(dx), *args, None, ctypes.byref(nbytes), stream_ptr()), "cddmsl_roi_align_backward_nchw_anyorder(size)")
-    ws = workspace("roi_nchw_b", max(nbytes.value, 1), grad.device)
-    check(_L().cddmsl_roi_align_backward_nchw_anyorder(ptr(grad), ptr(rois), ptr(dx), *args, ptr(ws), ctypes.byref(nbytes), stream_ptr()), "cddmsl_roi_align_backward_nchw_anyorder")
+    _with_temp(_L().cddmsl_roi_align_backward_nchw_anyorder, "cddmsl_roi_align_backward_nchw_anyorder", "roi_nchw_b", grad.device, ptr(grad), ptr(rois),
+               ptr(dx), N, C, H, W, K, ph, pw, spatial_scale, sampling_ratio, int(aligned), _dt(grad))
     return dx
 
 
@@ -1134,6 +1016,15 @@ def workspace(key, nbytes, device):
         buf = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
         _WS[k] = buf
     return buf
+
+
+def _with_temp(fn, what, key, device, *head):
+    """Query-then-run for an entry point whose parameters end in (temp, temp_bytes, stream): ``fn(*head, NULL, &bytes, stream)``
+    reports the scratch it needs, the persistent ``workspace(key)`` supplies it, and the same call with the buffer does the work."""
+    nbytes = ctypes.c_size_t(0)
+    check(fn(*head, None, ctypes.byref(nbytes), stream_ptr()), what + "(size)")
+    ws = workspace(key, max(nbytes.value, 1), device)
+    check(fn(*head, ptr(ws), ctypes.byref(nbytes), stream_ptr()), what)
 
 
 INSTANCE_ID_LO, INSTANCE_ID_HI = 24, 34000      # ids the instance-box kernel reports: [24, 34000)
@@ -1187,12 +1078,7 @@ def sort_desc(keys):
     keys_out = torch.empty_like(keys)
     idx = torch.empty((N, total), device=dev, dtype=torch.int32)
     order = torch.empty((N, total), device=dev, dtype=torch.int32)
-    nbytes = ctypes.c_size_t(0)
-    check(_L().cddmsl_sort_desc(ptr(keys), ptr(keys_out), ptr(idx), ptr(order), ptr(offs), N, total, None, ctypes.byref(nbytes),
-                                stream_ptr()), "cddmsl_sort_desc(size)")
-    ws = workspace("sort", nbytes.value, dev)
-    check(_L().cddmsl_sort_desc(ptr(keys), ptr(keys_out), ptr(idx), ptr(order), ptr(offs), N, total, ptr(ws), ctypes.byref(nbytes),
-                                stream_ptr()), "cddmsl_sort_desc")
+    _with_temp(_L().cddmsl_sort_desc, "cddmsl_sort_desc", "sort", dev, ptr(keys), ptr(keys_out), ptr(idx), ptr(order), ptr(offs), N, total)
     return keys_out, order
 
 
@@ -1204,12 +1090,7 @@ def nms_anyorder(boxes, scores, iou_threshold):
     assert boxes.dtype == scores.dtype == torch.float32 and boxes.is_contiguous() and scores.is_contiguous() and scores.numel() == K
     keep = torch.empty(K, device=boxes.device, dtype=torch.int64)
     nkeep = torch.zeros(1, device=boxes.device, dtype=torch.int32)
-    nbytes = ctypes.c_size_t(0)
-    check(_L().cddmsl_nms_anyorder(ptr(boxes), ptr(scores), ptr(keep), ptr(nkeep), K, iou_threshold, None, ctypes.byref(nbytes), stream_ptr()),
-          "cddmsl_nms_anyorder(size)")
-    ws = workspace("nms_any", max(nbytes.value, 1), boxes.device)
-    check(_L().cddmsl_nms_anyorder(ptr(boxes), ptr(scores), ptr(keep), ptr(nkeep), K, iou_threshold, ptr(ws), ctypes.byref(nbytes), stream_ptr()),
-          "cddmsl_nms_anyorder")
+    _with_temp(_L().cddmsl_nms_anyorder, "cddmsl_nms_anyorder", "nms_any", boxes.device, ptr(boxes), ptr(scores), ptr(keep), ptr(nkeep), K, iou_threshold)
     return keep, nkeep
 
 
@@ -1235,13 +1116,8 @@ def soft_nms(boxes, scores, idxs, method, sigma, iou_threshold, prune_threshold,
     keep = torch.empty(K, device=boxes.device, dtype=torch.int64)
     keep_scores = torch.empty(K, device=boxes.device, dtype=torch.float32)
     nkeep = torch.zeros(1, device=boxes.device, dtype=torch.int32)
-    nbytes = ctypes.c_size_t(0)
-    args = (K, int(method), float(sigma), float(iou_threshold), float(prune_threshold), int(max_keep))
-    check(_L().cddmsl_soft_nms(ptr(boxes), ptr(scores), ptr(idxs), ptr(keep), ptr(keep_scores), ptr(nkeep), *args, None, ctypes.byref(nbytes),
-                               stream_ptr()), "cddmsl_soft_nms(size)")
-    ws = workspace("soft_nms", max(nbytes.value, 1), boxes.device)
-    check(_L().cddmsl_soft_nms(ptr(boxes), ptr(scores), ptr(idxs), ptr(keep), ptr(keep_scores), ptr(nkeep), *args, ptr(ws), ctypes.byref(nbytes),
-                               stream_ptr()), "cddmsl_soft_nms")
+    _with_temp(_L().cddmsl_soft_nms, "cddmsl_soft_nms", "soft_nms", boxes.device, ptr(boxes), ptr(scores), ptr(idxs), ptr(keep), ptr(keep_scores),
+               ptr(nkeep), K, int(method), float(sigma), float(iou_threshold), float(prune_threshold), int(max_keep))
     return keep, keep_scores, nkeep
 
 
@@ -1411,12 +1287,9 @@ def openset_select_raw(logits, stats, K, boxes, objectness, img_h, img_w, score_
     cand_box = torch.empty((cap, 4), device=dev, dtype=torch.float32)
     valid = torch.empty(R, device=dev, dtype=torch.uint8)
     count = torch.zeros(1, device=dev, dtype=torch.int32)
-    nbytes = ctypes.c_size_t(0)
-    head = (ptr(logits), ptr(stats), ld, ptr(boxes), boxes.shape[1], ptr(objectness), R, int(K), float(img_h), float(img_w), float(score_thresh),
-            ptr(cand_row), ptr(cand_cls), ptr(cand_score), ptr(cand_box), ptr(valid), ptr(count), cap)
-    check(_L().cddmsl_openset_select(*head, None, ctypes.byref(nbytes), stream_ptr()), "cddmsl_openset_select(size)")
-    ws = workspace("openset_select", max(nbytes.value, 1), dev)
-    check(_L().cddmsl_openset_select(*head, ptr(ws), ctypes.byref(nbytes), stream_ptr()), "cddmsl_openset_select")
+    _with_temp(_L().cddmsl_openset_select, "cddmsl_openset_select", "openset_select", dev, ptr(logits), ptr(stats), ld, ptr(boxes), boxes.shape[1],
+               ptr(objectness), R, int(K), float(img_h), float(img_w), float(score_thresh),
+               ptr(cand_row), ptr(cand_cls), ptr(cand_score), ptr(cand_box), ptr(valid), ptr(count), cap)
     return cand_row, cand_cls, cand_score, cand_box, valid, count
 
 

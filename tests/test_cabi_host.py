@@ -33,6 +33,76 @@ def test_exports_match_header(lib):
     assert lib.cddmsl_abi_version() == 3
 
 
+def _header_declarations():
+    """{name: parameter count} read off the header independently of the package's parser: commas of the parameter list + 1."""
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "cddmsl_hip.h")).read(), flags=re.S)
+    decls = {n: (0 if p.strip() == "void" else p.count(",") + 1) for n, p in re.findall(r"\bint\s+(cddmsl_\w+)\s*\(([^)]*)\)\s*;", hdr)}
+    assert len(decls) == len(re.findall(r"\bcddmsl_\w+\s*\(", hdr)) == 104
+    return decls
+
+
+def test_signatures_follow_header(lib):
+    """Every declared function is typed by lib(): int return, one argtype per declared parameter."""
+    for name, nparams in _header_declarations().items():
+        fn = getattr(lib, name)
+        assert fn.restype is ctypes.c_int, name
+        assert len(fn.argtypes) == nparams, (name, len(fn.argtypes), nparams)
+
+
+def test_signature_anchors(lib):
+    """A few signatures stated by hand, one per kind of parameter the header uses."""
+    vp, ci, cl, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+    assert lib.cddmsl_abi_version.argtypes == []
+    assert lib.cddmsl_conv_fwd.argtypes == [vp] * 7 + [ci] * 16 + [vp]
+    assert lib.cddmsl_attnpool_softmax_fwd.argtypes == [vp] * 3 + [cl, ci, ci, ci, cf, ci, vp]
+    assert lib.cddmsl_nms_anyorder.argtypes == [vp] * 4 + [ci, cf, vp, vp, vp]                           # size_t* temp_bytes
+    assert lib.cddmsl_preprocess_batch.argtypes == [vp, vp, vp, ci, vp, ci, ci, ci, vp, vp, ci, ci, vp]  # const unsigned char* const*
+    assert lib.cddmsl_weight_prep_multi.argtypes == [vp, ci, ci, vp]                                     # const long long*
+    assert lib.cddmsl_set_workspace.argtypes == [vp, cl]
+
+
+def test_header_parser_rejects_what_it_does_not_know():
+    from cddmsl_amd._lib import HipLibraryError, header_signatures
+    assert header_signatures("/* c */ int cddmsl_ok(const float* a, long n, void* stream);\nint cddmsl_none(void);") == {
+        "cddmsl_ok": [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p], "cddmsl_none": []}
+    with pytest.raises(HipLibraryError, match=r"cddmsl_bad_param.*double eps"):
+        header_signatures("int cddmsl_bad_param(const float* x, double eps, void* stream);")
+    with pytest.raises(HipLibraryError, match="cddmsl_bad_return"):
+        header_signatures("float cddmsl_bad_return(const float* x, void* stream);")
+    with pytest.raises(HipLibraryError, match=r"cddmsl_bad_unsigned.*unsigned int n"):
+        header_signatures("int cddmsl_bad_unsigned(unsigned int n);")
+
+
+def test_stale_library_is_refused(lib, monkeypatch, tmp_path):
+    """A function the header declares and the library lacks: lib() refuses the library, it does not leave the call untyped."""
+    from cddmsl_amd import _lib
+    hdr = tmp_path / "cddmsl_hip.h"
+    hdr.write_text(open(_lib.HEADER_PATH).read().replace("#ifdef __cplusplus\n}", "int cddmsl_not_built_yet(int n);\n#ifdef __cplusplus\n}"))
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(hdr))
+    monkeypatch.setattr(_lib, "_lib", None)
+    with pytest.raises(_lib.HipLibraryError, match=r"stale.*cddmsl_not_built_yet"):
+        _lib.lib()
+
+
+def test_resize_item_matches_header(tmp_path):
+    """hip.ResizeItem against struct cddmsl_resize_item: members as the header lists them, size and offsets as the C compiler
+    lays them out (2 long + 10 int = 56 bytes under LP64)."""
+    import subprocess
+    from cddmsl_amd import hip
+    from cddmsl_amd._lib import HEADER_PATH, header_struct
+    fields = header_struct(open(HEADER_PATH).read(), "cddmsl_resize_item")
+    names = ["src_off", "dst_off", "h", "w", "newh", "neww", "flip", "reverse_channels", "xtab", "xks", "ytab", "yks"]
+    assert [n for n, _ in fields] == names
+    assert hip.ResizeItem._fields_ == fields
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include "cddmsl_hip.h"\nint main(void) {\n  printf("%zu", sizeof(cddmsl_resize_item));\n'
+                   + "".join('  printf(" %%zu", offsetof(cddmsl_resize_item, %s));\n' % n for n in names) + "  return 0;\n}\n")
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "layout")])
+    size, *offsets = (int(v) for v in subprocess.check_output([str(tmp_path / "layout")], text=True).split())
+    assert ctypes.sizeof(hip.ResizeItem) == size == 56
+    assert [getattr(hip.ResizeItem, n).offset for n in names] == offsets
+
+
 def test_header_compiles_as_c():
     import subprocess
     subprocess.check_call(["gcc", "-std=c99", "-fsyntax-only", "-x", "c", os.path.join(ROOT, "include", "cddmsl_hip.h")])

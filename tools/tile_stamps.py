@@ -3,7 +3,7 @@ main-loop start, main-loop end and exit (after the wave's stores have left), fro
 the shipped library carries no stamps).  Reports, per shape, the medians over all waves of prologue / main loop / epilogue in
 microseconds and the launch's event time.
 
-  build:  for f in cddmsl_amd/csrc/*.hip: hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off [-DCDDMSL_TILE_STAMPS for gemm_conv, conv_fwd, conv_fwd256, conv_wgrad, bottleneck64] -c ...
+  build:  for f in cddmsl_amd/csrc/*.hip: hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -I include [-DCDDMSL_TILE_STAMPS for gemm_conv, conv_fwd, conv_fwd256, conv_wgrad, bottleneck64] -c ...
           hipcc -shared -fPIC *.o -o scratch/libstamps.so
   run:    python tools/tile_stamps.py scratch/libstamps.so
 """
