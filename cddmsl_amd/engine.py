@@ -301,6 +301,10 @@ class SimpleTrainer:
         nf = layers.FP8_SCALES.nonfinite
         if nf is not None and bool(nf.item()):       # fp8 configuration: e4m3 copies saturate, so an Inf / NaN activation can leave the loss finite
             raise FloatingPointError(f"An activation or gradient quantised to e4m3 held Inf / NaN at or before iteration={self.iter} (loss_dict = {metrics})")
+        if any(bool(f.item()) for f in layers.RPN_SPARSE_OVERFLOW.flags()):
+            raise RuntimeError("The RPN head's sparse backward pass found more rows with a gradient than the sampled anchors' count at or "
+                               f"before iteration={self.iter}: gradient rows were dropped, and every optimizer step since the previous metrics "
+                               "write may have used such a gradient -- the weights are not to be trusted.  Rerun with CDDMSL_RPN_SPARSE_BWD=0")
         self.storage.update(metrics)
         self.storage["total_loss"] = total
         self.storage["data_time"] = data_time

@@ -10,11 +10,12 @@ from ctypes import c_float, c_int, c_long, c_void_p
 
 import torch
 
-from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from ._lib import check, lib, lib_rpn_sparse, ptr, require_cuda, stream_ptr
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
 _L = lib      # the loaded library, every entry point typed from include/cddmsl_hip.h (_lib.py)
+_LR = lib_rpn_sparse      # the RPN head's sparse backward pass: libcddmsl_rpn_sparse.so, typed from include/cddmsl_rpn_sparse.h
 
 
 class _Profiler:
@@ -849,6 +850,70 @@ def colsum(x2d, period=1, out=None):
         out = torch.zeros((period, cols) if period > 1 else (cols,), device=x2d.device, dtype=torch.float32)
     check(_L().cddmsl_colsum(ptr(x2d), ptr(out), rows, cols, period, _dt(x2d), stream_ptr()), "cddmsl_colsum")
     return out
+
+
+# ---- sparse backward pass of the RPN head: the bookkeeping kernels around the GEMM entry points (csrc/rpn_sparse.hip, a library of its own)
+def _rows_profiled(name, launch, what, shape, nbytes, flops=0.0):
+    # (FLOP model: the copies and the scan do none; the gather-sum adds each partial row once)
+    e0 = PROFILE.begin(name) if PROFILE.on else None
+    check(launch(), what)
+    PROFILE.end(e0, name, float(flops), shape, nbytes=float(nbytes))
+
+
+def rpn_active_rows(dy2d, cap, overflow):
+    """The rows of ``dy2d`` [positions, cols] (f32 or the compute dtype) that hold a non-zero, compacted in ascending order:
+    ``rows`` [cap] int32 (-1 behind the last one) and ``slot`` [positions] int32 (index into rows, -1 = inactive).  More than
+    ``cap`` active rows set ``overflow`` [1] int32 and are dropped: whoever owns the flag reads it and raises."""
+    require_cuda(dy2d, overflow)
+    M, cols = dy2d.shape
+    assert dy2d.is_contiguous() and dy2d.dtype in DT and cap > 0 and overflow.dtype == torch.int32
+    marks = torch.empty(M, device=dy2d.device, dtype=torch.int32)
+    rows = torch.empty(cap, device=dy2d.device, dtype=torch.int32)
+    slot = torch.empty(M, device=dy2d.device, dtype=torch.int32)
+    f32 = int(dy2d.dtype == torch.float32)
+    _rows_profiled("rpn_mark_rows", lambda: _LR().cddmsl_rpn_mark_rows(ptr(dy2d), ptr(marks), M, cols, f32, 1 if f32 else 0, stream_ptr()),
+                   "cddmsl_rpn_mark_rows", (M, cols), dy2d.numel() * dy2d.element_size() + 4 * M)
+    _rows_profiled("rpn_compact_rows", lambda: _LR().cddmsl_rpn_compact_rows(ptr(marks), ptr(rows), ptr(slot), ptr(overflow), M, cap, stream_ptr()),
+                   "cddmsl_rpn_compact_rows", (M, cap), 12 * M + 4 * cap)                 # (the marks twice, the slots once)
+    return rows, slot
+
+
+def rpn_gather_rows(src2d, rows, dtype):
+    """``src2d[rows]`` in ``dtype`` (src f32 or ``dtype``), zero rows where ``rows`` < 0"""
+    require_cuda(src2d, rows)
+    cap, cols = rows.numel(), src2d.shape[1]
+    assert src2d.is_contiguous() and rows.dtype == torch.int32 and src2d.dtype in (dtype, torch.float32)
+    out = torch.empty((cap, cols), device=src2d.device, dtype=dtype)
+    _rows_profiled("rpn_gather_rows", lambda: _LR().cddmsl_rpn_gather_rows(ptr(src2d), ptr(rows), ptr(out), cap, cols,
+                                                                          int(src2d.dtype == torch.float32 and dtype != torch.float32), DT[dtype], stream_ptr()),
+                   "cddmsl_rpn_gather_rows", (cap, cols), cap * cols * (src2d.element_size() + out.element_size()) + 4 * cap)
+    return out
+
+
+def rpn_im2col_rows(x, rows, KH, KW, pad):
+    """The im2col rows of the positions ``rows`` of x NHWC: [cap, KH*KW*Cin], tap-major then channel (the order of a
+    [Cout][KH][KW][Cin] filter), zeros where a tap leaves its image"""
+    require_cuda(x, rows)
+    N, H, W, C = x.shape
+    cap = rows.numel()
+    assert x.is_contiguous() and rows.dtype == torch.int32
+    out = torch.empty((cap, KH * KW * C), device=x.device, dtype=x.dtype)
+    _rows_profiled("rpn_im2col_rows", lambda: _LR().cddmsl_rpn_im2col_rows(ptr(x), ptr(rows), ptr(out), cap, N, H, W, C, KH, KW, pad, _dt(x), stream_ptr()),
+                   "cddmsl_rpn_im2col_rows", (cap, KH * KW * C), 2 * out.numel() * out.element_size() + 4 * cap)
+    return out
+
+
+def rpn_dx_gather(P, slot, x_shape, KH, KW, pad, dtype):
+    """dx NHWC ``x_shape`` = per pixel the sum, in tap order, of the rows P[tap][slot[neighbour]] (P [KH*KW, cap, Cin] f32)"""
+    require_cuda(P, slot)
+    N, H, W, C = x_shape
+    taps, cap, C2 = P.shape
+    assert P.dtype == torch.float32 and P.is_contiguous() and taps == KH * KW and C2 == C and slot.numel() == N * H * W and slot.dtype == torch.int32
+    dx = torch.empty(tuple(x_shape), device=P.device, dtype=dtype)
+    # bytes: dx once, the slots, and every partial row once (a row of P[tap] is read by exactly one pixel)
+    _rows_profiled("rpn_dx_gather", lambda: _LR().cddmsl_rpn_dx_gather(ptr(P), ptr(slot), ptr(dx), cap, N, H, W, C, KH, KW, pad, DT[dtype], stream_ptr()),
+                   "cddmsl_rpn_dx_gather", (N * H * W, C, cap), dx.numel() * dx.element_size() + 4 * slot.numel() + P.numel() * 4, flops=P.numel())
+    return dx
 
 
 def same_layout(a, b):

@@ -423,6 +423,8 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        # (RpnHeadFn.backward's dense branch restates the bf16 / f32 launches below for the RPN head's 3x3 convolution: a change to
+        # them is mirrored there; tests/test_gpu_rpn_sparse_bwd.py::test_dense_route_is_conv_then_fused_heads holds the two bit-equal)
         x, y, x8 = ctx.saved_tensors
         stride, pad, relu, out_f32, train_w = ctx.cfg
         # (fp8 configuration, only where the forward took the e4m3 kernel: one e4m3 copy of the gradient feeds both gradient GEMMs)
@@ -516,22 +518,38 @@ def linear(x2d, pw, bias=None, relu=False, out_f32=False, train_w=True, residual
     return y.view(M, -1)
 
 
+def _heads_operands(heads, T, device):
+    """(forward weights [Npad,1,1,K], input-gradient weights, f32 bias [Npad], Npad) of several 1x1 heads as one GEMM operand:
+    N = sum of the head widths, zero-padded to a multiple of 8 so every row of y / dy is whole 16-byte chunks"""
+    ws = [w.detach().reshape(w.shape[0], -1) for w, _ in heads]
+    n = sum(w.shape[0] for w in ws)
+    npad = (n + 7) // 8 * 8
+    wcat = torch.zeros(npad, 1, 1, ws[0].shape[1], device=device, dtype=torch.float32)
+    wcat[:n, 0, 0] = torch.cat(ws, dim=0)
+    bcat = torch.zeros(npad, device=device, dtype=torch.float32)
+    bcat[:n] = torch.cat([b.detach() for _, b in heads])
+    wf, wd = hip.weight_prep(wcat, None, T, True, True)
+    return wf, wd, bcat, npad
+
+
+def _heads_add_grads(heads, dw, db):
+    """adds the row blocks of the fused heads' dW [Npad,1,1,K] / db [Npad] to each head's gradient buffers"""
+    off = 0
+    for w, b in heads:
+        n = w.shape[0]
+        _grad_buf(w).view(n, -1).add_(dw[off:off + n].view(n, -1)) if w.dim() == 2 else \
+            _ohwi(_grad_buf(w)).add_(dw[off:off + n])
+        _grad_buf(b).add_(db[off:off + n])
+        off += n
+
+
 class FusedHeadsFn(torch.autograd.Function):
     """Several 1x1 heads over the same input as ONE GEMM (N = sum of head widths, zero-padded to a multiple of 8 so
     every row of y / dy is whole 16-byte chunks): the RPN's objectness (A) + anchor-delta (4A) heads, rpn.py:173-176."""
 
     @staticmethod
     def forward(ctx, x, anchor, heads, out_f32):
-        T = x.dtype
-        K = heads[0][0].shape[1] if heads[0][0].dim() == 2 else heads[0][0].shape[1]
-        ws = [w.detach().reshape(w.shape[0], -1) for w, _ in heads]
-        n = sum(w.shape[0] for w in ws)
-        npad = (n + 7) // 8 * 8
-        wcat = torch.zeros(npad, 1, 1, ws[0].shape[1], device=x.device, dtype=torch.float32)
-        wcat[:n, 0, 0] = torch.cat(ws, dim=0)
-        bcat = torch.zeros(npad, device=x.device, dtype=torch.float32)
-        bcat[:n] = torch.cat([b.detach() for _, b in heads])
-        wf, wd = hip.weight_prep(wcat, None, T, True, True)
+        wf, wd, bcat, npad = _heads_operands(heads, x.dtype, x.device)
         y = hip.conv_fwd(x, wf, None, bcat, out_f32=out_f32)
         ctx.heads, ctx.wd, ctx.npad = heads, wd, npad
         ctx.save_for_backward(x)
@@ -539,6 +557,7 @@ class FusedHeadsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        # (restated in RpnHeadFn.backward's dense branch, as ConvFn.backward is: keep the two in step)
         (x,) = ctx.saved_tensors
         T = x.dtype
         dy = dy.contiguous()
@@ -547,13 +566,7 @@ class FusedHeadsFn(torch.autograd.Function):
         K = x.shape[-1]
         dw = hip.conv_wgrad(x, dy, (ctx.npad, 1, 1, K))
         db = hip.colsum(dy.view(-1, ctx.npad))
-        off = 0
-        for w, b in ctx.heads:
-            n = w.shape[0]
-            _grad_buf(w).view(n, -1).add_(dw[off:off + n].view(n, -1)) if w.dim() == 2 else \
-                _ohwi(_grad_buf(w)).add_(dw[off:off + n])
-            _grad_buf(b).add_(db[off:off + n])
-            off += n
+        _heads_add_grads(ctx.heads, dw, db)
         dx = hip.conv_fwd(dy, ctx.wd) if ctx.needs_input_grad[0] else None
         return dx, None, None, None
 
@@ -561,6 +574,135 @@ class FusedHeadsFn(torch.autograd.Function):
 def fused_heads(x, heads, out_f32=True):
     """heads: list of (weight [Ni,K,1,1] or [Ni,K], bias [Ni]).  Returns y [..., Npad]; slice per head."""
     return FusedHeadsFn.apply(x, heads[0][0], heads, out_f32)
+
+
+# ------------------------------------------------------------------------------------------------
+# RPN head as ONE node: 3x3 conv + ReLU -> fused heads, with a backward pass over the sampled rows only
+# ------------------------------------------------------------------------------------------------
+class ActiveRows:
+    """What the loss knows about the gradient it will send into the RPN head, handed to the head's node between its forward
+    and its backward pass: ``cap``, a host-side bound on the number of positions with a non-zero gradient row (the sampled
+    anchors' count: rpn.py:365-429 sums over them alone); None = unknown, the backward pass then runs dense."""
+
+    def __init__(self):
+        self.cap = None
+
+
+class _SparseOverflow:
+    """Device flag [1] int32 per device: a sparse backward pass found more active rows than the bound it was given, so rows were
+    dropped.  Read where the trainer reads back anyway (engine._write_metrics, next to FP8_SCALES.nonfinite); the run raises."""
+
+    def __init__(self):
+        self._flags = {}
+
+    def flag(self, device):
+        f = self._flags.get(device)
+        if f is None:
+            f = self._flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
+        return f
+
+    def flags(self):
+        return list(self._flags.values())
+
+
+RPN_SPARSE_OVERFLOW = _SparseOverflow()
+
+
+def rpn_sparse_bwd_rows(cap, positions, cout, elem_size):
+    """(rows the sparse backward pass of the RPN head costs, rows the dense one costs), both in rows of the 3x3 convolution's two
+    gradient GEMMs.  Dense: every position.  Sparse: ``cap`` rows, each also written and read once as an im2col row (9 Cin
+    elements of ``elem_size`` bytes) and as nine f32 partial rows (9 Cin x 4 bytes) -- 2 x 9 Cin x (elem_size + 4) bytes of
+    traffic next to the row's 2 x 2 x 9 Cin x Cout FLOP.  At the rates the two kinds of kernel reach here (1.4 PFLOP/s
+    in the staged GEMM loops, 4 TB/s streaming, i.e. 350 FLOP per byte) that traffic takes as long as
+    350 x (elem_size + 4) / (2 Cout) GEMM rows: one more row at Cout = 1024 in bf16, far more for a narrow layer."""
+    flop_per_byte = 350.0
+    return cap * (1.0 + flop_per_byte * (elem_size + 4) / (2.0 * cout)), float(positions)
+
+
+def rpn_sparse_bwd_wanted(cap, positions, cout, elem_size):
+    """Does the RPN head's backward pass take the sparse route?  Only with a known bound, and where it is cheaper by
+    ``rpn_sparse_bwd_rows`` (16 maps of 50 x 83 with 4096 sampled anchors: 8 300 against 66 400 rows; one 8 x 10 map with 256:
+    dense).  CDDMSL_RPN_SPARSE_BWD=0 / 1 forces never / always (A/B, tests; read per call)."""
+    if cap is None or cap <= 0:
+        return False
+    v = os.environ.get("CDDMSL_RPN_SPARSE_BWD", "")
+    if v in ("0", "1"):
+        return v == "1"
+    sparse, dense = rpn_sparse_bwd_rows(cap, positions, cout, elem_size)
+    return sparse < dense
+
+
+class RpnHeadFn(torch.autograd.Function):
+    """y = heads(relu(conv3x3(x, W) + b)) (rpn.py:66-177): the launches of ``ConvFn`` followed by ``FusedHeadsFn``, as one node so
+    that the backward pass can skip the rows whose gradient is zero.  ``active.cap`` (set by the loss before the backward pass)
+    bounds the rows of dy that are non-zero; the sparse route then
+      finds them on the device (a scan of dy, so correctness does not rest on WHICH anchors the caller sampled; more than cap
+        raises ``RPN_SPARSE_OVERFLOW``), gathers dy[rows] and the hidden activations t[rows],
+      heads:  dW_h, db_h from the gathered rows; G = (t[rows] > 0) * (dy[rows] W_h)  [cap, C]   -- no [positions, C] gradient, no relu_bwd pass
+      dW    = G^T im2col(x)[rows]   (the weight-gradient entry point as a 1x1 problem over 9 Cin), db = column sums of G
+      dx    = per pixel the sum, in tap order, of the f32 rows P[tap][slot[neighbour]], P[tap] = G W_tap (one batched GEMM)
+    The same non-zero products as the dense route, in another f32 summation order."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, pw, bias, heads, active):
+        T = x.dtype
+        KH, KW = _ohwi(pw.param).shape[1:3]
+        assert KH == KW and KH % 2 == 1, "the RPN head's hidden convolution is a square, odd, 'same' filter"
+        t = conv_fwd_auto(x, pw, None, bias.detach(), False, relu=True, stride=1, pad=(KH - 1) // 2)
+        wf, wd, bcat, npad = _heads_operands(heads, T, x.device)
+        y = hip.conv_fwd(t, wf, None, bcat, out_f32=True)
+        ctx.pw, ctx.bias, ctx.heads, ctx.wd_heads, ctx.npad, ctx.active = pw, bias, heads, wd, npad, active
+        ctx.save_for_backward(x, t)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, t = ctx.saved_tensors
+        T = x.dtype
+        w = ctx.pw.param
+        Cout, KH, KW, Cin = _ohwi(w).shape
+        pad, npad = (KH - 1) // 2, ctx.npad
+        M = t.numel() // Cout
+        dy = dy.contiguous()
+        if not rpn_sparse_bwd_wanted(ctx.active.cap, M, Cout, x.element_size()):
+            # the dense launches of FusedHeadsFn.backward, then ConvFn.backward (bf16 / f32 route), restated: a change there is mirrored here
+            if dy.dtype != T:
+                dy = dy.to(T)
+            dwh = hip.conv_wgrad(t, dy, (npad, 1, 1, Cout))
+            dbh = hip.colsum(dy.view(-1, npad))
+            _heads_add_grads(ctx.heads, dwh, dbh)
+            g = hip.relu_bwd(hip.conv_fwd(dy, ctx.wd_heads), t)
+            hip.conv_wgrad(x, g, (Cout, KH, KW, Cin), None, stride=1, pad=pad, out=_ohwi(_grad_buf(w)))
+            hip.colsum(g.view(-1, Cout), out=_grad_buf(ctx.bias))
+            dx = None
+            if ctx.needs_input_grad[0]:
+                _, wd = ctx.pw.get(T, need_dgrad=True)
+                dx = hip.conv_fwd(g, wd, stride=1, pad=KH - 1 - pad)
+            return dx, None, None, None, None, None
+        cap = int(ctx.active.cap)
+        rows, slot = hip.rpn_active_rows(dy.view(M, npad), cap, RPN_SPARSE_OVERFLOW.flag(dy.device))
+        dyg = hip.rpn_gather_rows(dy.view(M, npad), rows, T).view(1, 1, cap, npad)
+        tg = hip.rpn_gather_rows(t.view(M, Cout), rows, T).view(1, 1, cap, Cout)
+        dwh = hip.conv_wgrad(tg, dyg, (npad, 1, 1, Cout))
+        dbh = hip.colsum(dyg.view(cap, npad))
+        _heads_add_grads(ctx.heads, dwh, dbh)
+        g = hip.conv_fwd(dyg, ctx.wd_heads, relu_mask=tg)                                    # [1, 1, cap, Cout]
+        xg = hip.rpn_im2col_rows(x, rows, KH, KW, pad).view(1, 1, cap, KH * KW * Cin)
+        hip.conv_wgrad(xg, g, (Cout, 1, 1, KH * KW * Cin), out=_ohwi(_grad_buf(w)).view(Cout, 1, 1, KH * KW * Cin))
+        hip.colsum(g.view(cap, Cout), out=_grad_buf(ctx.bias))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            _, wd = ctx.pw.get(T, need_dgrad=True)                                           # [Cin, KH, KW, Cout], flipped
+            part = torch.empty(KH * KW, cap, Cin, device=x.device, dtype=torch.float32)
+            hip.gemm_nt_batched(g, wd, part, cap, Cin, Cout, Cout, KH * KW * Cout, Cin, KH * KW, 0, Cout, cap * Cin)
+            dx = hip.rpn_dx_gather(part, slot, x.shape, KH, KW, pad, T)
+        return dx, None, None, None, None, None
+
+
+def rpn_head(x, pw, bias, heads, active):
+    """The RPN head (3x3 conv + bias + ReLU, then ``fused_heads``) on x NHWC -> y [..., Npad] f32.  ``active``: an ``ActiveRows``
+    the caller fills in before the backward pass."""
+    return RpnHeadFn.apply(x, pw.param, pw, bias, heads, active)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -222,10 +222,17 @@ class StandardRPNHead(nn.Module):
         self.anchor_deltas = _Conv2d(in_channels, num_anchors * box_dim, 1)
 
     def forward_nhwc(self, x):
-        t = layers.conv(x, self.conv.pw(), self.conv.bias, 1, 1, relu=True, fp8=self.fp8)
         a = self.objectness_logits.weight.shape[0]
-        y = layers.fused_heads(t, [(self.objectness_logits.weight, self.objectness_logits.bias),
-                                   (self.anchor_deltas.weight, self.anchor_deltas.bias)])      # one GEMM, N = 5A (padded)
+        heads = [(self.objectness_logits.weight, self.objectness_logits.bias), (self.anchor_deltas.weight, self.anchor_deltas.bias)]
+        self.active_rows = None
+        if self.fp8 or not torch.is_grad_enabled():
+            # (fp8 configuration: the 3x3 convolution keeps its dense e4m3 gradients)
+            t = layers.conv(x, self.conv.pw(), self.conv.bias, 1, 1, relu=True, fp8=self.fp8)
+            y = layers.fused_heads(t, heads)      # one GEMM, N = 5A (padded)
+        else:
+            # one node for both layers: its backward pass runs over the sampled rows only, once the loss has told it how many
+            self.active_rows = layers.ActiveRows()
+            y = layers.rpn_head(x, self.conv.pw(), self.conv.bias, heads, self.active_rows)
         return y[..., :a], y[..., a:5 * a]     # NHWC f32: [N,H,W,A], [N,H,W,4A]
 
     def forward(self, features):
@@ -304,7 +311,10 @@ class RPN(nn.Module):
         gt_off = to_device_async(torch.tensor([0] + [len(g) for g in gts]).cumsum(0)[:-1], gl.device)
         gt_cat = torch.cat(gts) if sum(len(g) for g in gts) else torch.zeros((1, 4), device=gl.device)
         norm = self.batch_size_per_image * n
+        self.sampled_rows = None
         if logits.is_cuda and logits.dtype == torch.float32 and getattr(self, "last_neg_global", None) is not None:
+            # (both terms below touch the sampled anchors alone: at most this many positions get a gradient -- host integers, no read-back)
+            self.sampled_rows = int(pos_g.numel() + self.last_neg_global.numel())
             # both losses over the sampled anchors' index lists (known on the host side of the sampling: no mask, no dense pass)
             neg_g = self.last_neg_global
             self.storage["rpn/num_pos_anchors"] = pos_g.numel() / n      # (= (labels == 1).sum() / n: every positive label IS a sampled index)
@@ -376,6 +386,7 @@ class RPN(nn.Module):
         of stalling the queue.  The anchor and proposal samplers own separate generators, so the draw order is unchanged."""
         N, hf, wf, _ = res4.shape
         logits, deltas = self.rpn_head.forward_nhwc(res4)
+        active = getattr(self.rpn_head, "active_rows", None)       # (this pass's: the head may run again before the backward pass)
         lg = logits.reshape(N, -1)                # (N, Hi*Wi*A)   rpn.py:456-460
         dl = deltas.reshape(N, -1, 4)             # (N, Hi*Wi*A, 4) rpn.py:461-467 (NHWC already has (h,w,a,b) order)
         losses = {}
@@ -394,7 +405,10 @@ class RPN(nn.Module):
             if pending is None:
                 return {}
             labels, matched = self.label_anchors_finish(*pending)
-            return self.losses(anchors, lg, labels, dl, matched)
+            out = self.losses(anchors, lg, labels, dl, matched)
+            if active is not None and self.sampled_rows is not None:
+                active.cap = self.sampled_rows
+            return out
 
         if defer_losses:
             return finish(), losses_fn
