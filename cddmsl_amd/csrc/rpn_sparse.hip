@@ -9,9 +9,9 @@
 //   im2col   X[s][tap][c] = x[n][h + kh - pad][w + kw - pad][c] of position rows[s] = (n, h, w), zeros outside the image
 //   dx       dx[p][c]   = sum over taps, in tap order, of P[tap][slot[p + tap - pad]][c]  (f32 partials, rounded once)
 // No atomics: every output element has one writer and a fixed summation order.
-// Linked into a library of its own, libcddmsl_rpn_sparse.so, declared in include/cddmsl_rpn_sparse.h.
+// Declared in include/cddmsl_hip.h with every other entry point of libcddmsl_hip.so (common.h includes it: the compiler checks
+// each definition against its declaration).
 #include "common.h"
-#include "cddmsl_rpn_sparse.h"   // the compiler checks each entry point's definition against its declaration
 
 namespace {
 

@@ -10,12 +10,11 @@ from ctypes import c_float, c_int, c_long, c_void_p
 
 import torch
 
-from ._lib import check, lib, lib_rpn_sparse, ptr, require_cuda, stream_ptr
+from ._lib import check, lib, ptr, require_cuda, stream_ptr
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
 _L = lib      # the loaded library, every entry point typed from include/cddmsl_hip.h (_lib.py)
-_LR = lib_rpn_sparse      # the RPN head's sparse backward pass: libcddmsl_rpn_sparse.so, typed from include/cddmsl_rpn_sparse.h
 
 
 class _Profiler:
@@ -852,7 +851,7 @@ def colsum(x2d, period=1, out=None):
     return out
 
 
-# ---- sparse backward pass of the RPN head: the bookkeeping kernels around the GEMM entry points (csrc/rpn_sparse.hip, a library of its own)
+# ---- sparse backward pass of the RPN head: the bookkeeping kernels around the GEMM entry points (csrc/rpn_sparse.hip)
 def _rows_profiled(name, launch, what, shape, nbytes, flops=0.0):
     # (FLOP model: the copies and the scan do none; the gather-sum adds each partial row once)
     e0 = PROFILE.begin(name) if PROFILE.on else None
@@ -871,9 +870,9 @@ def rpn_active_rows(dy2d, cap, overflow):
     rows = torch.empty(cap, device=dy2d.device, dtype=torch.int32)
     slot = torch.empty(M, device=dy2d.device, dtype=torch.int32)
     f32 = int(dy2d.dtype == torch.float32)
-    _rows_profiled("rpn_mark_rows", lambda: _LR().cddmsl_rpn_mark_rows(ptr(dy2d), ptr(marks), M, cols, f32, 1 if f32 else 0, stream_ptr()),
+    _rows_profiled("rpn_mark_rows", lambda: _L().cddmsl_rpn_mark_rows(ptr(dy2d), ptr(marks), M, cols, f32, 1 if f32 else 0, stream_ptr()),
                    "cddmsl_rpn_mark_rows", (M, cols), dy2d.numel() * dy2d.element_size() + 4 * M)
-    _rows_profiled("rpn_compact_rows", lambda: _LR().cddmsl_rpn_compact_rows(ptr(marks), ptr(rows), ptr(slot), ptr(overflow), M, cap, stream_ptr()),
+    _rows_profiled("rpn_compact_rows", lambda: _L().cddmsl_rpn_compact_rows(ptr(marks), ptr(rows), ptr(slot), ptr(overflow), M, cap, stream_ptr()),
                    "cddmsl_rpn_compact_rows", (M, cap), 12 * M + 4 * cap)                 # (the marks twice, the slots once)
     return rows, slot
 
@@ -884,8 +883,8 @@ def rpn_gather_rows(src2d, rows, dtype):
     cap, cols = rows.numel(), src2d.shape[1]
     assert src2d.is_contiguous() and rows.dtype == torch.int32 and src2d.dtype in (dtype, torch.float32)
     out = torch.empty((cap, cols), device=src2d.device, dtype=dtype)
-    _rows_profiled("rpn_gather_rows", lambda: _LR().cddmsl_rpn_gather_rows(ptr(src2d), ptr(rows), ptr(out), cap, cols,
-                                                                          int(src2d.dtype == torch.float32 and dtype != torch.float32), DT[dtype], stream_ptr()),
+    _rows_profiled("rpn_gather_rows", lambda: _L().cddmsl_rpn_gather_rows(ptr(src2d), ptr(rows), ptr(out), cap, cols,
+                                                                         int(src2d.dtype == torch.float32 and dtype != torch.float32), DT[dtype], stream_ptr()),
                    "cddmsl_rpn_gather_rows", (cap, cols), cap * cols * (src2d.element_size() + out.element_size()) + 4 * cap)
     return out
 
@@ -898,7 +897,7 @@ def rpn_im2col_rows(x, rows, KH, KW, pad):
     cap = rows.numel()
     assert x.is_contiguous() and rows.dtype == torch.int32
     out = torch.empty((cap, KH * KW * C), device=x.device, dtype=x.dtype)
-    _rows_profiled("rpn_im2col_rows", lambda: _LR().cddmsl_rpn_im2col_rows(ptr(x), ptr(rows), ptr(out), cap, N, H, W, C, KH, KW, pad, _dt(x), stream_ptr()),
+    _rows_profiled("rpn_im2col_rows", lambda: _L().cddmsl_rpn_im2col_rows(ptr(x), ptr(rows), ptr(out), cap, N, H, W, C, KH, KW, pad, _dt(x), stream_ptr()),
                    "cddmsl_rpn_im2col_rows", (cap, KH * KW * C), 2 * out.numel() * out.element_size() + 4 * cap)
     return out
 
@@ -911,7 +910,7 @@ def rpn_dx_gather(P, slot, x_shape, KH, KW, pad, dtype):
     assert P.dtype == torch.float32 and P.is_contiguous() and taps == KH * KW and C2 == C and slot.numel() == N * H * W and slot.dtype == torch.int32
     dx = torch.empty(tuple(x_shape), device=P.device, dtype=dtype)
     # bytes: dx once, the slots, and every partial row once (a row of P[tap] is read by exactly one pixel)
-    _rows_profiled("rpn_dx_gather", lambda: _LR().cddmsl_rpn_dx_gather(ptr(P), ptr(slot), ptr(dx), cap, N, H, W, C, KH, KW, pad, DT[dtype], stream_ptr()),
+    _rows_profiled("rpn_dx_gather", lambda: _L().cddmsl_rpn_dx_gather(ptr(P), ptr(slot), ptr(dx), cap, N, H, W, C, KH, KW, pad, DT[dtype], stream_ptr()),
                    "cddmsl_rpn_dx_gather", (N * H * W, C, cap), dx.numel() * dx.element_size() + 4 * slot.numel() + P.numel() * 4, flops=P.numel())
     return dx
 

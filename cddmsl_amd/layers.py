@@ -423,47 +423,50 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        # (RpnHeadFn.backward's dense branch restates the bf16 / f32 launches below for the RPN head's 3x3 convolution: a change to
-        # them is mirrored there; tests/test_gpu_rpn_sparse_bwd.py::test_dense_route_is_conv_then_fused_heads holds the two bit-equal)
         x, y, x8 = ctx.saved_tensors
         stride, pad, relu, out_f32, train_w = ctx.cfg
-        # (fp8 configuration, only where the forward took the e4m3 kernel: one e4m3 copy of the gradient feeds both gradient GEMMs)
-        f8 = ctx.fp8 and x8 is not None and stride == 1
-        g_slot = fp8_slot_of(ctx.pw, "_fp8_g") if f8 else None
-        T = x.dtype
-        dy_in = dy
-        dy = dy.contiguous()
-        if relu:
-            dy = hip.relu_bwd(dy, y if y.dtype == T else y.to(T))
-        elif dy.dtype != T:
-            dy = bf16_of(dy) if T == torch.bfloat16 else dy.to(T)
-        w = ctx.pw.param
-        if train_w:
-            if f8:
-                wgrad_auto(x, dy, ctx.pw, None, pad, _ohwi(_grad_buf(w)), True, x8, g_slot, min_m=65536)
-            else:
-                hip.conv_wgrad(x, dy, _ohwi(w).shape, None, stride=stride, pad=pad, out=_ohwi(_grad_buf(w)))
-            if ctx.bias is not None:
-                hip.colsum(dy.view(-1, dy.shape[-1]), out=_grad_buf(ctx.bias))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            assert stride == 1, "input gradient of a strided conv is not on the hot path"
-            _, wd = ctx.pw.get(T, need_dgrad=True)
-            KH = _ohwi(w).shape[1]
-            Kd, rows = dy.shape[-1], dy.numel() // dy.shape[-1]
-            if KH == 1 and _ohwi(w).shape[2] == 1 and pad == 0 and rows <= 1024 and Kd >= 8192 and Kd % (16 * 64) == 0:
-                # few rows, very long reduction (the mapper's 1024 -> 40*768 linear: 544 x 1024 outputs over K = 30720 would be
-                # 12 tiles on 256 CUs): 16 reduction slices as one batched launch, f32 partial sums added afterwards
-                S, N = 16, x.shape[-1]
-                part = torch.empty(S, rows, N, device=dy.device, dtype=torch.float32)
-                hip.gemm_nt_batched(dy, wd, part, rows, N, Kd // S, Kd, Kd, N, S, Kd // S, Kd // S, rows * N)
-                dx = part.sum(0).to(T).view(x.shape)
-            elif f8:
-                dx = dgrad_auto(dy, ctx.pw, True, g_slot, pad=KH - 1 - pad)
-            else:
-                dx = hip.conv_fwd(dy, wd, stride=1, pad=KH - 1 - pad)
+        dx = _conv_backward(x, y, x8, dy, ctx.pw, ctx.bias, stride, pad, relu, train_w, ctx.needs_input_grad[0], ctx.fp8)
         # y = conv + residual (no ReLU with a residual): the residual's gradient is the incoming one, as it came
-        return dx, None, None, None, None, None, None, None, None, (dy_in if ctx.needs_input_grad[9] else None), None
+        return dx, None, None, None, None, None, None, None, None, (dy if ctx.needs_input_grad[9] else None), None
+
+
+def _conv_backward(x, y, x8, dy, pw, bias, stride, pad, relu, train_w, need_dx, fp8):
+    """Backward pass of y = relu?(conv(x, W) + b) (``ConvFn``; the 3x3 convolution of ``RpnHeadFn``'s dense route): adds dW / db to
+    their gradient buffers with ``train_w`` and returns dx (None without ``need_dx``).  ``y``: the saved output (ReLU only);
+    ``x8``: the forward's e4m3 copy of x, None where it did not take the e4m3 kernel."""
+    # (fp8 configuration, only where the forward took the e4m3 kernel: one e4m3 copy of the gradient feeds both gradient GEMMs)
+    f8 = fp8 and x8 is not None and stride == 1
+    g_slot = fp8_slot_of(pw, "_fp8_g") if f8 else None
+    T = x.dtype
+    dy = dy.contiguous()
+    if relu:
+        dy = hip.relu_bwd(dy, y if y.dtype == T else y.to(T))
+    elif dy.dtype != T:
+        dy = bf16_of(dy) if T == torch.bfloat16 else dy.to(T)
+    w = pw.param
+    if train_w:
+        if f8:
+            wgrad_auto(x, dy, pw, None, pad, _ohwi(_grad_buf(w)), True, x8, g_slot, min_m=65536)
+        else:
+            hip.conv_wgrad(x, dy, _ohwi(w).shape, None, stride=stride, pad=pad, out=_ohwi(_grad_buf(w)))
+        if bias is not None:
+            hip.colsum(dy.view(-1, dy.shape[-1]), out=_grad_buf(bias))
+    if not need_dx:
+        return None
+    assert stride == 1, "input gradient of a strided conv is not on the hot path"
+    _, wd = pw.get(T, need_dgrad=True)
+    KH = _ohwi(w).shape[1]
+    Kd, rows = dy.shape[-1], dy.numel() // dy.shape[-1]
+    if KH == 1 and _ohwi(w).shape[2] == 1 and pad == 0 and rows <= 1024 and Kd >= 8192 and Kd % (16 * 64) == 0:
+        # few rows, very long reduction (the mapper's 1024 -> 40*768 linear: 544 x 1024 outputs over K = 30720 would be
+        # 12 tiles on 256 CUs): 16 reduction slices as one batched launch, f32 partial sums added afterwards
+        S, N = 16, x.shape[-1]
+        part = torch.empty(S, rows, N, device=dy.device, dtype=torch.float32)
+        hip.gemm_nt_batched(dy, wd, part, rows, N, Kd // S, Kd, Kd, N, S, Kd // S, Kd // S, rows * N)
+        return part.sum(0).to(T).view(x.shape)
+    if f8:
+        return dgrad_auto(dy, pw, True, g_slot, pad=KH - 1 - pad)
+    return hip.conv_fwd(dy, wd, stride=1, pad=KH - 1 - pad)
 
 
 class FrozenMlpFn(torch.autograd.Function):
@@ -557,18 +560,20 @@ class FusedHeadsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        # (restated in RpnHeadFn.backward's dense branch, as ConvFn.backward is: keep the two in step)
         (x,) = ctx.saved_tensors
-        T = x.dtype
-        dy = dy.contiguous()
-        if dy.dtype != T:
-            dy = dy.to(T)
-        K = x.shape[-1]
-        dw = hip.conv_wgrad(x, dy, (ctx.npad, 1, 1, K))
-        db = hip.colsum(dy.view(-1, ctx.npad))
-        _heads_add_grads(ctx.heads, dw, db)
-        dx = hip.conv_fwd(dy, ctx.wd) if ctx.needs_input_grad[0] else None
-        return dx, None, None, None
+        return _heads_backward(x, dy.contiguous(), ctx.heads, ctx.wd, ctx.npad, ctx.needs_input_grad[0]), None, None, None
+
+
+def _heads_backward(x, dy, heads, wd, npad, need_dx):
+    """Backward pass of the fused heads' GEMM (``FusedHeadsFn``; the heads of ``RpnHeadFn``'s dense route) for a contiguous dy:
+    adds each head's dW / db to its gradient buffers and returns dx (None without ``need_dx``).  ``wd``: the input-gradient
+    weights of ``_heads_operands``."""
+    if dy.dtype != x.dtype:
+        dy = dy.to(x.dtype)
+    dw = hip.conv_wgrad(x, dy, (npad, 1, 1, x.shape[-1]))
+    db = hip.colsum(dy.view(-1, npad))
+    _heads_add_grads(heads, dw, db)
+    return hip.conv_fwd(dy, wd) if need_dx else None
 
 
 def fused_heads(x, heads, out_f32=True):
@@ -665,19 +670,9 @@ class RpnHeadFn(torch.autograd.Function):
         M = t.numel() // Cout
         dy = dy.contiguous()
         if not rpn_sparse_bwd_wanted(ctx.active.cap, M, Cout, x.element_size()):
-            # the dense launches of FusedHeadsFn.backward, then ConvFn.backward (bf16 / f32 route), restated: a change there is mirrored here
-            if dy.dtype != T:
-                dy = dy.to(T)
-            dwh = hip.conv_wgrad(t, dy, (npad, 1, 1, Cout))
-            dbh = hip.colsum(dy.view(-1, npad))
-            _heads_add_grads(ctx.heads, dwh, dbh)
-            g = hip.relu_bwd(hip.conv_fwd(dy, ctx.wd_heads), t)
-            hip.conv_wgrad(x, g, (Cout, KH, KW, Cin), None, stride=1, pad=pad, out=_ohwi(_grad_buf(w)))
-            hip.colsum(g.view(-1, Cout), out=_grad_buf(ctx.bias))
-            dx = None
-            if ctx.needs_input_grad[0]:
-                _, wd = ctx.pw.get(T, need_dgrad=True)
-                dx = hip.conv_fwd(g, wd, stride=1, pad=KH - 1 - pad)
+            # dense: the backward pass of FusedHeadsFn, then ConvFn's (bf16 / f32 route)
+            dt = _heads_backward(t, dy, ctx.heads, ctx.wd_heads, npad, True)
+            dx = _conv_backward(x, t, None, dt, ctx.pw, ctx.bias, 1, pad, True, True, ctx.needs_input_grad[0], False)
             return dx, None, None, None, None, None
         cap = int(ctx.active.cap)
         rows, slot = hip.rpn_active_rows(dy.view(M, npad), cap, RPN_SPARSE_OVERFLOW.flag(dy.device))

@@ -559,6 +559,30 @@ int cddmsl_layernorm_bwd_params(const void* dy, const float* x, const float* mea
 int cddmsl_adamw_step(float** params, const float** grads, float** exp_avg, float** exp_avg_sq, const long* sizes, int count, float lr,
                       float beta1, float beta2, float eps, float weight_decay, long step, void* stream);
 
+/* ---- Sparse backward pass of the RPN head (3x3 "same" conv + ReLU -> fused 1x1 heads) ------------------------------------
+ * The sampled loss (rpn.py:365-429) leaves the heads' output gradient non-zero on a few rows, and the convolution's two gradient
+ * GEMMs then run over those rows only, through cddmsl_conv_fwd / cddmsl_conv_wgrad / cddmsl_gemm_nt_batched.  These five
+ * (csrc/rpn_sparse.hip) are the bookkeeping around them; none uses atomics.
+ * rpn_mark_rows:    marks[r] (int) = 1 where row r of dy [rows][cols] holds anything but +-0 (a NaN marks its row), else 0.  dy is f32
+ *                   (src_f32) or `dtype`; a row is whole 16-byte chunks.
+ * rpn_compact_rows: rows_out[cap] = the marked positions in ascending order, -1 in the unused tail; slot[positions] = a position's
+ *                   index in rows_out, -1 if unmarked or past cap.  More than cap marks: overflow[0] = 1 (never cleared here) and the
+ *                   surplus rows are dropped -- the caller must read the flag and refuse the result.  One block; positions <= 2^30.
+ * rpn_gather_rows:  dst [cap][cols] (`dtype`) = src[rows[s]] (f32 with src_f32, else `dtype`), zeros where rows[s] < 0.
+ * rpn_im2col_rows:  out [cap][KH*KW][Cin] = x[n][h + kh - pad][w + kw - pad] of position rows[s] = (n*H + h)*W + w, zeros where the
+ *                   tap leaves the image or rows[s] < 0; x NHWC [Nimg][H][W][Cin], 2 pad == KH - 1 == KW - 1.
+ * rpn_dx_gather:    dx [Nimg][H][W][Cin] (`dtype`) = sum over taps (kh, kw), in that order, of P[kh*KW + kw][slot[q]], q = the
+ *                   position at (h + kh - pad, w + kw - pad) of the same image, skipped where q leaves the image or slot[q] < 0;
+ *                   P [KH*KW][cap][Cin] f32.  One f32 sum per element in a fixed order, rounded once: the same bits every call.
+ * Rows of cols / Cin elements are whole 16-byte chunks and every pointer is 16-byte aligned; anything else is CDDMSL_ERR_ARG. */
+int cddmsl_rpn_mark_rows(const void* dy, int* marks, long rows, int cols, int src_f32, int dtype, void* stream);
+int cddmsl_rpn_compact_rows(const int* marks, int* rows_out, int* slot, int* overflow, long positions, int cap, void* stream);
+int cddmsl_rpn_gather_rows(const void* src, const int* rows, void* dst, int cap, int cols, int src_f32, int dtype, void* stream);
+int cddmsl_rpn_im2col_rows(const void* x, const int* rows, void* out, int cap, int Nimg, int H, int W, int Cin, int KH, int KW, int pad,
+                           int dtype, void* stream);
+int cddmsl_rpn_dx_gather(const float* P, const int* slot, void* dx, int cap, int Nimg, int H, int W, int Cin, int KH, int KW, int pad,
+                         int dtype, void* stream);
+
 /* ---- Cityscapes instance boxes (input side, not the training step) -------------------------------------------------------
  * replaces the per-id `inst_image == instance_id` + np.nonzero loop of data/datasets/cityscapes.py:501-540 (from_json=False).
  * maps [B][H][W] instance ids, dtype 0 = uint16, 1 = int32.  For every map b, one record per id in [24, 34000) that occurs in it,

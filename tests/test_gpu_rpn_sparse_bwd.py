@@ -12,7 +12,7 @@ of the plain module with every materialised tensor rounded to bf16, floor 2^-8 (
 result of the node to set a limit).
 
 Four tests without a GPU: the row-count rule that chooses the route, the trainer raising on the overflow flag, the sparse
-kernels' library against its header, and the random cases' limits against graph_ref's caps."""
+kernels' entry points in the main library and its header, and the random cases' limits against graph_ref's caps."""
 import pytest
 import torch
 
@@ -343,9 +343,9 @@ def test_overflow_flag_makes_the_metrics_write_raise():
         layers.RPN_SPARSE_OVERFLOW._flags.pop(torch.device("cpu"), None)
 
 
-def test_library_exports_what_its_header_declares():
-    """libcddmsl_rpn_sparse.so against include/cddmsl_rpn_sparse.h, as tests/test_cabi_host.py holds libcddmsl_hip.so to its header: the
-    same names both ways, int return and one argtype per declared parameter; libcddmsl_hip.so exports none of them"""
+def test_sparse_kernels_live_in_the_main_library():
+    """the five entry points are declared in include/cddmsl_hip.h, exported by libcddmsl_hip.so and typed by _lib.lib() (int return, one
+    argtype per declared parameter), as tests/test_cabi_host.py holds every entry point; no library, loader or header beside them"""
     import ctypes
     import os
     import re
@@ -353,17 +353,19 @@ def test_library_exports_what_its_header_declares():
     import __graft_entry__ as g
     g.build()
     from cddmsl_amd import _lib
-    L = _lib.lib_rpn_sparse()
-    hdr = re.sub(r"/\*.*?\*/", " ", open(_lib.RPN_SPARSE_HEADER_PATH).read(), flags=re.S)
-    decls = {n: p.count(",") + 1 for n, p in re.findall(r"\bint\s+(cddmsl_\w+)\s*\(([^)]*)\)\s*;", hdr)}
-    assert sorted(decls) == ["cddmsl_rpn_compact_rows", "cddmsl_rpn_dx_gather", "cddmsl_rpn_gather_rows", "cddmsl_rpn_im2col_rows", "cddmsl_rpn_mark_rows"]
-    nm = lambda path: sorted(set(re.findall(r"\bT (cddmsl_\w+)", subprocess.check_output(["nm", "-D", "--defined-only", path], text=True))))
-    assert nm(_lib.RPN_SPARSE_LIB_PATH) == sorted(decls)
-    assert not set(nm(_lib.LIB_PATH)) & set(decls)
+    L = _lib.lib()
+    hdr = re.sub(r"/\*.*?\*/", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    five = ["cddmsl_rpn_compact_rows", "cddmsl_rpn_dx_gather", "cddmsl_rpn_gather_rows", "cddmsl_rpn_im2col_rows", "cddmsl_rpn_mark_rows"]
+    decls = {n: p.count(",") + 1 for n, p in re.findall(r"\bint\s+(cddmsl_\w+)\s*\(([^)]*)\)\s*;", hdr) if n in five}
+    assert sorted(decls) == five
+    exported = set(re.findall(r"\bT (cddmsl_\w+)", subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)))
+    assert set(decls) <= exported
     for n, k in decls.items():
         fn = getattr(L, n)
         assert fn.restype is ctypes.c_int and len(fn.argtypes) == k, n
-    assert os.path.dirname(_lib.RPN_SPARSE_LIB_PATH) == os.path.dirname(_lib.LIB_PATH)
+    stem = "rpn_sparse"                         # (the former side library's loader and header, named after the source file)
+    assert not hasattr(_lib, "lib_" + stem)
+    assert not [f for _, _, files in os.walk(os.path.dirname(_lib.HEADER_PATH)) for f in files if f == "cddmsl_" + stem + ".h"]
 
 
 def _random_case_list():
@@ -438,9 +440,9 @@ def test_mark_rows_beyond_one_sweep_of_its_grid():
 @gpu
 @pytest.mark.parametrize("tname", ["bf16", "f32"])
 def test_dense_route_is_conv_then_fused_heads(tname):
-    """CDDMSL_RPN_SPARSE_BWD=0: the node's dense branch restates ConvFn.backward and FusedHeadsFn.backward -- the same launches, so the
-    same bits as layers.conv followed by layers.fused_heads, in the output and in every gradient (shapes at which these kernels do not
-    split their reductions: the sums have one order)"""
+    """CDDMSL_RPN_SPARSE_BWD=0: the node's dense branch runs the backward passes of FusedHeadsFn and ConvFn (layers._heads_backward,
+    layers._conv_backward) -- the same launches, so the same bits as layers.conv followed by layers.fused_heads, in the output and in
+    every gradient (shapes at which these kernels do not split their reductions: the sums have one order)"""
     from cddmsl_amd import layers
     H, W = 5, 7
     T = DT[tname]
