@@ -154,6 +154,9 @@ def get_cfg():
                    "CLIP_GRADIENTS": {"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0},
                    "AMP": {"ENABLED": False}},
         "TEST": {"EVAL_PERIOD": 0, "DETECTIONS_PER_IMAGE": 100,
+                 # project-specific: GeneralizedRCNN.inference also returns its RPN proposals ("proposals") and the evaluation entry
+                 # points report their recall (box_proposals: AR@100 ... ARl@1000) next to the box AP of every test set
+                 "PROPOSAL_RECALL": False,
                  # test-time augmentation (defaults.py:718-721): multi-scale + flip views, merged by per-class NMS; results under *_TTA
                  "AUG": {"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000, "FLIP": True}},
         "OUTPUT_DIR": "./output",

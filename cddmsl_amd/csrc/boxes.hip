@@ -11,6 +11,7 @@
 // Bit-exactness: IoU and NMS use only f32 add/sub/mul/div in the reference's association order with
 // contraction off (no a*b+c patterns exist), IEEE division; indices are therefore identical to the CPU path.
 #include "common.h"
+#include "box_iou.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -182,15 +183,7 @@ __global__ __launch_bounds__(256) void k_nms_scan(const unsigned long long* mask
   if (t == 0) nkeep[img] = s_cnt;
 }
 
-// ---------------------------------------------------------------- fused IoU + Matcher
-__device__ __forceinline__ float iou_pair(const float* g, float x0, float y0, float x1, float y1, float ap) {
-  float w = fminf(g[2], x1) - fmaxf(g[0], x0);
-  float h = fminf(g[3], y1) - fmaxf(g[1], y0);
-  w = fmaxf(w, 0.f); h = fmaxf(h, 0.f);
-  float inter = w * h;
-  float ag = (g[2] - g[0]) * (g[3] - g[1]);
-  return inter > 0.f ? inter / (ag + ap - inter) : 0.f;
-}
+// ---------------------------------------------------------------- fused IoU + Matcher (iou_pair: box_iou.h)
 // pass 1: per prediction j: max/argmax over gt (first max), threshold label; per gt: atomic max over j.
 // gt [G][4] for this image, preds [P][4].  thresholds: up to 2 cut points t0 <= t1 with labels l0,l1,l2.
 __global__ void k_match1(const float* gt, int G, const float* preds, int P, long* matches, signed char* labels,

@@ -347,6 +347,9 @@ def build_trainer(cfg, per_rank_batch, height=800, width=1333, seed=1):
     from .modeling import build_model
     limit_host_threads()
     rank, _ = get_rank(), get_world_size()
+    if cfg.MODEL.META_ARCHITECTURE == "ProposalNetwork":      # run_step calls the caption branches, which such a model does not have
+        raise ValueError("MODEL.META_ARCHITECTURE ProposalNetwork cannot be trained by this trainer (its step runs the caption-consistency "
+                         "branches on the model); build it with modeling.build_model and evaluate it with --eval-only")
     model = build_model(cfg)
     model.proposal_generator.sample_generator.manual_seed(seed + rank)
     model.roi_heads.sample_generator.manual_seed(seed + rank + 7919)

@@ -343,10 +343,10 @@ def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False, prefi
     dicts = load_voc_instances(args.voc_root, args.voc_split, names)
     loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
     ev = PascalVOCDetectionEvaluator(args.voc_root, args.voc_split, args.voc_year, names)
-    res = inference_on_dataset(model, loader, ev)
+    res = inference_on_dataset(model, loader, with_proposal_recall(ev, model, cfg, dicts))
     if rank == 0:
-        print(prefix + str({k: round(v, 4) for k, v in res["bbox"].items()}))
-    if tta_enabled(cfg):            # train_caption_consistency.py:105-118,149-150: the same set again through the TTA model
+        _print_results(prefix, res)
+    if tta_enabled(cfg) and not is_proposal_network(model):            # train_caption_consistency.py:105-118,149-150: the same set again through the TTA model
         loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
         tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, ev))
         if rank == 0:
@@ -727,6 +727,291 @@ class COCODetectionEvaluator:
         return {"bbox": res}
 
 
+# ------------------------------------------------------------------------------------------------ proposal recall (AR)
+# evaluation/coco_evaluation.py:492-511: the named area ranges of _evaluate_box_proposals, in its order
+PROPOSAL_AREA_NAMES = ("all", "small", "medium", "large", "96-128", "128-256", "256-512", "512-inf")
+PROPOSAL_AREA_RNGS = ((0 ** 2, 1e5 ** 2), (0 ** 2, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e5 ** 2), (96 ** 2, 128 ** 2),
+                      (128 ** 2, 256 ** 2), (256 ** 2, 512 ** 2), (512 ** 2, 1e5 ** 2))
+PROPOSAL_LIMITS = (100, 1000)                            # coco_evaluation.py:284
+PROPOSAL_REPORTED = (("all", ""), ("small", "s"), ("medium", "m"), ("large", "l"))     # coco_evaluation.py:283: range, key suffix
+
+
+def proposal_area_bits(areas):
+    """stored areas -> u8 [G], bit a = the box counts in PROPOSAL_AREA_RNGS[a].  The reference compares
+    ``torch.as_tensor([area, ...])`` -- Python floats become float32 -- with ``lo <= area <= hi``, inclusive at both ends, the bounds
+    taking the tensor's type: so the areas pass through float32 first (1024.00001 is 1024 and counts as small AND as medium; an
+    integer below 2^24 is itself)."""
+    a = np.asarray(areas, dtype=np.float64).reshape(-1).astype(np.float32)
+    bits = np.zeros(len(a), dtype=np.uint8)
+    for i, (lo, hi) in enumerate(PROPOSAL_AREA_RNGS):
+        bits |= (((a >= np.float32(lo)) & (a <= np.float32(hi))).astype(np.uint8) << np.uint8(i))
+    return bits
+
+
+def proposal_ground_truth(dataset_dicts):
+    """{image id: (boxes f32 [g, 4] XYXY, range bits u8 [g])} in data-set order, as the recall walk reads the dicts: ``iscrowd``
+    boxes are left out (coco_evaluation.py:527-534), the area is the stored ``area``, else the box area"""
+    gt = OrderedDict()
+    for d in dataset_dicts:
+        anns = [a for a in d.get("annotations", []) if not a.get("iscrowd", 0)]
+        boxes = np.array([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4).astype(np.float32)
+        areas = [a.get("area", (a["bbox"][2] - a["bbox"][0]) * (a["bbox"][3] - a["bbox"][1])) for a in anns]
+        gt[str(d["image_id"])] = (boxes, proposal_area_bits(areas))
+    return gt
+
+
+def pairwise_iou_f32(boxes1, boxes2):
+    """structures/boxes.py:322-367 ``pairwise_iou`` in numpy f32, operation for operation: [N, M]"""
+    b1, b2 = np.asarray(boxes1, dtype=np.float32).reshape(-1, 4), np.asarray(boxes2, dtype=np.float32).reshape(-1, 4)
+    area1 = (b1[:, 2] - b1[:, 0]) * (b1[:, 3] - b1[:, 1])
+    area2 = (b2[:, 2] - b2[:, 0]) * (b2[:, 3] - b2[:, 1])
+    wh = np.minimum(b1[:, None, 2:], b2[None, :, 2:]) - np.maximum(b1[:, None, :2], b2[None, :, :2])
+    wh = np.maximum(wh, np.float32(0))
+    inter = wh[:, :, 0] * wh[:, :, 1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        iou = inter / (area1[:, None] + area2[None, :] - inter)
+    return np.where(inter > 0, iou, np.float32(0)).astype(np.float32)
+
+
+def proposal_cover_host(boxes, logits, gt_boxes, gt_rng, limits=PROPOSAL_LIMITS, num_ranges=len(PROPOSAL_AREA_RNGS)):
+    """``hip.proposal_cover``'s output for ONE image from the host walk -- the per-image body of ``_evaluate_box_proposals``
+    (coco_evaluation.py:517-571) for every (limit, area range): ``boxes`` f32 [P, 4] XYXY, ``logits`` f32 [P], ``gt_boxes`` f32
+    [G, 4], ``gt_rng`` u8 [G] (``proposal_area_bits``; crowd boxes left out or without a bit), ``limits``: ints, None = no limit
+    -> cover f32 [L, A, G]: -1 = the box is not counted (bit clear, or P == 0: the reference skips an image without proposals
+    before it adds to num_pos), else the IoU recorded on the box, 0.0 when the walk ended before it.
+    The proposals are ranked by logit descending, stably (equal logits by input index, NaN last; the reference's ``Tensor.sort`` is
+    not stable, so with equal logits this is one of its possible orders); a pick is ``overlaps.max(dim=0)`` then ``.max(dim=0)`` with
+    the first maximal index each time.  The no-device path, and what an image beyond the kernel's caps goes through."""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    logits = np.asarray(logits, dtype=np.float32).reshape(-1)
+    gt_boxes = np.asarray(gt_boxes, dtype=np.float32).reshape(-1, 4)
+    gt_rng = np.asarray(gt_rng, dtype=np.uint8).reshape(-1)
+    P, G = len(logits), len(gt_rng)
+    cover = -np.ones((len(limits), num_ranges, G), dtype=np.float32)
+    if P == 0 or G == 0:
+        return cover
+    order = np.argsort(-logits, kind="stable")              # NaN last, equal logits by input index
+    iou = pairwise_iou_f32(boxes[order], gt_boxes)          # independent of limit and range: rows by rank
+    for li, limit in enumerate(limits):
+        pk = P if limit is None else min(P, max(int(limit), 0))
+        for a in range(num_ranges):
+            cols = np.flatnonzero((gt_rng >> a) & 1)
+            if not cols.size:
+                continue
+            overlaps = iou[:pk][:, cols].copy()
+            rec = np.zeros(len(cols), dtype=np.float32)
+            for _ in range(min(pk, len(cols))):
+                argmax_overlaps = overlaps.argmax(axis=0)   # (numpy, like torch on the host, returns the first maximal index)
+                max_overlaps = overlaps[argmax_overlaps, np.arange(len(cols))]
+                gt_ind = int(max_overlaps.argmax())
+                box_ind = int(argmax_overlaps[gt_ind])
+                rec[gt_ind] = overlaps[box_ind, gt_ind]
+                overlaps[box_ind, :] = -1
+                overlaps[:, gt_ind] = -1
+            cover[li, a, cols] = rec
+    return cover
+
+
+def proposal_recall_stats(values):
+    """The tail of ``_evaluate_box_proposals`` (coco_evaluation.py:572-592), its own expressions, on one (limit, range)'s cover
+    values of all images (-1 = not counted) -> {"ar", "recalls", "thresholds", "gt_overlaps", "num_pos"}"""
+    values = np.asarray(values, dtype=np.float32).reshape(-1)
+    counted = values >= 0
+    num_pos = int(counted.sum())
+    gt_overlaps, _ = torch.sort(torch.from_numpy(np.ascontiguousarray(values[counted])))
+    thresholds = torch.arange(0.5, 0.95 + 1e-5, 0.05, dtype=torch.float32)
+    recalls = torch.zeros_like(thresholds)
+    for i, t in enumerate(thresholds):
+        recalls[i] = (gt_overlaps >= t).float().sum() / float(num_pos)      # (num_pos == 0: 0 / 0, a NaN, as in the reference)
+    return {"ar": recalls.mean(), "recalls": recalls, "thresholds": thresholds, "gt_overlaps": gt_overlaps, "num_pos": num_pos}
+
+
+class ProposalRecallEvaluator:
+    """Proposal recall, the ``box_proposals`` task of the reference's COCO evaluator (``COCOEvaluator._eval_box_proposals`` over
+    ``_evaluate_box_proposals``, coco_evaluation.py:253-290,484-592), with the ``reset / process / evaluate`` protocol and rank-0
+    gather of the other evaluators.  ``process`` reads ``output["proposals"]`` (``proposal_boxes``, ``objectness_logits``) -- what
+    ``ProposalNetwork`` returns, and ``GeneralizedRCNN`` with ``TEST.PROPOSAL_RECALL`` -- and ``evaluate`` returns
+    ``{"box_proposals": {"AR@100", "ARs@100", "ARm@100", "ARl@100", "AR@1000", ...}}`` in percent: per image the proposals are ranked
+    by objectness and cut at the limit, then the best-covered unused ground-truth box is retired with its proposal until either runs
+    out; recall = the share of counted boxes covered at IoU >= t, averaged over t = .50:.05:.95.  NaN where no box is counted.
+    An image without any proposal does not count its boxes (the reference skips it before ``num_pos``), ``iscrowd`` boxes are left
+    out, the area ranges judge the stored ``area`` (else the box area) after a pass through float32, inclusive at both ends.
+
+    ``device``: a GPU device moves the walk there.  The ground truth is uploaded once; ``process`` copies nothing to the host and
+    does not synchronise -- one ``hip.proposal_cover`` launch per call; ``evaluate`` reads the cover records back in ONE copy and
+    gathers only those to rank 0.  Same dictionary as without ``device``, value for value.  An image beyond the kernel's caps
+    (hip.PROPOSAL_COVER_MAX_PROPOSALS / PROPOSAL_COVER_MAX_GT) is walked by ``proposal_cover_host``, never truncated."""
+
+    def __init__(self, dataset_dicts, device=None, limits=PROPOSAL_LIMITS):
+        self.limits = tuple(limits)
+        self.num_ranges = len(PROPOSAL_REPORTED)
+        assert [n for n, _ in PROPOSAL_REPORTED] == list(PROPOSAL_AREA_NAMES[: self.num_ranges])
+        self.device = torch.device(device) if device is not None and torch.device(device).type != "cpu" else None
+        self._gt = proposal_ground_truth(dataset_dicts)
+        self._index = {k: i for i, k in enumerate(self._gt)}          # image id -> data-set index
+        self._gt_list = list(self._gt.values())
+        if self.device is not None:
+            from . import hip
+            self._gt_dev = hip.ProposalGroundTruth.from_host(self._gt_list, self.limits, self.num_ranges, self.device)
+        self.reset()
+
+    def reset(self):
+        self._cover = {}                 # data-set index -> cover [L, A, g] of the image
+        self._batches = []               # device path: one entry per process() call, everything still on the device
+
+    def _process_device(self, inputs, outputs):
+        from . import hip
+        from ._lib import to_device_async
+        idx, boxes, logits = [], [], []
+        for inp, out in zip(inputs, outputs):
+            i = self._index.get(str(inp["image_id"]))
+            if i is None:                # not an image of this data set
+                continue
+            prop = out["proposals"]
+            idx.append(i)
+            boxes.append(prop.proposal_boxes.tensor.detach().float().reshape(-1, 4).to(self.device, non_blocking=True))
+            logits.append(prop.objectness_logits.detach().float().reshape(-1).to(self.device, non_blocking=True))
+        if not idx:
+            return
+        lens = [len(s) for s in logits]
+        gcounts = [len(self._gt_list[i][1]) for i in idx]
+        n = len(idx)
+        meta = to_device_async(torch.tensor(np.concatenate([[0], np.cumsum(lens), idx, [0], np.cumsum(gcounts)]).astype(np.int64)), self.device)
+        b, s = torch.cat(boxes).contiguous(), torch.cat(logits).contiguous()
+        cover, over = hip.proposal_cover(b, s, meta[: n + 1], meta[n + 1: 2 * n + 1], meta[2 * n + 1:], sum(gcounts), self._gt_dev)
+        self._batches.append({"idx": idx, "lens": lens, "gcounts": gcounts, "boxes": b, "logits": s, "cover": cover, "over": over})
+
+    def _device_records(self):
+        """the ONE readback -> {data-set index: cover [L, A, g]}; an image processed twice: the later call replaces the earlier"""
+        rec = {}
+        if not self._batches:
+            return rec
+        host = torch.cat([e["cover"].reshape(-1) for e in self._batches] + [e["over"].view(torch.float32) for e in self._batches]).cpu().numpy()
+        L, A = len(self.limits), self.num_ranges
+        sizes = [L * A * sum(e["gcounts"]) for e in self._batches]
+        over = np.ascontiguousarray(host[sum(sizes):]).view(np.int32)
+        pos, j0 = 0, 0
+        for e, size in zip(self._batches, sizes):
+            cover = host[pos: pos + size].reshape(L, A, -1)
+            pos += size
+            nb = len(e["idx"])
+            starts = np.concatenate([[0], np.cumsum(e["gcounts"])])
+            pstarts = np.concatenate([[0], np.cumsum(e["lens"])])
+            bx = lg = None
+            for j, i in enumerate(e["idx"]):
+                if over[j0 + j]:                                     # beyond a cap of the kernel: the host walk, on the same values
+                    if bx is None:
+                        bx, lg = e["boxes"].cpu().numpy(), e["logits"].cpu().numpy()
+                    gb, gr = self._gt_list[i]
+                    rec[i] = proposal_cover_host(bx[pstarts[j]: pstarts[j + 1]], lg[pstarts[j]: pstarts[j + 1]], gb, gr, self.limits, A)
+                else:
+                    rec[i] = cover[:, :, starts[j]: starts[j + 1]].copy()
+            j0 += nb
+        return rec
+
+    def process(self, inputs, outputs):
+        if self.device is not None:
+            return self._process_device(inputs, outputs)
+        for inp, out in zip(inputs, outputs):
+            i = self._index.get(str(inp["image_id"]))
+            if i is None:
+                continue
+            prop = out["proposals"]
+            gb, gr = self._gt_list[i]
+            self._cover[i] = proposal_cover_host(prop.proposal_boxes.tensor.detach().float().cpu().numpy(),
+                                                 prop.objectness_logits.detach().float().cpu().numpy(), gb, gr, self.limits, self.num_ranges)
+
+    def _gathered(self):
+        import torch.distributed as dist
+        rec = self._device_records() if self.device is not None else self._cover
+        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            return rec
+        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+        dist.gather_object(rec, parts, dst=0)
+        if dist.get_rank() != 0:
+            return None
+        merged = {}
+        for part in parts:
+            merged.update(part)
+        return merged
+
+    def stats(self, rec):
+        """{(limit index, range index): ``proposal_recall_stats``} over the images of ``rec`` in data-set order"""
+        out = {}
+        for li in range(len(self.limits)):
+            for a in range(self.num_ranges):
+                vals = [rec[i][li, a] for i in sorted(rec)]
+                out[li, a] = proposal_recall_stats(np.concatenate(vals) if vals else np.zeros(0, dtype=np.float32))
+        return out
+
+    def evaluate(self):
+        rec = self._gathered()
+        if rec is None:
+            return None
+        st = self.stats(rec)
+        res = OrderedDict()
+        for li, limit in enumerate(self.limits):
+            for a, (_, suffix) in enumerate(PROPOSAL_REPORTED):
+                key = "AR{}@{}".format(suffix, "all" if limit is None else "{:d}".format(limit))
+                res[key] = float(st[li, a]["ar"].item() * 100)          # coco_evaluation.py:287-288
+        return {"box_proposals": res}
+
+
+class DatasetEvaluators:
+    """evaluation/evaluator.py:67-100: several evaluators behind one ``reset / process / evaluate``; ``evaluate`` merges their
+    dictionaries (on the rank that has them) and refuses a task two of them report"""
+
+    def __init__(self, evaluators):
+        self._evaluators = list(evaluators)
+
+    def reset(self):
+        for e in self._evaluators:
+            e.reset()
+
+    def process(self, inputs, outputs):
+        for e in self._evaluators:
+            e.process(inputs, outputs)
+
+    def evaluate(self):
+        results, any_result = OrderedDict(), False
+        for e in self._evaluators:
+            res = e.evaluate()               # (every evaluator gathers, so every rank calls every one)
+            if res is None:
+                continue
+            any_result = True
+            for k, v in res.items():
+                if k in results:
+                    raise ValueError(f"Different evaluators produce results with the same key {k}")
+                results[k] = v
+        return results if any_result else None
+
+
+def proposal_recall_enabled(cfg):
+    return bool(cfg.TEST.get("PROPOSAL_RECALL", False))
+
+
+def is_proposal_network(model):
+    """a model whose outputs hold ``"proposals"`` only (``ProposalNetwork.proposals_only``)"""
+    return bool(getattr(getattr(model, "module", model), "proposals_only", False))
+
+
+def with_proposal_recall(evaluator, model, cfg, dicts):
+    """the evaluator of one test set's plain pass: ``evaluator`` itself, paired with a ``ProposalRecallEvaluator`` under
+    ``TEST.PROPOSAL_RECALL``, replaced by one for a ``ProposalNetwork`` (its outputs hold proposals only)"""
+    if is_proposal_network(model):
+        return ProposalRecallEvaluator(dicts, device=cfg.MODEL.DEVICE)
+    if proposal_recall_enabled(cfg):
+        return DatasetEvaluators([evaluator, ProposalRecallEvaluator(dicts, device=cfg.MODEL.DEVICE)])
+    return evaluator
+
+
+def _print_results(prefix, res):
+    """one line per task of a result dict: the box AP line as it always was, then the others"""
+    for task, metrics in res.items():
+        print(prefix + str({k: round(v, 4) for k, v in metrics.items()} if task == "bbox" else {task: {k: round(v, 4) for k, v in metrics.items()}}),
+              flush=True)
+
+
 _VOC_EVALUATORS = {}            # (name, datasets root, device) -> PascalVOCDetectionEvaluator of run_eval_only_catalog
 
 
@@ -776,11 +1061,11 @@ def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_res
             continue
         loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
         new_evaluator = (lambda: voc) if voc is not None else (lambda: COCODetectionEvaluator(dicts, classes, device=cfg.MODEL.DEVICE))
-        res = inference_on_dataset(model, loader, new_evaluator())
+        res = inference_on_dataset(model, loader, with_proposal_recall(new_evaluator(), model, cfg, dicts))
         if rank == 0:
-            print(f"{prefix}{name}: " + str({k: round(v, 4) for k, v in res["bbox"].items()}), flush=True)
+            _print_results(f"{prefix}{name}: ", res)
             results[name] = res
-        if tta_enabled(cfg):
+        if tta_enabled(cfg) and not is_proposal_network(model):
             loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
             tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, new_evaluator()))
             if rank == 0:

@@ -10,7 +10,7 @@ from ctypes import c_float, c_int, c_long, c_void_p
 
 import torch
 
-from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from ._lib import check, lib, lib_proposal_recall, ptr, require_cuda, stream_ptr
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
@@ -1245,6 +1245,73 @@ def coco_match(dt_boxes, dt_scores, dt_cls, dt_off, img_idx, gt, num_classes, ma
                                  gt.rngs.shape[0], int(num_classes), int(max_dets), ptr(rank), ptr(matched), ptr(ignored), ptr(over),
                                  stream_ptr()), "cddmsl_coco_match")
     return rank, matched, ignored, over
+
+
+# cddmsl_proposal_cover (libcddmsl_proposal_recall.so, include/cddmsl_proposal_recall.h): what one image may hold; an image beyond a cap comes back flagged in ``over`` and is walked on the host
+PROPOSAL_COVER_MAX_PROPOSALS = 2048  # proposals of one image (the RPN's post-NMS top-k is 2000 in training, 1000 at test time)
+PROPOSAL_COVER_MAX_GT = 512          # ground-truth boxes of one image
+PROPOSAL_COVER_MAX_LIMITS = 4        # proposal limits per launch
+PROPOSAL_COVER_MAX_RANGES = 8        # area ranges per launch (one bit each in ``rng``)
+
+
+class ProposalGroundTruth:
+    """A data set's ground truth on the device, as cddmsl_proposal_cover reads it: ``boxes`` f32 [G, 4] XYXY, ``rng`` u8 [G] (bit a =
+    the box counts in area range a; a crowd box has no bit) concatenated over the images, ``off`` int64 [n_images + 1]; plus the
+    walk's ``limits`` int32 [L] (a value >= PROPOSAL_COVER_MAX_PROPOSALS is "no limit") and the number of ranges ``A``.  Built once
+    per evaluator from host arrays (``from_host``)."""
+
+    def __init__(self, boxes, rng, off, limits, num_ranges):
+        require_cuda(boxes, rng, off, limits)
+        G = rng.numel()
+        assert boxes.dtype == torch.float32 and rng.dtype == torch.uint8 and off.dtype == torch.int64 and limits.dtype == torch.int32
+        assert tuple(boxes.shape) == (G, 4) and off.dim() == 1 and off.numel() >= 1 and limits.dim() == 1
+        assert all(t.is_contiguous() for t in (boxes, rng, off, limits))
+        if not 1 <= limits.numel() <= PROPOSAL_COVER_MAX_LIMITS:
+            raise ValueError(f"proposal_cover: {limits.numel()} limits outside [1, {PROPOSAL_COVER_MAX_LIMITS}]")
+        if not 1 <= num_ranges <= PROPOSAL_COVER_MAX_RANGES:
+            raise ValueError(f"proposal_cover: {num_ranges} area ranges outside [1, {PROPOSAL_COVER_MAX_RANGES}]")
+        self.boxes, self.rng, self.off, self.limits, self.num_ranges = boxes, rng, off, limits, int(num_ranges)
+        self.n_images, self.n_boxes = off.numel() - 1, G
+
+    @classmethod
+    def from_host(cls, per_image, limits, num_ranges, device):
+        """``per_image``: [(boxes [g, 4] f32 XYXY, rng [g] u8)] numpy, in data-set order; ``limits``: ints, None = no limit"""
+        import numpy as np
+        from ._lib import to_device_async
+        boxes = np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 4) for b, _ in per_image] or [np.zeros((0, 4), dtype=np.float32)])
+        rng = np.concatenate([np.asarray(r, dtype=np.uint8).reshape(-1) for _, r in per_image] or [np.zeros(0, dtype=np.uint8)])
+        off = np.zeros(len(per_image) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for _, r in per_image])
+        lim = np.asarray([PROPOSAL_COVER_MAX_PROPOSALS if l is None else min(max(int(l), 0), PROPOSAL_COVER_MAX_PROPOSALS) for l in limits],
+                         dtype=np.int32)
+        up = lambda a: to_device_async(torch.from_numpy(np.ascontiguousarray(a)), device)
+        return cls(up(boxes), up(rng), up(off), up(lim), num_ranges)
+
+
+@_timed("proposal_cover")
+def proposal_cover(boxes, logits, off, img_idx, cover_off, num_slots, gt):
+    """The per-image walk of ``_evaluate_box_proposals`` for every (image, limit, area range) of a batch in one launch
+    (cddmsl_proposal_cover), bit-identical to ``evaluation.proposal_cover_host`` per image.  ``boxes`` f32 [P, 4] XYXY, ``logits`` f32
+    [P]: the batch's proposals, image after image in any order inside an image, with offsets ``off`` int64 [B + 1]; ``img_idx`` int64
+    [B]: the images' indices into ``gt`` (a ``ProposalGroundTruth``); ``cover_off`` int64 [B + 1]: the running sum of the batch
+    images' ground-truth counts, ``num_slots`` its last value (a host int).  All on the device; nothing is read back and nothing
+    synchronises.
+    -> (cover f32 [L, A, num_slots]: per ground-truth box -1 = not counted (outside the range, or an image without proposals), else the
+    IoU the walk recorded on it, 0.0 when the walk ended before it; over int32 [B]: 1 = the image exceeds a cap
+    (PROPOSAL_COVER_MAX_PROPOSALS / PROPOSAL_COVER_MAX_GT), none of its slots is written and the caller has to walk it on the host)."""
+    require_cuda(boxes, logits, off, img_idx, cover_off)
+    P, B = logits.numel(), img_idx.numel()
+    assert boxes.dtype == logits.dtype == torch.float32 and off.dtype == img_idx.dtype == cover_off.dtype == torch.int64
+    assert tuple(boxes.shape) == (P, 4) and off.numel() == B + 1 and cover_off.numel() == B + 1
+    assert boxes.is_contiguous() and logits.is_contiguous() and off.is_contiguous() and img_idx.is_contiguous() and cover_off.is_contiguous()
+    dev = boxes.device
+    L, A = gt.limits.numel(), gt.num_ranges
+    cover = torch.empty((L, A, int(num_slots)), device=dev, dtype=torch.float32)
+    over = torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib_proposal_recall().cddmsl_proposal_cover(ptr(boxes), ptr(logits), ptr(off), ptr(img_idx), B, P, ptr(gt.boxes), ptr(gt.rng), ptr(gt.off),
+                                     gt.n_images, gt.n_boxes, ptr(gt.limits), L, A, ptr(cover_off), int(num_slots), ptr(cover), ptr(over),
+                                     stream_ptr()), "cddmsl_proposal_cover")
+    return cover, over
 
 
 VOC_MATCH_MAX_THRS = 16              # cddmsl_voc_match: IoU thresholds per launch (one bit each in the u16 masks)

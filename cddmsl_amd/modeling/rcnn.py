@@ -93,6 +93,8 @@ class GeneralizedRCNN(nn.Module):
         self.share_source_pass = False
         self._shared = None
         self.defer_rpn_losses = True
+        # TEST.PROPOSAL_RECALL (project-specific): ``inference`` also returns the RPN proposals it computes anyway
+        self.return_proposals = bool(cfg.TEST.get("PROPOSAL_RECALL", False))
 
     @property
     def device(self):
@@ -223,11 +225,18 @@ class GeneralizedRCNN(nn.Module):
     def inference(self, batched_inputs: List[Dict], detected_instances=None, do_postprocess: bool = True):
         assert not self.training
         images, sizes = self.preprocess_image(batched_inputs, "image")
-        results = self._inference_preprocessed(images, sizes, detected_instances)
-        return self._postprocess(results, batched_inputs, sizes) if do_postprocess else results
+        keep = [] if self.return_proposals and do_postprocess and detected_instances is None else None
+        results = self._inference_preprocessed(images, sizes, detected_instances, keep_proposals=keep)
+        if not do_postprocess:
+            return results
+        out = self._postprocess(results, batched_inputs, sizes)
+        if keep:        # the same proposals the box head was given, rescaled like the detections (detector_postprocess clones the boxes)
+            for o, p, inp, size in zip(out, keep[0], batched_inputs, sizes):
+                o["proposals"] = detector_postprocess(p, inp.get("height", size[0]), inp.get("width", size[1]))
+        return out
 
     @torch.no_grad()
-    def _inference_preprocessed(self, images, sizes, detected_instances=None):
+    def _inference_preprocessed(self, images, sizes, detected_instances=None, keep_proposals=None):
         """``inference`` behind ``preprocess_image``: images = the normalised, zero-padded NHWC batch in the compute dtype, sizes = each
         image's (h, w) inside it -> per-image Instances in the coordinates of those sizes (no postprocess).  The entry of callers that
         make the batch tensor themselves (test-time augmentation builds its views on the device)."""
@@ -236,6 +245,8 @@ class GeneralizedRCNN(nn.Module):
         feats = {"res4": to_nchw(res4)}
         if detected_instances is None:
             proposals, _ = self.proposal_generator.forward_nhwc(sizes, res4, None)
+            if keep_proposals is not None:
+                keep_proposals.append(proposals)
             kw = dict(res5=self.backbone.layer4, attnpool=self.backbone.attnpool) if self.use_clip_c4 else {}
             results, _ = self.roi_heads(ImageList(None, sizes), feats, proposals, None, **kw)
         else:
@@ -308,6 +319,47 @@ class GeneralizedRCNN(nn.Module):
         losses.update(detector_losses)
         losses.update(proposal_losses)
         return losses
+
+
+@META_ARCH_REGISTRY.register()
+class ProposalNetwork(nn.Module):
+    """meta_arch/rcnn.py:787-937: backbone + proposal generator only.  Training mode returns the RPN loss dict, eval mode
+    ``[{"proposals": Instances(proposal_boxes, objectness_logits)}]`` rescaled to the input's ``height`` / ``width``.  The parameter
+    names are the detector's ``backbone.*`` / ``proposal_generator.*``, so a detector checkpoint loads (``strict=False`` skips the
+    rest).  The trainer does not take it (``build_trainer`` refuses): the reference's ``run_step`` would call the caption branches
+    on it too."""
+    proposals_only = True       # what the evaluation entry points ask: no "instances" in the outputs, box_proposals is the only task
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.backbone = build_backbone(cfg)
+        self.proposal_generator = build_proposal_generator(cfg, self.backbone.output_shape())
+        self.input_format = cfg.INPUT.FORMAT
+        self.pixel_mean_list, self.pixel_std_list = list(cfg.MODEL.PIXEL_MEAN), list(cfg.MODEL.PIXEL_STD)
+        self.register_buffer("pixel_mean", torch.tensor(self.pixel_mean_list).view(-1, 1, 1), False)
+        self.register_buffer("pixel_std", torch.tensor(self.pixel_std_list).view(-1, 1, 1), False)
+        self.div_pixel = sum(self.pixel_mean_list) < 3.0
+        assert not self.div_pixel or self.input_format == "RGB"
+        self.compute_dtype = self.backbone.compute_dtype
+
+    @property
+    def device(self):
+        return self.pixel_mean.device
+
+    def forward(self, batched_inputs: List[Dict]):
+        imgs = [x["image"].to(self.device).contiguous() for x in batched_inputs]
+        sizes = [tuple(i.shape[-2:]) for i in imgs]
+        Hp, Wp = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        images = hip.preprocess(imgs, Hp, Wp, self.pixel_mean_list, self.pixel_std_list, self.compute_dtype, div255=self.div_pixel)
+        res4 = self.backbone.forward_nhwc(images, want_res5=False)["res4"]
+        if self.training:
+            gts = [as_instances(x["instances"]).to(self.device) for x in batched_inputs]
+            _, losses = self.proposal_generator.forward_nhwc(sizes, res4, gts)
+            return losses
+        with torch.no_grad():
+            proposals, _ = self.proposal_generator.forward_nhwc(sizes, res4, None)
+        return [{"proposals": detector_postprocess(p, inp.get("height", size[0]), inp.get("width", size[1]))}
+                for p, inp, size in zip(proposals, batched_inputs, sizes)]
 
 
 def build_model(cfg):

@@ -14,6 +14,8 @@ cddmsl_amd/coco_json.py) and for the VOC family of the VOC config (cddmsl_amd/vo
 chained into one paired loader, Pascal VOC AP on ``voc_2007_test`` / ``Clipart1k_test`` / ``Watercolor_test`` / ``Comic_test`` by name;
 ``--voc-root`` with ``--dt-data`` keeps precedence), ``TEST.EVAL_PERIOD`` repeats that evaluation during training whenever a test set is given, and
 ``MODEL.WEIGHTS`` / ``--resume`` / ``MODEL.PRE_TRAINED_RCLIP_PATH`` go through cddmsl_amd/checkpoint.py.
+``TEST.PROPOSAL_RECALL True`` adds a ``box_proposals`` line (AR@100 ... ARl@1000 of the RPN proposals) per test set to every
+evaluation; ``--eval-only MODEL.META_ARCHITECTURE ProposalNetwork`` evaluates backbone + RPN alone and prints only that line.
 """
 import argparse
 import os
@@ -77,6 +79,27 @@ def build_eval_hook(tr, cfg, args, rank, world, max_iter):
     return evaluation.PeriodicEval(tr, period, fn, max_iter, rank)
 
 
+def eval_proposal_network(cfg, args, rank, world):
+    """--eval-only with MODEL.META_ARCHITECTURE ProposalNetwork: the model alone (the trainer does not take it), a detector
+    checkpoint's backbone.* / proposal_generator.* (or the seeded synthetic ones), and box_proposals per test set"""
+    from cddmsl_amd import evaluation, synthetic
+    from cddmsl_amd.checkpoint import DetectionCheckpointer
+    from cddmsl_amd.modeling import build_model
+    model = build_model(cfg)
+    if not cfg.MODEL.WEIGHTS:
+        own = model.state_dict()
+        model.load_state_dict({k: v for k, v in synthetic.make_state_dict(0, num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES).items() if k in own},
+                              strict=False)
+    else:
+        inc = DetectionCheckpointer(model, cfg.OUTPUT_DIR).load(cfg.MODEL.WEIGHTS)
+        if rank == 0:
+            print(f"checkpoint: {len(inc.missing_keys)} missing, {len(inc.unexpected_keys)} unexpected, {len(inc.incorrect_shapes)} shape-skipped")
+    if args.datasets_root and not args.voc_root:
+        return evaluation.run_eval_only_catalog(model, cfg, args.datasets_root, rank, world)
+    assert args.voc_root, "--eval-only needs --voc-root (a VOC devkit year directory) or --datasets-root: datasets are not shipped"
+    return evaluation.run_eval_only(model, cfg, args, rank, world)
+
+
 def main(args):
     import torch
     from cddmsl_amd import cityscapes, engine, synthetic, voc_catalog
@@ -86,6 +109,8 @@ def main(args):
     cfg.MODEL.DEVICE = f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}"
     torch.cuda.set_device(cfg.MODEL.DEVICE)
     per_rank = max(cfg.SOLVER.IMS_PER_BATCH // world, 1)       # data/build.py:287
+    if args.eval_only and cfg.MODEL.META_ARCHITECTURE == "ProposalNetwork":
+        raise SystemExit(eval_proposal_network(cfg, args, rank, world))
     tr = engine.build_trainer(cfg, per_rank, args.height, args.width, seed=cfg.SEED)
     from cddmsl_amd.checkpoint import DetectionCheckpointer
     ckpt = DetectionCheckpointer(tr.model, cfg.OUTPUT_DIR, optimizer=tr.optimizer, trainer=tr)
