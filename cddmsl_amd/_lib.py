@@ -14,12 +14,8 @@ import torch  # noqa: F401  (must be imported first: it loads the HIP runtime th
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcddmsl_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_hip.h")
-# the proposal-recall cover walk: a library and a header of its own, bound the same way
-PROPOSAL_RECALL_LIB_PATH = os.path.join(_HERE, "libcddmsl_proposal_recall.so")
-PROPOSAL_RECALL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_proposal_recall.h")
 
 _lib = None
-_lib_proposal_recall = None
 
 
 class HipLibraryError(RuntimeError):
@@ -78,39 +74,26 @@ def header_struct(header_text, name):
     return fields
 
 
-def _load(lib_path, header_path):
-    """Load a library and type every entry point from its header.  Raises if the library is not built or lacks a function the
-    header declares; exports the header does not declare are left untyped."""
-    if not os.path.exists(lib_path):
-        raise HipLibraryError(
-            f"{lib_path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  cddmsl_amd has no fallback path."
-        )
-    L = ctypes.CDLL(lib_path)
-    with open(header_path) as f:
-        sigs = header_signatures(f.read())
-    for name, argtypes in sigs.items():
-        fn = getattr(L, name, None)
-        if fn is None:
-            raise HipLibraryError(f"{lib_path} is stale: it does not export {name}, which include/{os.path.basename(header_path)} declares; rebuild it")
-        fn.restype, fn.argtypes = ctypes.c_int, argtypes
-    return L
-
-
 def lib():
-    """Return the loaded library, loading it on first use, every entry point typed from include/cddmsl_hip.h."""
+    """Return the loaded library, loading it on first use, every entry point typed from include/cddmsl_hip.h.  Raises if the
+    library is not built or lacks a function the header declares; exports the header does not declare are left untyped."""
     global _lib
     if _lib is None:
-        _lib = _load(LIB_PATH, HEADER_PATH)
+        if not os.path.exists(LIB_PATH):
+            raise HipLibraryError(
+                f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(hipcc --offload-arch=gfx950).  cddmsl_amd has no fallback path."
+            )
+        L = ctypes.CDLL(LIB_PATH)
+        with open(HEADER_PATH) as f:
+            sigs = header_signatures(f.read())
+        for name, argtypes in sigs.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                raise HipLibraryError(f"{LIB_PATH} is stale: it does not export {name}, which include/cddmsl_hip.h declares; rebuild it")
+            fn.restype, fn.argtypes = ctypes.c_int, argtypes
+        _lib = L
     return _lib
-
-
-def lib_proposal_recall():
-    """libcddmsl_proposal_recall.so (csrc/proposal_recall.hip), typed from include/cddmsl_proposal_recall.h; loaded on first use."""
-    global _lib_proposal_recall
-    if _lib_proposal_recall is None:
-        _lib_proposal_recall = _load(PROPOSAL_RECALL_LIB_PATH, PROPOSAL_RECALL_HEADER_PATH)
-    return _lib_proposal_recall
 
 
 def stream_ptr():

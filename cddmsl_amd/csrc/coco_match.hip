@@ -19,23 +19,13 @@
 // detections.  An (image, class) beyond a cap sets over[b] = 1 and writes nothing: the caller matches that image on the host, it
 // is never truncated.  rank is pre-set to -1 and the masks to 0, so a detection no wave owns (class outside [0, K)) is dropped.
 #include "common.h"
+#include "box_iou.h"
 
 namespace {
 
 constexpr int CM_MAXD = 1024;     // detections of one class in one image
 constexpr int CM_MAXG = 256;      // ground-truth boxes of one class in one image
 constexpr int CM_KEEP = 128;      // kept detections per (image, class): max_dets <= CM_KEEP
-
-// np.minimum / np.maximum on doubles: the first operand unless the second is strictly beyond it (a NaN first operand stays)
-__device__ __forceinline__ double np_min(double a, double b) { return (a <= b || a != a) ? a : b; }
-__device__ __forceinline__ double np_max(double a, double b) { return (a >= b || a != a) ? a : b; }
-
-// argsort(-score, kind="mergesort"): q comes before p
-__device__ __forceinline__ bool cm_before(float sq, int q, float sp, int p) {
-  const bool nq = sq != sq, np = sp != sp;
-  if (nq || np) return (!nq && np) || (nq && np && q < p);
-  return sq > sp || (sq == sp && q < p);
-}
 
 __global__ __launch_bounds__(64) void k_coco_match(const float* __restrict__ dt_boxes, const float* __restrict__ dt_scores,
                                                    const long long* __restrict__ dt_cls, const long long* __restrict__ dt_off,
@@ -111,7 +101,7 @@ __global__ __launch_bounds__(64) void k_coco_match(const float* __restrict__ dt_
   for (int p = lane; p < Dk; p += 64) {
     const float sp = s_score[p];
     int r = 0;
-    for (int q = 0; q < Dk; ++q) r += cm_before(s_score[q], q, sp, p) ? 1 : 0;
+    for (int q = 0; q < Dk; ++q) r += score_before(s_score[q], q, sp, p) ? 1 : 0;
     const bool kept = r < max_dets;
     if (kept) s_kd[r] = p;
     rank[d0 + s_didx[p]] = kept ? r : -1;

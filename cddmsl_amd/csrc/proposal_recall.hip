@@ -21,7 +21,6 @@
 // inconsistent offsets, sets over[b] = 1 and writes nothing else: the caller walks that image on the host, it is never truncated.
 #include "common.h"
 #include "box_iou.h"
-#include "cddmsl_proposal_recall.h"   // the compiler checks the entry point's definition against its declaration
 
 namespace {
 
@@ -32,13 +31,6 @@ constexpr int PR_MAXA = 8;        // area ranges per launch (one bit each in gt_
 constexpr int PR_THREADS = 256;
 constexpr int PR_WAVES = PR_THREADS / 64;
 constexpr float PR_RETIRED = -2.f;   // s_best of a box that has been picked (an IoU is >= 0, a column without proposals -1)
-
-// logits.sort(descending=True), made stable: q comes before p
-__device__ __forceinline__ bool pr_before(float sq, int q, float sp, int p) {
-  const bool nq = sq != sq, np = sp != sp;
-  if (nq || np) return (!nq && np) || (nq && np && q < p);
-  return sq > sp || (sq == sp && q < p);
-}
 
 // one wave: box j against the unused proposals of ranks [0, Pk) -> (best IoU, its lowest rank) in s_best[j] / s_bestr[j]
 __device__ __forceinline__ void pr_column(int j, int lane, int Pk, const f32x4* s_pb, const f32x4* s_gb, const unsigned int* s_used,
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(PR_THREADS) void k_proposal_cover(
   for (int p = tid; p < P; p += PR_THREADS) {
     const float sp = s_scratch[p];
     int r = 0;
-    for (int q = 0; q < P; ++q) r += pr_before(s_scratch[q], q, sp, p) ? 1 : 0;
+    for (int q = 0; q < P; ++q) r += score_before(s_scratch[q], q, sp, p) ? 1 : 0;
     if (r < Pk) s_pb[r] = ((const f32x4*)boxes)[p0 + p];
   }
   __syncthreads();                                // the logits are dead: s_scratch becomes the per-box arrays

@@ -20,12 +20,9 @@
 // There is NO cap on boxes or detections per segment.  No atomics: tp / fp of a detection, the claimed bits of a ground-truth row and
 // bad[s] each have one writer (lane 0 of the segment's wave, provided perm lists a detection once and seg_gt a row once).
 #include "common.h"
+#include "box_iou.h"
 
 namespace {
-
-// np.minimum / np.maximum on doubles: the first operand unless the second is strictly beyond it (a NaN first operand stays)
-__device__ __forceinline__ double np_min(double a, double b) { return (a <= b || a != a) ? a : b; }
-__device__ __forceinline__ double np_max(double a, double b) { return (a >= b || a != a) ? a : b; }
 
 // np.argmax's order: does (v, box g) stand before (b, box a)?  A negative index is "nothing yet".
 __device__ __forceinline__ bool vm_before(double v, int g, double b, int a) {

@@ -22,6 +22,32 @@ from collections import OrderedDict, defaultdict
 import numpy as np
 import torch
 
+def gather_to_rank0(part):
+    """The evaluators' one gather: without a process group (or with one rank) ``[part]``; else rank 0 gets every rank's part in rank
+    order and the other ranks None.  Each caller merges the list in its own way."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return [part]
+    parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+    dist.gather_object(part, parts, dst=0)
+    return parts
+
+
+def merge_by_key(parts):
+    """the ranks' dictionaries (keyed by image) -> one, a later rank's entry replacing an earlier rank's; None stays None"""
+    if parts is None:
+        return None
+    merged = {}
+    for part in parts:
+        merged.update(part)
+    return merged
+
+
+def matching_device(device):
+    """the evaluators' ``device`` argument -> a non-CPU ``torch.device`` (the matching runs there), or None (it runs on the host)"""
+    return torch.device(device) if device is not None and torch.device(device).type != "cpu" else None
+
+
 VOC_CLASS_NAMES = ("aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog",
                    "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")   # datasets/pascal_voc.py:19-24
 
@@ -161,7 +187,7 @@ class PascalVOCDetectionEvaluator:
         self.class_names = list(class_names)
         self.target_classnames = list(target_classnames) if target_classnames is not None else list(class_names)
         self.is_2007 = year == 2007
-        self.device = torch.device(device) if device is not None and torch.device(device).type != "cpu" else None
+        self.device = matching_device(device)
         self._gt, self._gt_dev = None, None
         self.reset()
 
@@ -217,15 +243,8 @@ class PascalVOCDetectionEvaluator:
                 tab[:, 5].astype(np.int64), img)
 
     def _gathered_records(self):
-        import torch.distributed as dist
-        rec = self._device_records()
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-            return rec
-        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
-        dist.gather_object(rec, parts, dst=0)
-        if dist.get_rank() != 0:
-            return None
-        return merge_voc_records(parts)
+        parts = gather_to_rank0(self._device_records())
+        return None if parts is None else merge_voc_records(parts)
 
     def _match_device(self, rec, class_ids):
         """rank 0: one upload, ONE launch for all classes and thresholds, one readback -> {class: (tp bits, fp bits) in rank order}"""
@@ -261,12 +280,8 @@ class PascalVOCDetectionEvaluator:
                                              float(f"{x1:.1f}"), float(f"{y1:.1f}")))
 
     def _gathered(self):
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-            return self._predictions
-        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
-        dist.gather_object(dict(self._predictions), parts, dst=0)
-        if dist.get_rank() != 0:
+        parts = gather_to_rank0(dict(self._predictions))
+        if parts is None:
             return None
         merged = defaultdict(list)
         for part in parts:
@@ -579,7 +594,7 @@ class COCODetectionEvaluator:
 
     def __init__(self, dataset_dicts, class_names, device=None):
         self.class_names = list(class_names)
-        self.device = torch.device(device) if device is not None and torch.device(device).type != "cpu" else None
+        self.device = matching_device(device)
         self._gt = {}
         for d in dataset_dicts:
             anns = d.get("annotations", [])
@@ -663,13 +678,8 @@ class COCODetectionEvaluator:
         return rec, int(live.sum())
 
     def _gathered_records(self):
-        import torch.distributed as dist
-        rec, n = self._device_records()
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-            return merge_coco_records([rec]), n
-        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
-        dist.gather_object((rec, n), parts, dst=0)
-        if dist.get_rank() != 0:
+        parts = gather_to_rank0(self._device_records())
+        if parts is None:
             return None, 0
         return merge_coco_records([p[0] for p in parts]), sum(p[1] for p in parts)
 
@@ -684,17 +694,7 @@ class COCODetectionEvaluator:
                                                        inst.pred_classes.detach().cpu().numpy().astype(np.int64))
 
     def _gathered(self):
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-            return self._predictions
-        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
-        dist.gather_object(self._predictions, parts, dst=0)
-        if dist.get_rank() != 0:
-            return None
-        merged = {}
-        for part in parts:
-            merged.update(part)
-        return merged
+        return merge_by_key(gather_to_rank0(self._predictions))
 
     def evaluate(self):
         if self.device is not None:
@@ -846,7 +846,7 @@ class ProposalRecallEvaluator:
         self.limits = tuple(limits)
         self.num_ranges = len(PROPOSAL_REPORTED)
         assert [n for n, _ in PROPOSAL_REPORTED] == list(PROPOSAL_AREA_NAMES[: self.num_ranges])
-        self.device = torch.device(device) if device is not None and torch.device(device).type != "cpu" else None
+        self.device = matching_device(device)
         self._gt = proposal_ground_truth(dataset_dicts)
         self._index = {k: i for i, k in enumerate(self._gt)}          # image id -> data-set index
         self._gt_list = list(self._gt.values())
@@ -922,18 +922,7 @@ class ProposalRecallEvaluator:
                                                  prop.objectness_logits.detach().float().cpu().numpy(), gb, gr, self.limits, self.num_ranges)
 
     def _gathered(self):
-        import torch.distributed as dist
-        rec = self._device_records() if self.device is not None else self._cover
-        if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
-            return rec
-        parts = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
-        dist.gather_object(rec, parts, dst=0)
-        if dist.get_rank() != 0:
-            return None
-        merged = {}
-        for part in parts:
-            merged.update(part)
-        return merged
+        return merge_by_key(gather_to_rank0(self._device_records() if self.device is not None else self._cover))
 
     def stats(self, rec):
         """{(limit index, range index): ``proposal_recall_stats``} over the images of ``rec`` in data-set order"""

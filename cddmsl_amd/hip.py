@@ -8,9 +8,10 @@ import math
 import os
 from ctypes import c_float, c_int, c_long, c_void_p
 
+import numpy as np
 import torch
 
-from ._lib import check, lib, lib_proposal_recall, ptr, require_cuda, stream_ptr
+from ._lib import check, lib, ptr, require_cuda, stream_ptr, to_device_async
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
@@ -535,7 +536,6 @@ def tta_views(image_u8, sizes, flip, mean, std, dtype, batch_size=3, div255=True
         off += 2 * outsize + outsize * ks
     tab = None
     if parts:
-        from ._lib import to_device_async
         tab = to_device_async(torch.from_numpy(np.concatenate(parts)), image_u8.device)
 
     def axis(insize, outsize):
@@ -1191,6 +1191,21 @@ COCO_MATCH_MAX_GT = 256              # ground-truth boxes of one class in one im
 COCO_MATCH_MAX_KEPT = 128            # kept detections per (image, class): the ``max_dets`` argument
 
 
+def _upload(array, device):
+    return to_device_async(torch.from_numpy(np.ascontiguousarray(array)), device)
+
+
+def _pack_ground_truth(items, fields, device):
+    """What the three ground-truth classes' ``from_host`` share.  ``items``: one tuple of numpy arrays per image (or row), ``fields``: a
+    ``(dtype, trailing shape)`` per tuple member -> the members concatenated over the items ([G, *trailing], contiguous, zero rows
+    for an empty list) followed by ``off`` int64 [len(items) + 1], the running sum of the items' lengths; all uploaded without a
+    synchronisation."""
+    cols = [[np.asarray(it[k], dtype=dt).reshape(-1, *tail) for it in items] for k, (dt, tail) in enumerate(fields)]
+    arrays = [np.concatenate(col) if col else np.zeros((0, *tail), dtype=dt) for col, (dt, tail) in zip(cols, fields)]
+    off = np.concatenate([[0], np.cumsum([len(a) for a in cols[0]])]).astype(np.int64)
+    return [_upload(a, device) for a in arrays + [off]]
+
+
 class CocoGroundTruth:
     """A data set's ground truth on the device, as cddmsl_coco_match reads it: ``xywh`` f64 [G, 4], ``area`` f64 [G], ``crowd`` u8 [G],
     ``cls`` int64 [G] concatenated over the images, ``off`` int64 [n_images + 1]; plus the walk's constants ``thrs`` f64 [T] and
@@ -1209,14 +1224,8 @@ class CocoGroundTruth:
     @classmethod
     def from_host(cls, per_image, thrs, rngs, device):
         """``per_image``: [(xywh [g,4], area [g], crowd [g] bool, class [g])] numpy, in data-set order"""
-        import numpy as np
-        from ._lib import to_device_async
-        cat = lambda i, dt, shape: np.concatenate([np.asarray(p[i], dtype=dt).reshape(shape) for p in per_image] or [np.zeros(shape, dtype=dt)])
-        off = np.zeros(len(per_image) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(p[1]) for p in per_image])
-        up = lambda a: to_device_async(torch.from_numpy(np.ascontiguousarray(a)), device)
-        return cls(up(cat(0, np.float64, (-1, 4))), up(cat(1, np.float64, (-1,))), up(cat(2, np.uint8, (-1,))), up(cat(3, np.int64, (-1,))),
-                   up(off), up(np.asarray(thrs, dtype=np.float64)), up(np.asarray(rngs, dtype=np.float64).reshape(-1, 2)))
+        packed = _pack_ground_truth(per_image, [(np.float64, (4,)), (np.float64, ()), (np.uint8, ()), (np.int64, ())], device)
+        return cls(*packed, _upload(np.asarray(thrs, dtype=np.float64), device), _upload(np.asarray(rngs, dtype=np.float64).reshape(-1, 2), device))
 
 
 @_timed("coco_match")
@@ -1247,7 +1256,7 @@ def coco_match(dt_boxes, dt_scores, dt_cls, dt_off, img_idx, gt, num_classes, ma
     return rank, matched, ignored, over
 
 
-# cddmsl_proposal_cover (libcddmsl_proposal_recall.so, include/cddmsl_proposal_recall.h): what one image may hold; an image beyond a cap comes back flagged in ``over`` and is walked on the host
+# cddmsl_proposal_cover: what one image may hold; an image beyond a cap comes back flagged in ``over`` and is walked on the host
 PROPOSAL_COVER_MAX_PROPOSALS = 2048  # proposals of one image (the RPN's post-NMS top-k is 2000 in training, 1000 at test time)
 PROPOSAL_COVER_MAX_GT = 512          # ground-truth boxes of one image
 PROPOSAL_COVER_MAX_LIMITS = 4        # proposal limits per launch
@@ -1276,16 +1285,9 @@ class ProposalGroundTruth:
     @classmethod
     def from_host(cls, per_image, limits, num_ranges, device):
         """``per_image``: [(boxes [g, 4] f32 XYXY, rng [g] u8)] numpy, in data-set order; ``limits``: ints, None = no limit"""
-        import numpy as np
-        from ._lib import to_device_async
-        boxes = np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 4) for b, _ in per_image] or [np.zeros((0, 4), dtype=np.float32)])
-        rng = np.concatenate([np.asarray(r, dtype=np.uint8).reshape(-1) for _, r in per_image] or [np.zeros(0, dtype=np.uint8)])
-        off = np.zeros(len(per_image) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(r) for _, r in per_image])
         lim = np.asarray([PROPOSAL_COVER_MAX_PROPOSALS if l is None else min(max(int(l), 0), PROPOSAL_COVER_MAX_PROPOSALS) for l in limits],
                          dtype=np.int32)
-        up = lambda a: to_device_async(torch.from_numpy(np.ascontiguousarray(a)), device)
-        return cls(up(boxes), up(rng), up(off), up(lim), num_ranges)
+        return cls(*_pack_ground_truth(per_image, [(np.float32, (4,)), (np.uint8, ())], device), _upload(lim, device), num_ranges)
 
 
 @_timed("proposal_cover")
@@ -1308,7 +1310,7 @@ def proposal_cover(boxes, logits, off, img_idx, cover_off, num_slots, gt):
     L, A = gt.limits.numel(), gt.num_ranges
     cover = torch.empty((L, A, int(num_slots)), device=dev, dtype=torch.float32)
     over = torch.empty(B, device=dev, dtype=torch.int32)
-    check(lib_proposal_recall().cddmsl_proposal_cover(ptr(boxes), ptr(logits), ptr(off), ptr(img_idx), B, P, ptr(gt.boxes), ptr(gt.rng), ptr(gt.off),
+    check(_L().cddmsl_proposal_cover(ptr(boxes), ptr(logits), ptr(off), ptr(img_idx), B, P, ptr(gt.boxes), ptr(gt.rng), ptr(gt.off),
                                      gt.n_images, gt.n_boxes, ptr(gt.limits), L, A, ptr(cover_off), int(num_slots), ptr(cover), ptr(over),
                                      stream_ptr()), "cddmsl_proposal_cover")
     return cover, over
@@ -1335,14 +1337,8 @@ class VocGroundTruth:
     @classmethod
     def from_host(cls, rows, thrs, device):
         """``rows``: [(bbox [g, 4], difficult [g])] numpy, one per (class, image) in row order"""
-        import numpy as np
-        from ._lib import to_device_async
-        boxes = np.concatenate([np.asarray(b, dtype=np.float64).reshape(-1, 4) for b, _ in rows] or [np.zeros((0, 4))])
-        diff = np.concatenate([np.asarray(d).astype(np.uint8).reshape(-1) for _, d in rows] or [np.zeros(0, dtype=np.uint8)])
-        off = np.zeros(len(rows) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(d) for _, d in rows])
-        up = lambda a: to_device_async(torch.from_numpy(np.ascontiguousarray(a)), device)
-        return cls(up(boxes), up(diff), up(off), up(np.asarray(thrs, dtype=np.float64)))
+        rows = [(b, np.asarray(d).astype(np.uint8)) for b, d in rows]          # (difficult is a bool array)
+        return cls(*_pack_ground_truth(rows, [(np.float64, (4,)), (np.uint8, ())], device), _upload(np.asarray(thrs, dtype=np.float64), device))
 
 
 @_timed("voc_match")
@@ -1495,7 +1491,6 @@ def iou_match_batched(gt_list, preds, pred_counts, thresholds, labels, allow_low
     """Fused pairwise_iou + Matcher for ALL images in one launch pair.  ``gt_list``: per-image [G_i, 4] f32 tensors;
     ``preds``: [P, 4] shared by every image (``pred_counts`` None; returns [N, P] tensors) or the images' predictions
     concatenated [sum P_i, 4] with ``pred_counts`` = [P_i] (returns [sum P_i] tensors)."""
-    from ._lib import to_device_async
     require_cuda(preds, *gt_list)
     dev = preds.device
     N = len(gt_list)

@@ -37,7 +37,7 @@ def _header_declarations():
     """{name: parameter count} read off the header independently of the package's parser: commas of the parameter list + 1."""
     hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "cddmsl_hip.h")).read(), flags=re.S)
     decls = {n: (0 if p.strip() == "void" else p.count(",") + 1) for n, p in re.findall(r"\bint\s+(cddmsl_\w+)\s*\(([^)]*)\)\s*;", hdr)}
-    assert len(decls) == len(re.findall(r"\bcddmsl_\w+\s*\(", hdr)) == 109
+    assert len(decls) == len(re.findall(r"\bcddmsl_\w+\s*\(", hdr)) == 110
     return decls
 
 
@@ -60,6 +60,7 @@ def test_signature_anchors(lib):
     assert lib.cddmsl_weight_prep_multi.argtypes == [vp, ci, ci, vp]                                     # const long long*
     assert lib.cddmsl_set_workspace.argtypes == [vp, cl]
     assert lib.cddmsl_rpn_compact_rows.argtypes == [vp] * 4 + [cl, ci, vp]
+    assert lib.cddmsl_proposal_cover.argtypes == [vp] * 4 + [ci, cl, vp, vp, vp, cl, cl, vp, ci, ci, vp, cl, vp, vp, vp]
 
 
 def test_header_parser_rejects_what_it_does_not_know():

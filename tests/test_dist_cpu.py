@@ -243,6 +243,78 @@ def test_eval_only_two_ranks_equals_one_rank(tmp_path):
     assert any(v == v and v > 0 for v in one.values()), one
 
 
+# The COCO and the proposal-recall evaluators' host paths over the same gather (evaluation.gather_to_rank0): 6 images with 0..3 boxes
+# (one of them a crowd box), one image whose input holds no detection and no proposal, one input of an image outside the set, and
+# image 2 once more as the last input with other boxes (the later input replaces the earlier: rank order decides across ranks)
+_COCO_CLASSES = ("a", "b", "c")
+
+
+def _coco_set():
+    """-> (dataset dicts, inputs, outputs), generated; the same in every process"""
+    from cddmsl_amd.structures import Boxes, Instances
+    rng = np.random.default_rng(5)
+    dicts = []
+    for i, n in enumerate((2, 0, 3, 1, 3, 2)):
+        xy = rng.uniform(0, 120, size=(n, 2))
+        wh = rng.uniform(10, 120, size=(n, 2))            # areas on both sides of 32^2 and 96^2
+        anns = [{"bbox": [float(v) for v in (*xy[k], *(xy[k] + wh[k]))], "category_id": int((i + k) % 3), "iscrowd": int(i == 4 and k == 1)}
+                for k in range(n)]
+        dicts.append({"image_id": str(i), "height": 256, "width": 256, "annotations": anns})
+
+    def output(d, seed, empty=False):
+        r = np.random.default_rng(seed)
+        gt = np.array([a["bbox"] for a in d["annotations"]], dtype=np.float64).reshape(-1, 4)
+        boxes = np.concatenate([gt + r.uniform(-6, 6, size=gt.shape), [[5.0, 5.0, 60.0, 70.0], [100.0, 90.0, 200.0, 220.0]]])
+        cls = np.array([a["category_id"] for a in d["annotations"]] + [0, 2], dtype=np.int64)
+        keep = slice(0, 0) if empty else slice(None)
+        boxes, cls = torch.from_numpy(boxes[keep]).float(), torch.from_numpy(cls[keep])
+        scores = torch.from_numpy(r.uniform(0.05, 1.0, size=len(cls))).float()
+        return {"instances": Instances((256, 256), pred_boxes=Boxes(boxes), scores=scores, pred_classes=cls),
+                "proposals": Instances((256, 256), proposal_boxes=Boxes(boxes.clone()), objectness_logits=scores * 4 - 2)}
+
+    order = [dicts[i] for i in range(6)] + [dict(dicts[0], image_id="99"), dicts[2]]
+    inputs = [{"image_id": d["image_id"]} for d in order]
+    outputs = [output(d, 100 + j, empty=(j == 3)) for j, d in enumerate(order)]
+    return dicts, inputs, outputs
+
+
+def _coco_eval_worker(rank, world, port, ret):
+    if world > 1:
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from cddmsl_amd import evaluation
+        dicts, inputs, outputs = _coco_set()
+        evs = [evaluation.COCODetectionEvaluator(dicts, _COCO_CLASSES, device=None), evaluation.ProposalRecallEvaluator(dicts, device=None)]
+        for i in range(rank, len(inputs), world):
+            for ev in evs:
+                ev.process([inputs[i]], [outputs[i]])
+        res = [ev.evaluate() for ev in evs]
+        if rank == 0:
+            ret["w%d" % world] = {**res[0]["bbox"], **res[1]["box_proposals"]}
+        else:
+            ret["other"] = res
+    finally:
+        if world > 1:
+            dist.destroy_process_group()
+
+
+def test_coco_and_proposal_eval_two_ranks_equal_one_rank():
+    dicts, inputs, outputs = _coco_set()
+    assert sorted(len(d["annotations"]) for d in dicts) == [0, 1, 2, 2, 3, 3] and sum(a["iscrowd"] for d in dicts for a in d["annotations"]) == 1
+    assert [x["image_id"] for x in inputs] == ["0", "1", "2", "3", "4", "5", "99", "2"] and len(outputs[3]["instances"].scores) == 0
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    _coco_eval_worker(0, 1, 0, ret)
+    mp.spawn(_coco_eval_worker, args=(2, _free_port(), ret), nprocs=2, join=True)
+    one, two = ret["w1"], ret["w2"]
+    assert list(one) == list(two) and {"AP", "AP50", "AP-a", "AR@100", "ARs@1000"} <= set(one)
+    for k in one:
+        assert (one[k] != one[k] and two[k] != two[k]) or one[k] == two[k], (k, one[k], two[k])
+    assert one["AP"] == one["AP"] and one["AP"] > 0 and one["AR@100"] == one["AR@100"] and one["AR@100"] > 0, one
+    assert ret["other"] == [None, None]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # gradient all-reduce overlapped with backward (engine/defaults.py:72-74: the DDP reducer fires a bucket when its last gradient
 # is ready): same averaged gradients as the plain post-backward reduction, buckets on the wire before backward has finished

@@ -123,7 +123,7 @@ def test_caps_hand_back_exactly_the_image_beyond_them():
     over = torch.full((len(images),), -77, device=DEV, dtype=torch.int32)
     gt = _gt_dev(images, limits, A)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
-    st = hip.lib_proposal_recall().cddmsl_proposal_cover(p(boxes), p(logits), p(off), p(idx), len(images), logits.numel(), p(gt.boxes), p(gt.rng), p(gt.off), gt.n_images,
+    st = hip.lib().cddmsl_proposal_cover(p(boxes), p(logits), p(off), p(idx), len(images), logits.numel(), p(gt.boxes), p(gt.rng), p(gt.off), gt.n_images,
                                         gt.n_boxes, p(gt.limits), len(limits), A, p(coff), n, p(cover), p(over), hip.stream_ptr())
     torch.cuda.synchronize()
     assert st == 0 and over.tolist() == [0, 1, 0, 0, 1, 0]
@@ -157,7 +157,7 @@ def test_every_slot_is_written_and_nothing_beyond():
     over = torch.full((len(batch) + TAIL,), -77, device=DEV, dtype=torch.int32)
     gt = _gt_dev(images, C.LIMITS, A)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
-    st = hip.lib_proposal_recall().cddmsl_proposal_cover(p(boxes), p(logits), p(off), p(idx), len(batch), logits.numel(), p(gt.boxes), p(gt.rng), p(gt.off), gt.n_images,
+    st = hip.lib().cddmsl_proposal_cover(p(boxes), p(logits), p(off), p(idx), len(batch), logits.numel(), p(gt.boxes), p(gt.rng), p(gt.off), gt.n_images,
                                         gt.n_boxes, p(gt.limits), L, A, p(coff), n, p(buf), p(over), hip.stream_ptr())
     torch.cuda.synchronize()
     assert st == 0 and over[: len(batch)].tolist() == [0] * len(batch)
@@ -197,7 +197,7 @@ def test_cabi_checks_its_arguments_and_writes_nothing_when_it_refuses():
 
     def call(**kw):
         a = dict(base, **kw)
-        return hip.lib_proposal_recall().cddmsl_proposal_cover(a["boxes"], p(logits), a["off"], p(idx), a["B"], a["P"], p(gt.boxes), p(gt.rng), p(gt.off), a["NI"], a["G"],
+        return hip.lib().cddmsl_proposal_cover(a["boxes"], p(logits), a["off"], p(idx), a["B"], a["P"], p(gt.boxes), p(gt.rng), p(gt.off), a["NI"], a["G"],
                                               p(gt.limits), a["L"], a["A"], p(coff), a["Gb"], a["cover"], a["over"], hip.stream_ptr())
     bad = [dict(L=0), dict(L=hip.PROPOSAL_COVER_MAX_LIMITS + 1), dict(A=0), dict(A=hip.PROPOSAL_COVER_MAX_RANGES + 1), dict(B=-1), dict(P=-1),
            dict(G=-1), dict(NI=-1), dict(Gb=-1), dict(boxes=ctypes.c_void_p(boxes.data_ptr() + 4)), dict(off=None), dict(over=None),
@@ -217,6 +217,39 @@ def test_cabi_checks_its_arguments_and_writes_nothing_when_it_refuses():
         hip.ProposalGroundTruth.from_host([(g, r) for g, r, _, _ in images], (1, 2, 3, 4, 5), 8, DEV)
     with pytest.raises(HipLibraryError):
         hip.proposal_cover(boxes.cpu(), logits.cpu(), off.cpu(), idx.cpu(), coff.cpu(), n, gt)
+
+
+@pytest.mark.parametrize("kind", ["coco", "proposal", "voc"])
+@pytest.mark.parametrize("n_items", [0, 2])
+def test_ground_truth_from_host_packs_empty_and_boxless_items(kind, n_items):
+    """the three ground-truth classes' ``from_host`` on no item at all and on two items of which the first has no box: dtype, shape and
+    values of every tensor against the numpy built here, ``off``, the image / row count and the box count"""
+    from cddmsl_amd import hip
+    b64 = np.array([[1.0, 2.0, 30.5, 40.25], [5.0, 6.0, 7.0, 8.0], [0.0, 0.0, 100.0, 50.0]])
+    three = {"coco": (b64, np.array([10.0, 2.5, 5000.0]), np.array([False, True, False]), np.array([2, 0, 1], dtype=np.int64)),
+             "proposal": (b64.astype(np.float32), np.array([1, 0, 9], dtype=np.uint8)),
+             "voc": (b64, np.array([False, True, False]))}[kind]
+    items = [tuple(f[:0] for f in three), three][:n_items]
+    G, off = 3 * (n_items // 2), [0, 0, 3][: n_items + 1]
+    if kind == "coco":
+        gt = hip.CocoGroundTruth.from_host(items, [0.5, 0.75], [(0.0, 1e10), (0.0, 1024.0)], DEV)
+        got = [gt.xywh, gt.area, gt.crowd, gt.cls]
+        want = [(torch.float64, (G, 4)), (torch.float64, (G,)), (torch.uint8, (G,)), (torch.int64, (G,))]
+        assert gt.n_images == n_items and gt.thrs.cpu().tolist() == [0.5, 0.75] and gt.rngs.cpu().tolist() == [[0.0, 1e10], [0.0, 1024.0]]
+        assert gt.thrs.dtype == gt.rngs.dtype == torch.float64
+    elif kind == "proposal":
+        gt = hip.ProposalGroundTruth.from_host(items, (100, None, 5000, -3), 4, DEV)
+        got, want = [gt.boxes, gt.rng], [(torch.float32, (G, 4)), (torch.uint8, (G,))]
+        assert gt.n_images == n_items and gt.n_boxes == G and gt.num_ranges == 4
+        assert gt.limits.dtype == torch.int32 and gt.limits.cpu().tolist() == [100, 2048, 2048, 0]       # None and beyond the cap: the cap
+    else:
+        gt = hip.VocGroundTruth.from_host(items, [0.5, 0.7], DEV)
+        got, want = [gt.boxes, gt.difficult], [(torch.float64, (G, 4)), (torch.uint8, (G,))]
+        assert gt.n_rows == n_items and gt.n_boxes == G and gt.thrs.dtype == torch.float64 and gt.thrs.cpu().tolist() == [0.5, 0.7]
+    assert gt.off.dtype == torch.int64 and gt.off.is_cuda and gt.off.cpu().tolist() == off
+    for t, (dtype, shape), field in zip(got, want, three):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape
+        assert np.array_equal(t.cpu().numpy(), field[:G].astype(t.cpu().numpy().dtype))
 
 
 # ------------------------------------------------------------------------------------------------ the evaluator

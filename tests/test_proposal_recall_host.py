@@ -225,21 +225,29 @@ def test_eval_only_reports_box_proposals_under_the_switch(tmp_path, capsys, monk
     assert list(tta) == ["bbox", "box_proposals", "bbox_TTA"]
 
 
-def test_side_library_exports_and_signature_follow_its_header():
-    """libcddmsl_proposal_recall.so exports exactly what include/cddmsl_proposal_recall.h declares, typed from that header"""
+def test_proposal_cover_lives_in_the_main_library():
+    """cddmsl_proposal_cover is declared in include/cddmsl_hip.h, exported by libcddmsl_hip.so and typed by _lib.lib() from that header,
+    as tests/test_cabi_host.py holds every entry point; no library, loader, header or build table beside them"""
     import ctypes
     import re
     import subprocess
     import __graft_entry__ as g
     g.build()
     from cddmsl_amd import _lib
-    L = _lib.lib_proposal_recall()
-    hdr = open(_lib.PROPOSAL_RECALL_HEADER_PATH).read()
-    names = sorted(set(re.findall(r"\bint\s+(cddmsl_\w+)\s*\(", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))))
-    assert names == ["cddmsl_proposal_cover"]
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.PROPOSAL_RECALL_LIB_PATH], text=True)
-    assert sorted(set(re.findall(r"\bT (cddmsl_\w+)", out))) == names
+    L = _lib.lib()
+    hdr = re.sub(r"/\*.*?\*/", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    assert re.findall(r"\bint\s+(cddmsl_proposal_\w+)\s*\(", hdr) == ["cddmsl_proposal_cover"]
+    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
+    assert "cddmsl_proposal_cover" in set(re.findall(r"\bT (cddmsl_\w+)", out))
     vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
     fn = L.cddmsl_proposal_cover
     assert fn.restype is ctypes.c_int and fn.argtypes == [vp] * 4 + [ci, cl, vp, vp, vp, cl, cl, vp, ci, ci, vp, cl, vp, vp, vp]
-    subprocess.check_call(["gcc", "-std=c99", "-fsyntax-only", "-x", "c", _lib.PROPOSAL_RECALL_HEADER_PATH])
+    assert not hasattr(_lib, "lib_proposal_recall") and not [n for n in dir(_lib) if n.startswith("PROPOSAL_RECALL_")]
+    assert not hasattr(g, "SIDE_LIBS")
+    assert not [f for _, _, files in os.walk(os.path.dirname(_lib.HEADER_PATH)) for f in files if f == "cddmsl_proposal_recall.h"]
+
+
+def test_gather_to_rank0_without_a_process_group_is_the_part_itself():
+    part = {"some": "records"}
+    got = E.gather_to_rank0(part)
+    assert isinstance(got, list) and len(got) == 1 and got[0] is part
