@@ -14,8 +14,12 @@ import torch  # noqa: F401  (must be imported first: it loads the HIP runtime th
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcddmsl_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_hip.h")
+# the weight averaging of MODEL_EMA: a library and a header of its own, bound the same way
+WEIGHT_AVERAGE_LIB_PATH = os.path.join(_HERE, "libcddmsl_weight_average.so")
+WEIGHT_AVERAGE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_weight_average.h")
 
 _lib = None
+_lib_weight_average = None
 
 
 class HipLibraryError(RuntimeError):
@@ -74,26 +78,39 @@ def header_struct(header_text, name):
     return fields
 
 
+def _load(lib_path, header_path):
+    """Load a library and type every entry point from its header.  Raises if the library is not built or lacks a function the
+    header declares; exports the header does not declare are left untyped."""
+    if not os.path.exists(lib_path):
+        raise HipLibraryError(
+            f"{lib_path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  cddmsl_amd has no fallback path."
+        )
+    L = ctypes.CDLL(lib_path)
+    with open(header_path) as f:
+        sigs = header_signatures(f.read())
+    for name, argtypes in sigs.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise HipLibraryError(f"{lib_path} is stale: it does not export {name}, which include/{os.path.basename(header_path)} declares; rebuild it")
+        fn.restype, fn.argtypes = ctypes.c_int, argtypes
+    return L
+
+
 def lib():
-    """Return the loaded library, loading it on first use, every entry point typed from include/cddmsl_hip.h.  Raises if the
-    library is not built or lacks a function the header declares; exports the header does not declare are left untyped."""
+    """Return the loaded library, loading it on first use, every entry point typed from include/cddmsl_hip.h."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise HipLibraryError(
-                f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(hipcc --offload-arch=gfx950).  cddmsl_amd has no fallback path."
-            )
-        L = ctypes.CDLL(LIB_PATH)
-        with open(HEADER_PATH) as f:
-            sigs = header_signatures(f.read())
-        for name, argtypes in sigs.items():
-            fn = getattr(L, name, None)
-            if fn is None:
-                raise HipLibraryError(f"{LIB_PATH} is stale: it does not export {name}, which include/cddmsl_hip.h declares; rebuild it")
-            fn.restype, fn.argtypes = ctypes.c_int, argtypes
-        _lib = L
+        _lib = _load(LIB_PATH, HEADER_PATH)
     return _lib
+
+
+def lib_weight_average():
+    """libcddmsl_weight_average.so (csrc/weight_average.hip), typed from include/cddmsl_weight_average.h; loaded on first use."""
+    global _lib_weight_average
+    if _lib_weight_average is None:
+        _lib_weight_average = _load(WEIGHT_AVERAGE_LIB_PATH, WEIGHT_AVERAGE_HEADER_PATH)
+    return _lib_weight_average
 
 
 def stream_ptr():

@@ -142,8 +142,10 @@ def offline_backbone_state(all_params: Dict[str, torch.Tensor]) -> Dict[str, tor
 
 
 class DetectionCheckpointer:
-    def __init__(self, model, save_dir="", optimizer=None, trainer=None):
+    def __init__(self, model, save_dir="", optimizer=None, trainer=None, weight_average=None):
+        """``weight_average``: a solver.WeightAverage (MODEL_EMA); saved as ``data["weight_average"]`` and restored from it"""
         self.model, self.save_dir, self.optimizer, self.trainer = model, save_dir, optimizer, trainer
+        self.weight_average = weight_average
 
     def load(self, path, bb_rpn_weights=False) -> Incompatible:
         """detection_checkpoint.py:62-132: ``OAI_CLIP`` in the file name (or ``bb_rpn_weights``) -> name conversion first"""
@@ -157,6 +159,14 @@ class DetectionCheckpointer:
             self.optimizer.load_state_dict(data["optimizer"])
         if self.trainer is not None and "iteration" in data:
             self.trainer.iter = int(data["iteration"]) + 1            # resume at the next iteration (defaults.py:411-413)
+        if self.weight_average is not None:
+            if "weight_average" in data:
+                self.weight_average.load_state_dict(data["weight_average"])
+            else:           # the average then starts at the first update after the load (a copy of the weights of that step)
+                import torch.distributed as dist
+                if not (dist.is_available() and dist.is_initialized() and dist.get_rank() != 0):
+                    print(f"checkpoint: {path} holds no averaged weights (no weight_average entry): the average starts at the "
+                          "first update after this load", flush=True)
         return inc
 
     def load_offline_backbone(self, path):
@@ -170,6 +180,8 @@ class DetectionCheckpointer:
             data["optimizer"] = self.optimizer.state_dict()
         if iteration is not None:
             data["iteration"] = int(iteration)
+        if self.weight_average is not None:
+            data["weight_average"] = self.weight_average.state_dict()
         path = os.path.join(self.save_dir, name + ".pth")
         torch.save(data, path)
         with open(os.path.join(self.save_dir, "last_checkpoint"), "w") as f:

@@ -159,6 +159,30 @@ def get_cfg():
                  "PROPOSAL_RECALL": False,
                  # test-time augmentation (defaults.py:718-721): multi-scale + flip views, merged by per-class NMS; results under *_TTA
                  "AUG": {"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000, "FLIP": True}},
+        # project-specific (block name and DECAY as D2Go's MODEL_EMA): an average of the trainable weights kept after every step on the
+        # GPU, MODE "ema" (avg += (1 - DECAY)(w - avg)) or "uniform" (running mean of the snapshots since START_ITER, SWA); saved with
+        # every checkpoint and evaluated next to the training weights under *_EMA keys: EVAL "plain" / "averaged" / "both"
+        "MODEL_EMA": {"ENABLED": False, "MODE": "ema", "DECAY": 0.999, "START_ITER": 0, "EVAL": "both"},
         "OUTPUT_DIR": "./output",
     })
     return C
+
+
+MODEL_EMA_MODES = ("ema", "uniform")
+MODEL_EMA_EVALS = ("plain", "averaged", "both")
+
+
+def check_model_ema(cfg):
+    """-> cfg.MODEL_EMA if it is enabled and valid, None if absent or disabled; ValueError naming the key otherwise"""
+    e = cfg.get("MODEL_EMA", None)
+    if e is None or not e.ENABLED:
+        return None
+    if e.MODE not in MODEL_EMA_MODES:
+        raise ValueError("MODEL_EMA.MODE {!r}: one of {}".format(e.MODE, MODEL_EMA_MODES))
+    if e.EVAL not in MODEL_EMA_EVALS:
+        raise ValueError("MODEL_EMA.EVAL {!r}: one of {}".format(e.EVAL, MODEL_EMA_EVALS))
+    if isinstance(e.DECAY, bool) or not isinstance(e.DECAY, (int, float)) or not 0.0 <= e.DECAY < 1.0:
+        raise ValueError("MODEL_EMA.DECAY {!r}: a number in [0, 1)".format(e.DECAY))
+    if isinstance(e.START_ITER, bool) or not isinstance(e.START_ITER, int) or e.START_ITER < 0:
+        raise ValueError("MODEL_EMA.START_ITER {!r}: an integer >= 0".format(e.START_ITER))
+    return e

@@ -14,7 +14,7 @@ import torch.distributed as dist
 
 from .modeling.clipcap import TransformerMapper
 from .hip import same_layout
-from .solver import build_optimizer
+from .solver import build_optimizer, build_weight_average
 
 
 def get_world_size():
@@ -229,6 +229,7 @@ class SimpleTrainer:
         self._data_loader_iter = iter(data_loader)
         self.optimizer = optimizer
         self.buckets = GradBuckets(optimizer.params)
+        self.weight_average = None      # MODEL_EMA: solver.WeightAverage (build_trainer), updated right after every optimizer step
         self.iter = 0
         self.burn_in = 10000            # train_loop.py:334
         self.metrics_period = metrics_period
@@ -280,6 +281,8 @@ class SimpleTrainer:
         self.buckets.all_reduce_mean()
         self.optimizer.iteration = self.iter
         self.optimizer.step()
+        if self.weight_average is not None:
+            self.weight_average.update(self.iter)
         if self.metrics_period and self.iter % self.metrics_period == 0:
             self._write_metrics(loss_dict, data_time)
         self.iter += 1
@@ -356,4 +359,6 @@ def build_trainer(cfg, per_rank_batch, height=800, width=1333, seed=1):
     model.region_generator.manual_seed(seed + rank + 104729)
     opt = build_optimizer(cfg, model)
     loader = SyntheticPairedLoader(per_rank_batch, height, width, rank, cfg.MODEL.DEVICE, cfg.MODEL.ROI_HEADS.NUM_CLASSES)
-    return SimpleTrainer(model, loader, opt, cfg)
+    tr = SimpleTrainer(model, loader, opt, cfg)
+    tr.weight_average = build_weight_average(cfg, model, opt)
+    return tr

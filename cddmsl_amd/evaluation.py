@@ -345,11 +345,24 @@ def inference_on_dataset(model, data_loader, evaluator):
     return evaluator.evaluate()
 
 
-def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False, prefix=""):
+def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False, prefix="", weight_average=None):
     """tools/train_caption_consistency.py:143-152 (``--eval-only``): VOC-style test set under ``args.voc_root`` -> AP dict
     printed by rank 0.  Every rank evaluates its shard of the test set (``world`` has to be the process group's size: the
     evaluator merges all ranks' detections, so unsharded ranks would count every detection ``world`` times).  Returns the
-    process exit code (or the result dict: rank 0, ``return_results``)."""
+    process exit code (or the result dict: rank 0, ``return_results``).  ``weight_average`` (MODEL_EMA): see ``averaged_passes``."""
+    res = None
+    for averaged, weights in averaged_passes(model, cfg, weight_average):
+        with weights:
+            part = _eval_only_pass(model, cfg, args, rank, world, prefix, averaged)
+        if part is not None:
+            res = part if res is None else res
+            res.update(part)
+    return res if return_results else 0
+
+
+def _eval_only_pass(model, cfg, args, rank, world, prefix, averaged):
+    """one pass of ``run_eval_only`` over the weights the model holds now; ``averaged``: its task keys carry ``_EMA``"""
+    mark = with_ema_suffix if averaged else (lambda r: r)
     import torch.distributed as dist
     ws = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     assert world == ws, f"run_eval_only: world={world} but the process group has {ws} ranks"
@@ -358,16 +371,16 @@ def run_eval_only(model, cfg, args, rank=0, world=1, return_results=False, prefi
     dicts = load_voc_instances(args.voc_root, args.voc_split, names)
     loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
     ev = PascalVOCDetectionEvaluator(args.voc_root, args.voc_split, args.voc_year, names)
-    res = inference_on_dataset(model, loader, with_proposal_recall(ev, model, cfg, dicts))
+    res = mark(inference_on_dataset(model, loader, with_proposal_recall(ev, model, cfg, dicts)))
     if rank == 0:
         _print_results(prefix, res)
     if tta_enabled(cfg) and not is_proposal_network(model):            # train_caption_consistency.py:105-118,149-150: the same set again through the TTA model
         loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
-        tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, ev))
+        tta = mark(with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, ev)))
         if rank == 0:
             print(prefix + str({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()}))
             res.update(tta)
-    return res if return_results else 0
+    return res
 
 
 def num_test_classes(model, cfg):
@@ -390,6 +403,26 @@ def tta_model(cfg, model):
 def with_tta_suffix(res):
     """train_caption_consistency.py:117: ``{k + "_TTA": v}`` over the top-level keys (``bbox_TTA``); None (not rank 0) stays empty"""
     return OrderedDict((k + "_TTA", v) for k, v in (res or {}).items())
+
+
+def with_ema_suffix(res):
+    """``{k + "_EMA": v}`` over the top-level keys, for the results of the averaged weights (``bbox_EMA``, ``bbox_TTA_EMA``,
+    ``box_proposals_EMA``; in the storage ``<dataset>/bbox_EMA/AP``); None (not rank 0) stays empty"""
+    return OrderedDict((k + "_EMA", v) for k, v in (res or {}).items())
+
+
+def averaged_passes(model, cfg, weight_average):
+    """The passes of one evaluation under ``MODEL_EMA``: [(averaged, context manager)].  The plain pass runs the weights the model
+    holds; the averaged one runs inside ``weight_average.applied(model)`` and reports under ``_EMA`` keys -- also when it is the only
+    pass (``EVAL "averaged"``), so that a key never means two things.  Without a WeightAverage that has been updated at least once
+    (feature off, ``EVAL "plain"``, a checkpoint without the entry) there is the plain pass alone."""
+    import contextlib
+    from .config import check_model_ema
+    e = check_model_ema(cfg)
+    if e is None or weight_average is None or weight_average.updates == 0 or e.EVAL == "plain":
+        return [(False, contextlib.nullcontext())]
+    averaged = (True, weight_average.applied(model))
+    return [averaged] if e.EVAL == "averaged" else [(False, contextlib.nullcontext()), averaged]
 
 
 # ------------------------------------------------------------------------------------------------ COCO-style box AP
@@ -1004,13 +1037,27 @@ def _print_results(prefix, res):
 _VOC_EVALUATORS = {}            # (name, datasets root, device) -> PascalVOCDetectionEvaluator of run_eval_only_catalog
 
 
-def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_results=False, prefix=""):
+def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_results=False, prefix="", weight_average=None):
     """``--eval-only --datasets-root DIR``: every ``cfg.DATASETS.TEST`` name the catalog knows -- the Cityscapes splits of
     cddmsl_amd/cityscapes.py and the COCO-json sets of cddmsl_amd/coco_json.py (``bdd_100k_val``) -> COCO-style box AP; the VOC
     family of cddmsl_amd/voc_catalog.py (``voc_2007_test``, ``Clipart1k_test`` ...) -> Pascal VOC AP with the set's year's metric.
     One printed line per set from rank 0 (each starting with ``prefix``); a name the catalog does not know, or a set whose json /
     image-set file is not there, is skipped with one printed line.  The matching runs on ``cfg.MODEL.DEVICE`` (the evaluators' ``device``).
-    Returns the exit code (or {name: result dict} on rank 0 with ``return_results``)."""
+    Returns the exit code (or {name: result dict} on rank 0 with ``return_results``).  ``weight_average`` (MODEL_EMA): see
+    ``averaged_passes``; the averaged weights' lines follow the plain ones."""
+    results = OrderedDict()
+    for averaged, weights in averaged_passes(model, cfg, weight_average):
+        with weights:
+            part = _eval_only_catalog_pass(model, cfg, datasets_root, rank, world, prefix, averaged)
+        for name, res in part.items():
+            results.setdefault(name, res).update(res)
+    return results if return_results else 0
+
+
+def _eval_only_catalog_pass(model, cfg, datasets_root, rank, world, prefix, averaged):
+    """one pass of ``run_eval_only_catalog`` over the weights the model holds now -> {name: result dict} (rank 0; else empty);
+    ``averaged``: the task keys carry ``_EMA``"""
+    mark = with_ema_suffix if averaged else (lambda r: r)
     import torch.distributed as dist
     from . import cityscapes, coco_json, voc_catalog
     from .data import build_detection_test_loader
@@ -1050,17 +1097,17 @@ def run_eval_only_catalog(model, cfg, datasets_root, rank=0, world=1, return_res
             continue
         loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
         new_evaluator = (lambda: voc) if voc is not None else (lambda: COCODetectionEvaluator(dicts, classes, device=cfg.MODEL.DEVICE))
-        res = inference_on_dataset(model, loader, with_proposal_recall(new_evaluator(), model, cfg, dicts))
+        res = mark(inference_on_dataset(model, loader, with_proposal_recall(new_evaluator(), model, cfg, dicts)))
         if rank == 0:
             _print_results(f"{prefix}{name}: ", res)
             results[name] = res
         if tta_enabled(cfg) and not is_proposal_network(model):
             loader = build_detection_test_loader(cfg, dicts, batch_size=1, rank=rank, world=world, device=cfg.MODEL.DEVICE)
-            tta = with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, new_evaluator()))
+            tta = mark(with_tta_suffix(inference_on_dataset(tta_model(cfg, model), loader, new_evaluator())))
             if rank == 0:
                 print(f"{prefix}{name}: " + str({k: {m: round(v, 4) for m, v in r.items()} for k, r in tta.items()}), flush=True)
                 results[name].update(tta)
-    return results if return_results else 0
+    return results
 
 
 def flatten_results(results):

@@ -11,7 +11,7 @@ from ctypes import c_float, c_int, c_long, c_void_p
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, require_cuda, stream_ptr, to_device_async
+from ._lib import check, lib, lib_weight_average, ptr, require_cuda, stream_ptr, to_device_async
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
@@ -966,6 +966,26 @@ def sgd_step_groups(params, grads, moms, norm_ws, lrs, wds, momentum, nesterov, 
     WD = (c_float * n)(*wds)
     check(_L().cddmsl_sgd_step_groups(P, G, M, S, LR, WD, n, ptr(norm_ws), momentum, int(nesterov), int(clip_mode), clip_value,
                                       int(first_step), stream_ptr()), "cddmsl_sgd_step_groups")
+
+
+@_timed("weight_average")
+def weight_average(avgs, params, w, copy):
+    """The averaged weights after a step, over lists of f32 tensors: ``copy``: avg = param bit for bit; else avg += w (param - avg),
+    ``w`` in [0, 1] (EMA: 1 - decay; running mean of n + 1 snapshots: 1 / (n + 1)).  ``params`` are only read."""
+    n = len(avgs)
+    assert len(params) == n, "one averaged tensor per parameter"
+    if n == 0:
+        return
+    require_cuda(*avgs, *params)
+    for e, p in zip(avgs, params):
+        assert e.dtype == p.dtype == torch.float32
+        assert same_layout(e, p), "averaged tensor and parameter must share a memory layout"
+        # the kernel walks numel() elements from data_ptr(): the elements must fill that span (contiguous in some dimension order)
+        assert p.numel() == 0 or sum((n_ - 1) * s_ for n_, s_ in zip(p.shape, p.stride())) + 1 == p.numel(), "tensors must be dense"
+    E = (c_void_p * n)(*[e.data_ptr() for e in avgs])
+    P = (c_void_p * n)(*[p.data_ptr() for p in params])
+    S = (c_long * n)(*[p.numel() for p in params])
+    check(lib_weight_average().cddmsl_weight_average(E, P, S, n, float(w), int(bool(copy)), stream_ptr()), "cddmsl_weight_average")
 
 
 # ------------------------------------------------------------------------------------------------ RoIAlign

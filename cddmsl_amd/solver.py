@@ -5,6 +5,7 @@
 tensors x (norm + clip + update).  The configuration every shipped YAML uses -- one lr and one weight decay for all parameters, no
 Nesterov, clipping off or by L2 norm -- runs through ``hip.sgd_clip_step``; every other one through ``hip.sgd_step_groups``.
 """
+import contextlib
 import math
 
 import torch
@@ -179,6 +180,102 @@ class ClippedSGD:
         layers.bump_weight_version()   # prepared (cast / transposed) weights are stale now
         layers.FP8_SCALES.roll()       # fp8 configuration: this step's recorded activation maxima become the next step's scales
         return lr
+
+
+def average_weight(mode, decay, n):
+    """The weight ``w`` of update number ``n >= 1`` (``n`` updates done so far, the first of them the copy) in avg += w (param - avg):
+    ``"ema"``: 1 - decay; ``"uniform"``: 1 / (n + 1), the running mean of n + 1 snapshots (torch.optim.swa_utils.AveragedModel)."""
+    if n < 1:
+        raise ValueError("average_weight: update 0 is the copy and has no weight")
+    if mode == "ema":
+        return 1.0 - float(decay)
+    if mode == "uniform":
+        return 1.0 / (n + 1.0)
+    raise ValueError("MODEL_EMA.MODE {!r}: one of ('ema', 'uniform')".format(mode))
+
+
+class WeightAverage:
+    """An average of the trainable parameters, one f32 tensor per parameter, kept on the parameters' device by ONE multi-tensor HIP
+    launch family per step (``hip.weight_average``): an exponential moving average (``mode`` "ema", D2Go's MODEL_EMA) or the uniform
+    running mean of the snapshots taken since ``start_iter`` ("uniform", SWA / SWAD).  Every normalisation layer here is FrozenBN,
+    so the averaged weights need no batch-norm re-estimation: ``applied(model)`` evaluates them as they are.
+    Construction and the state handling work on CPU tensors; only ``update`` needs the device."""
+
+    def __init__(self, named_params, mode="ema", decay=0.999, start_iter=0):
+        average_weight(mode, decay, 1)                   # (refuses an unknown mode)
+        self.mode, self.decay, self.start_iter = mode, float(decay), int(start_iter)
+        self.names, self.params = [], []
+        for name, p in named_params:
+            self.names.append(name)
+            self.params.append(p)
+        if len(set(self.names)) != len(self.names):
+            raise ValueError("WeightAverage: a parameter name appears twice")
+        with torch.no_grad():
+            self.tensors = [torch.zeros_like(p, memory_format=torch.preserve_format) for p in self.params]
+        self.updates = 0
+
+    def update(self, iteration):
+        """after ``optimizer.step()`` of iteration ``iteration``: nothing before ``start_iter``, then a copy, then the average"""
+        if iteration < self.start_iter:
+            return
+        with torch.no_grad():
+            ps = [p.data for p in self.params]
+            if self.updates == 0:
+                hip.weight_average(self.tensors, ps, 0.0, True)
+            else:
+                hip.weight_average(self.tensors, ps, average_weight(self.mode, self.decay, self.updates), False)
+        self.updates += 1
+
+    def state_dict(self):
+        return {"mode": self.mode, "decay": self.decay, "start_iter": self.start_iter, "updates": self.updates,
+                "tensors": {k: t.detach().cpu().clone(memory_format=torch.contiguous_format) for k, t in zip(self.names, self.tensors)}}
+
+    def load_state_dict(self, sd):
+        if sd["mode"] != self.mode:
+            raise ValueError(f"WeightAverage: the saved average is of mode {sd['mode']!r}, the configured one of {self.mode!r}")
+        saved = sd["tensors"]
+        if set(saved) != set(self.names):
+            diff = sorted(set(saved) ^ set(self.names))
+            raise ValueError(f"WeightAverage: the saved average covers other parameters ({len(diff)} names differ, e.g. {diff[:3]})")
+        for k, t in zip(self.names, self.tensors):
+            if tuple(saved[k].shape) != tuple(t.shape):
+                raise ValueError(f"WeightAverage: {k} is {tuple(saved[k].shape)} in the saved average, {tuple(t.shape)} in the model")
+        with torch.no_grad():
+            for k, t in zip(self.names, self.tensors):
+                t.copy_(saved[k])
+        self.updates = int(sd["updates"])
+
+    @contextlib.contextmanager
+    def applied(self, model=None):
+        """The averaged values in the parameters for the length of the block, the training values back on exit (also on an
+        exception).  The contents are exchanged through the parameters' own storage, so every address the rest of the code holds
+        (gradient views, momentum keys) stays valid; the weight version is bumped on entry and on exit, so no prepared (cast /
+        transposed / FrozenBN-folded) weight of the other set survives.  Before the first update it does nothing."""
+        if self.updates == 0:
+            yield self
+            return
+        with torch.no_grad():
+            kept = [p.detach().clone(memory_format=torch.preserve_format) for p in self.params]
+            for p, t in zip(self.params, self.tensors):
+                p.data.copy_(t)
+        layers.bump_weight_version()
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                for p, k in zip(self.params, kept):
+                    p.data.copy_(k)
+            layers.bump_weight_version()
+
+
+def build_weight_average(cfg, model, optimizer):
+    """``cfg.MODEL_EMA`` -> a WeightAverage over the optimizer's parameters under their ``model.named_parameters()`` names, or None"""
+    from .config import check_model_ema
+    e = check_model_ema(cfg)
+    if e is None:
+        return None
+    names = {id(p): k for k, p in model.named_parameters()}
+    return WeightAverage([(names[id(p)], p) for p in optimizer.params], e.MODE, e.DECAY, e.START_ITER)
 
 
 def linear_warmup_schedule(step, warmup, total):

@@ -6,8 +6,15 @@ inside one process, one call each per round after a warm-up, each call timed wit
 10th and 90th percentile over the rounds and the achieved GB/s of the median.  Bytes come from the shapes: p, m read and written,
 g read once (5 N x 4) for none / value, g read twice (6 N x 4) for the norm modes and sgd_clip_step.  Gradients are views packed
 back to back into one flat buffer, parameters and momentum buffers separate tensors, as in training.  Prints a table and one JSON line.
+``--average`` times the weight averaging that follows the step under MODEL_EMA instead: hip.weight_average (avg read and written, p
+read: 3 N x 4) against ``torch._foreach_lerp_`` on the same tensors (the same expression, one launch per chunk of tensors), next to
+the grouped step it follows.  Each is timed twice: as above, on an idle device, where the window between the two events also holds
+the host's work to prepare the launch (for the ctypes wrappers the pointer arrays of 63 tensors, tens of microseconds in which the device
+waits), and "queued" behind a few milliseconds of matrix products issued just before the first event, so that the launch is
+already in the queue when the device gets to it and the window holds the device's time alone -- the situation in training, where
+the host runs ahead of the device.  The JSON line also holds the two ratios, from the queued times.
 
-    python tools/optimizer_bench.py [--rounds 200] [--warmup 20]
+    python tools/optimizer_bench.py [--rounds 200] [--warmup 20] [--average]
 """
 import argparse
 import json
@@ -24,6 +31,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--average", action="store_true", help="time hip.weight_average against torch._foreach_lerp_ and the grouped step")
     args = ap.parse_args()
     from cddmsl_amd import hip
     from cddmsl_amd.config import get_cfg
@@ -55,10 +63,26 @@ def main():
     for name, mode in hip.SGD_CLIP_MODES.items():
         variants.append((f"sgd_step_groups {name}", 6 if mode >= 2 else 5,
                          lambda mode=mode: hip.sgd_step_groups(ps, gs, ms, ws, [lr * 1e-2 for lr in lrs], wds, mo, True, mode, clip, False)))
+    if args.average:
+        es, et = [p.clone() for p in ps], [p.clone() for p in ps]
+        w = 1.0 - 0.999
+        variants = [("weight_average", 3, lambda: hip.weight_average(es, ps, w, False)),
+                    ("torch._foreach_lerp_", 3, lambda: torch._foreach_lerp_(et, ps, w)),
+                    ("weight_average copy", 2, lambda: hip.weight_average(es, ps, 0.0, True)),
+                    ("torch._foreach_copy_", 2, lambda: torch._foreach_copy_(et, ps)),
+                    ("sgd_step_groups none", 5, lambda: hip.sgd_step_groups(ps, gs, ms, ws, [lr * 1e-2 for lr in lrs], wds, mo, True, 0, clip, False))]
+    queued = set()
+    if args.average:                                             # every variant a second time, behind work that hides the host's share
+        block = torch.randn(8192, 8192, device=dev, generator=gen).bfloat16()
+        queued = {name + " queued" for name, _, _ in variants}
+        variants = variants + [(name + " queued", passes, fn) for name, passes, fn in variants]
     times = {name: [] for name, _, _ in variants}
     for r in range(args.warmup + args.rounds):
         for name, _, fn in variants:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            if name in queued:
+                for _ in range(3):
+                    torch.mm(block, block)
             e0.record()
             fn()
             e1.record()
@@ -67,14 +91,19 @@ def main():
                 times[name].append(e0.elapsed_time(e1))
     assert all(bool(torch.isfinite(p).all()) for p in ps[:4])
     print(f"{len(ps)} tensors, {N} f32 elements ({N * 4 / 1e6:.1f} MB of parameters), {args.rounds} rounds")
-    print(f"{'variant':28s} {'median ms':>10s} {'p10':>8s} {'p90':>8s} {'GB/s':>8s}")
+    print(f"{'variant':34s} {'median ms':>10s} {'p10':>8s} {'p90':>8s} {'GB/s':>8s}")
     out = {"tensors": len(ps), "elements": N, "rounds": args.rounds, "variants": {}}
     for name, passes, _ in variants:
         t = sorted(times[name])
         med, p10, p90 = t[len(t) // 2], t[len(t) // 10], t[(9 * len(t)) // 10]
         gbs = passes * N * 4 / (med * 1e-3) / 1e9
-        print(f"{name:28s} {med:10.4f} {p10:8.4f} {p90:8.4f} {gbs:8.0f}")
+        print(f"{name:34s} {med:10.4f} {p10:8.4f} {p90:8.4f} {gbs:8.0f}")
         out["variants"][name] = {"ms_median": med, "ms_p10": p10, "ms_p90": p90, "bytes": passes * N * 4, "gb_per_s": gbs}
+    if args.average:
+        med = {k[:-len(" queued")]: v["ms_median"] for k, v in out["variants"].items() if k in queued}
+        out["average_over_foreach_lerp"] = med["weight_average"] / med["torch._foreach_lerp_"]
+        out["average_over_step"] = med["weight_average"] / med["sgd_step_groups none"]
+        print(f"queued: weight_average / torch._foreach_lerp_ {out['average_over_foreach_lerp']:.3f}, / sgd_step_groups none {out['average_over_step']:.3f}")
     print(json.dumps(out))
 
 

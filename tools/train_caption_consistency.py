@@ -14,6 +14,9 @@ cddmsl_amd/coco_json.py) and for the VOC family of the VOC config (cddmsl_amd/vo
 chained into one paired loader, Pascal VOC AP on ``voc_2007_test`` / ``Clipart1k_test`` / ``Watercolor_test`` / ``Comic_test`` by name;
 ``--voc-root`` with ``--dt-data`` keeps precedence), ``TEST.EVAL_PERIOD`` repeats that evaluation during training whenever a test set is given, and
 ``MODEL.WEIGHTS`` / ``--resume`` / ``MODEL.PRE_TRAINED_RCLIP_PATH`` go through cddmsl_amd/checkpoint.py.
+``MODEL_EMA.ENABLED True`` keeps an average of the trainable weights (``MODE ema`` with ``DECAY``, or ``uniform`` from ``START_ITER``) on the
+GPU after every step, saves it in every checkpoint and evaluates it behind the training weights (``bbox_EMA`` ... lines; ``MODEL_EMA.EVAL``
+plain / averaged / both), with ``--eval-only`` from the ``weight_average`` entry of ``MODEL.WEIGHTS``.
 ``TEST.PROPOSAL_RECALL True`` adds a ``box_proposals`` line (AR@100 ... ARl@1000 of the RPN proposals) per test set to every
 evaluation; ``--eval-only MODEL.META_ARCHITECTURE ProposalNetwork`` evaluates backbone + RPN alone and prints only that line.
 """
@@ -70,10 +73,12 @@ def build_eval_hook(tr, cfg, args, rank, world, max_iter):
     if period <= 0:
         return None
     if args.datasets_root and not (args.voc_root and args.dt_data):
-        fn = lambda prefix: evaluation.run_eval_only_catalog(tr.model, cfg, args.datasets_root, rank, world, return_results=True, prefix=prefix)
+        fn = lambda prefix: evaluation.run_eval_only_catalog(tr.model, cfg, args.datasets_root, rank, world, return_results=True, prefix=prefix,
+                                                             weight_average=tr.weight_average)
     elif args.voc_root and os.path.exists(os.path.join(args.voc_root, "ImageSets", "Main", args.voc_split + ".txt")):
         name = cfg.DATASETS.TEST[0] if cfg.DATASETS.TEST else "voc_" + args.voc_split
-        fn = lambda prefix: {name: evaluation.run_eval_only(tr.model, cfg, args, rank, world, return_results=True, prefix=prefix)}
+        fn = lambda prefix: {name: evaluation.run_eval_only(tr.model, cfg, args, rank, world, return_results=True, prefix=prefix,
+                                                            weight_average=tr.weight_average)}
     else:
         return None
     return evaluation.PeriodicEval(tr, period, fn, max_iter, rank)
@@ -113,7 +118,7 @@ def main(args):
         raise SystemExit(eval_proposal_network(cfg, args, rank, world))
     tr = engine.build_trainer(cfg, per_rank, args.height, args.width, seed=cfg.SEED)
     from cddmsl_amd.checkpoint import DetectionCheckpointer
-    ckpt = DetectionCheckpointer(tr.model, cfg.OUTPUT_DIR, optimizer=tr.optimizer, trainer=tr)
+    ckpt = DetectionCheckpointer(tr.model, cfg.OUTPUT_DIR, optimizer=tr.optimizer, trainer=tr, weight_average=tr.weight_average)
     if not cfg.MODEL.WEIGHTS:       # no checkpoints offline: seeded synthetic weights
         tr.model.load_state_dict(synthetic.make_state_dict(0, num_classes=cfg.MODEL.ROI_HEADS.NUM_CLASSES), strict=False)
         tr.clipcap_model.load_state_dict(synthetic.make_mapper_state_dict(1))
@@ -129,9 +134,9 @@ def main(args):
     if args.eval_only:              # train_caption_consistency.py:143-152: model.eval(); inference over the test sets
         from cddmsl_amd import evaluation
         if args.datasets_root and not args.voc_root:
-            raise SystemExit(evaluation.run_eval_only_catalog(tr.model, cfg, args.datasets_root, rank, world))
+            raise SystemExit(evaluation.run_eval_only_catalog(tr.model, cfg, args.datasets_root, rank, world, weight_average=tr.weight_average))
         assert args.voc_root, "--eval-only needs --voc-root (a VOC devkit year directory) or --datasets-root: datasets are not shipped"
-        raise SystemExit(evaluation.run_eval_only(tr.model, cfg, args, rank, world))
+        raise SystemExit(evaluation.run_eval_only(tr.model, cfg, args, rank, world, weight_average=tr.weight_average))
     if args.voc_root and args.dt_data:      # real paired data; default: seeded synthetic batches
         from cddmsl_amd import data
         from cddmsl_amd.evaluation import VOC_CLASS_NAMES
