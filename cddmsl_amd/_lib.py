@@ -18,8 +18,13 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_hip.h")
 WEIGHT_AVERAGE_LIB_PATH = os.path.join(_HERE, "libcddmsl_weight_average.so")
 WEIGHT_AVERAGE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_weight_average.h")
 
+# the photometric augmentation of INPUT.COLOR_JITTER on the device path: likewise
+COLOR_JITTER_LIB_PATH = os.path.join(_HERE, "libcddmsl_color_jitter.so")
+COLOR_JITTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cddmsl_color_jitter.h")
+
 _lib = None
 _lib_weight_average = None
+_lib_color_jitter = None
 
 
 class HipLibraryError(RuntimeError):
@@ -111,6 +116,14 @@ def lib_weight_average():
     if _lib_weight_average is None:
         _lib_weight_average = _load(WEIGHT_AVERAGE_LIB_PATH, WEIGHT_AVERAGE_HEADER_PATH)
     return _lib_weight_average
+
+
+def lib_color_jitter():
+    """libcddmsl_color_jitter.so (csrc/color_jitter.hip), typed from include/cddmsl_color_jitter.h; loaded on first use."""
+    global _lib_color_jitter
+    if _lib_color_jitter is None:
+        _lib_color_jitter = _load(COLOR_JITTER_LIB_PATH, COLOR_JITTER_HEADER_PATH)
+    return _lib_color_jitter
 
 
 def stream_ptr():

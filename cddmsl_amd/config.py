@@ -7,6 +7,7 @@ takes the CLI ``KEY VALUE`` pairs (engine/defaults.py:133-140).
 """
 import ast
 import copy
+import math
 import os
 
 import yaml
@@ -141,7 +142,13 @@ def get_cfg():
         "INPUT": {"MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333, "FORMAT": "BGR",
                   "MIN_SIZE_TRAIN_SAMPLING": "choice", "RANDOM_FLIP": "horizontal",
                   # defaults.py:68-73: T.RandomCrop in front of the resize (training mapper only)
-                  "CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]}},
+                  "CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]},
+                  # project-specific: RandomBrightness / RandomContrast / RandomSaturation (intensity_min, intensity_max) and RandomLighting
+                  # (scale) of the reference, in that order, on the final uint8 image of the training mapper; a range of exactly (1.0, 1.0)
+                  # and a scale of 0.0 switch an operation off.  PROB: RandomApply's.  TWIN: the domain twin gets the "same" draws, draws of
+                  # its own ("independent") or is left alone ("none").  With DATALOADER.DEVICE_RESIZE one HIP launch per batch, same bytes
+                  "COLOR_JITTER": {"ENABLED": False, "PROB": 1.0, "BRIGHTNESS": (1.0, 1.0), "CONTRAST": (1.0, 1.0), "SATURATION": (1.0, 1.0),
+                                   "LIGHTING": 0.0, "TWIN": "same"}},
         "DATASETS": {"TRAIN": (), "TEST": ()},
         "DATALOADER": {"NUM_WORKERS": 4, "ASPECT_RATIO_GROUPING": True, "FILTER_EMPTY_ANNOTATIONS": True,
                        # build-specific: ResizeShortestEdge / RandomFlip / HWC -> CHW / RGB -> BGR of the loader's images in one HIP launch per
@@ -186,3 +193,34 @@ def check_model_ema(cfg):
     if isinstance(e.START_ITER, bool) or not isinstance(e.START_ITER, int) or e.START_ITER < 0:
         raise ValueError("MODEL_EMA.START_ITER {!r}: an integer >= 0".format(e.START_ITER))
     return e
+
+
+COLOR_JITTER_TWINS = ("same", "independent", "none")
+
+
+def _number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+
+
+def check_color_jitter(cfg):
+    """-> cfg.INPUT.COLOR_JITTER if it is enabled and valid, None if absent or disabled; ValueError naming the key otherwise.  The
+    values are judged whether the block is enabled or not; the channel order only when it is."""
+    j = cfg.INPUT.get("COLOR_JITTER", None)
+    if j is None:
+        return None
+    for name in ("BRIGHTNESS", "CONTRAST", "SATURATION"):
+        v = j[name]
+        if not (isinstance(v, (tuple, list)) and len(v) == 2 and all(_number(a) for a in v) and 0 <= v[0] <= v[1]):
+            raise ValueError("INPUT.COLOR_JITTER.{} {!r}: two finite numbers (intensity_min, intensity_max) with 0 <= min <= max".format(name, v))
+    if not _number(j.LIGHTING) or j.LIGHTING < 0:
+        raise ValueError("INPUT.COLOR_JITTER.LIGHTING {!r}: a finite number >= 0".format(j.LIGHTING))
+    if not _number(j.PROB) or not 0.0 <= j.PROB <= 1.0:
+        raise ValueError("INPUT.COLOR_JITTER.PROB {!r}: a number in [0, 1]".format(j.PROB))
+    if j.TWIN not in COLOR_JITTER_TWINS:
+        raise ValueError("INPUT.COLOR_JITTER.TWIN {!r}: one of {}".format(j.TWIN, COLOR_JITTER_TWINS))
+    if not j.ENABLED:
+        return None
+    channels = tuple(float(a) for a in j.SATURATION) != (1.0, 1.0) or j.LIGHTING != 0
+    if channels and cfg.INPUT.FORMAT not in ("RGB", "BGR"):
+        raise ValueError("INPUT.FORMAT {!r}: INPUT.COLOR_JITTER.SATURATION and .LIGHTING need RGB or BGR channels".format(cfg.INPUT.FORMAT))
+    return j

@@ -20,6 +20,10 @@ fvcore, which is not installed here, so their numerics are pinned by that shared
 ``DATALOADER.DEVICE_RESIZE`` (default off) moves resize, flip, HWC -> CHW and RGB -> BGR into ONE HIP launch per batch on the staging
 stream (``cddmsl_resize_batch_u8``, Pillow's resample bit for bit): the mapper then only decodes and records what is left to do, and
 ``DeviceBatches`` hands out the same bytes as the host path.
+
+``INPUT.COLOR_JITTER`` (default off; augment.py) varies the photometry of the training images after crop, resize and flip: in the mapper
+(numpy) on the host path, in one more HIP launch per batch (``cddmsl_color_jitter_batch_u8``) behind the resize on the device path --
+the same bytes either way.
 """
 import os
 import xml.etree.ElementTree as ET
@@ -28,6 +32,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from .augment import ColorJitter, color_jitter_u8
+from .config import check_color_jitter
 from .evaluation import VOC_CLASS_NAMES
 from .structures import Boxes, Instances
 
@@ -92,8 +98,9 @@ DEVICE_RESIZE_KEY = "device_resize"      # a sample's record of the resize / mir
 class DatasetMapper:
     """Dataset dict -> model input dict; the random draws come from ``rng`` in the reference's order: the crop window (INPUT.CROP,
     ``RandomCrop`` augmentation_impl.py:367-399), the short edge (``choice`` or, with MIN_SIZE_TRAIN_SAMPLING "range", ``randint``),
-    then the flip -- a ``RandomState(s)`` reproduces ``np.random.seed(s)`` on the reference.  With the shipped defaults that is one
-    ``rng.choice`` and one ``rng.uniform`` per sample.  The test mapper resizes only (``build_augmentation(cfg, False)``)."""
+    then the flip, then INPUT.COLOR_JITTER's (``augment.ColorJitter.draw_pair``; none when the block is off or no operation is active)
+    -- a ``RandomState(s)`` reproduces ``np.random.seed(s)`` on the reference.  With the shipped defaults that is one ``rng.choice`` and
+    one ``rng.uniform`` per sample.  The test mapper resizes only (``build_augmentation(cfg, False)``)."""
 
     CROP_TYPES = ("relative_range", "relative", "absolute", "absolute_range")
 
@@ -102,8 +109,11 @@ class DatasetMapper:
         self.is_train, self.fmt = is_train, i.FORMAT
         self.min_sizes = list(i.MIN_SIZE_TRAIN) if is_train else [i.MIN_SIZE_TEST]
         self.max_size = i.MAX_SIZE_TRAIN if is_train else i.MAX_SIZE_TEST
-        self.size_range, self.flip, self.crop_type, self.crop_size = False, 0, None, None
+        self.size_range, self.flip, self.crop_type, self.crop_size, self.jitter = False, 0, None, None, None
         if is_train:
+            block = check_color_jitter(cfg)
+            jitter = ColorJitter(block) if block is not None else None
+            self.jitter = jitter if jitter is not None and jitter.active else None      # (no active operation: no draws at all)
             style, flip, crop = i.get("MIN_SIZE_TRAIN_SAMPLING", "choice"), i.get("RANDOM_FLIP", "horizontal"), i.get("CROP") or {}
             if style not in ("choice", "range"):
                 raise ValueError(f"INPUT.MIN_SIZE_TRAIN_SAMPLING must be 'choice' or 'range', not {style!r}")
@@ -161,9 +171,14 @@ class DatasetMapper:
         newh, neww = shortest_edge_size(h, w, size, self.max_size) if size else (h, w)
         flip = bool(self.flip and self.rng.uniform() < 0.5) and self.flip      # False, or the code of the configured mirror
 
-        def tf(a):
+        jit, jit_twin = self.jitter.draw_pair(self.rng, twin is not None) if self.jitter is not None else (None, None)
+
+        def tf(a, jitter=None):
             a = resize_image(a, newh, neww)
-            return a[:, ::-1] if flip == 1 else (a[::-1] if flip == 2 else a)
+            a = a[:, ::-1] if flip == 1 else (a[::-1] if flip == 2 else a)
+            if jitter:
+                a = color_jitter_u8(a, jitter, self.fmt == "BGR")
+            return a
 
         if self.device_resize:
             # DATALOADER.DEVICE_RESIZE: the decoded (and cropped) [h, w, 3] RGB arrays go on as they are, with a record of what is still
@@ -174,13 +189,15 @@ class DatasetMapper:
             d[DEVICE_RESIZE_KEY] = {"size": (newh, neww), "flip": flip, "reverse_channels": self.fmt == "BGR",
                                     "xtab": packed_table(w, neww) if neww != w else None,
                                     "ytab": packed_table(h, newh) if newh != h else None}
+            if jit or jit_twin:                                      # INPUT.COLOR_JITTER's draws: applied behind the resize, one launch per batch
+                d[DEVICE_RESIZE_KEY]["jitter"] = {"image": jit, "image_trgt": jit_twin}
             d["image"] = torch.from_numpy(np.array(img, order="C"))     # (a copy: PIL hands out a read-only buffer; of the window only)
             if twin is not None:
                 d["image_trgt"] = torch.from_numpy(np.array(twin, order="C"))
         else:
-            d["image"] = torch.from_numpy(np.ascontiguousarray(tf(img).transpose(2, 0, 1)))
+            d["image"] = torch.from_numpy(np.ascontiguousarray(tf(img, jit).transpose(2, 0, 1)))
             if twin is not None:
-                d["image_trgt"] = torch.from_numpy(np.ascontiguousarray(tf(twin).transpose(2, 0, 1)))
+                d["image_trgt"] = torch.from_numpy(np.ascontiguousarray(tf(twin, jit_twin).transpose(2, 0, 1)))
         anns = d.pop("annotations", None)
         if not self.is_train or anns is None:
             return d
@@ -345,6 +362,7 @@ class DeviceBatches:
             slots.append((i, k, off, nb, t.dtype, tuple(t.shape)))
             off += n
         work, res_bytes = [], 0                            # the kernel's item descriptors, and where each result goes
+        jitter = []                                        # INPUT.COLOR_JITTER: (offset in the result, h, w, parameters, bgr) of the images that drew any
         for i, k, o, nb, dt, shape in slots:
             if i in recs and k in ("image", "image_trgt"):
                 rec = recs[i]
@@ -353,6 +371,8 @@ class DeviceBatches:
                 xt = (slots[tabs[(w, neww)]][2] // 4, rec["xtab"][1]) if neww != w else (-1, 0)
                 yt = (slots[tabs[(h, newh)]][2] // 4, rec["ytab"][1]) if newh != h else (-1, 0)
                 work.append((o, res_bytes, h, w, newh, neww, int(rec["flip"]), int(rec["reverse_channels"]), *xt, *yt))
+                if rec.get("jitter", {}).get(k):
+                    jitter.append((res_bytes, newh, neww, rec["jitter"][k], rec["reverse_channels"]))
                 res_bytes += (3 * newh * neww + 255) // 256 * 256
         owned = []
         with torch.cuda.stream(self._stream):
@@ -362,6 +382,8 @@ class DeviceBatches:
                 from . import hip
                 res = torch.empty(res_bytes, dtype=torch.uint8, device=self.device)
                 hip.resize_batch_u8(dev, res, dev.view(torch.int32) if tabs else None, work)
+                if jitter:                                 # (its workspace lives and dies on this stream)
+                    hip.color_jitter_batch_u8(res, jitter)
                 owned.append(res)
             ev = torch.cuda.Event()
             ev.record(self._stream)

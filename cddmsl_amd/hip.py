@@ -11,7 +11,7 @@ from ctypes import c_float, c_int, c_long, c_void_p
 import numpy as np
 import torch
 
-from ._lib import check, lib, lib_weight_average, ptr, require_cuda, stream_ptr, to_device_async
+from ._lib import check, lib, lib_color_jitter, lib_weight_average, ptr, require_cuda, stream_ptr, to_device_async
 
 DT = {torch.bfloat16: 0, torch.float32: 1}
 
@@ -579,6 +579,30 @@ def resize_batch_u8(src, dst, tab, items):
     check(_L().cddmsl_resize_batch_u8(ptr(src), src.numel(), ptr(dst), dst.numel(), ptr(tab), 0 if tab is None else tab.numel(),
                                       ctypes.cast(arr, c_void_p), len(items), stream_ptr()), "cddmsl_resize_batch_u8")
     return dst
+
+
+class JitterItem(ctypes.Structure):
+    """``cddmsl_jitter_item`` of include/cddmsl_color_jitter.h"""
+    _fields_ = [("off", c_long)] + [(k, c_int) for k in (
+        "h", "w", "ops", "bgr", "b_dw", "b_sw", "c_dw", "c_sw", "s_dw", "s_sw", "light_r", "light_g", "light_b", "reserved")]
+
+
+def color_jitter_batch_u8(buf, items):
+    """INPUT.COLOR_JITTER for a whole batch in place, on the current stream (a sum and an apply launch per 32 items).  ``buf``: device
+    uint8 buffer holding planar [3, h, w] images; ``items``: one ``(off, h, w, params, bgr)`` per image -- byte offset into ``buf``,
+    the parameters ``augment.ColorJitter.draw`` gave (None or {}: the image is left alone), and whether plane 0 is blue.  Bit-equal to
+    ``augment.color_jitter_u8`` on each image; bytes outside the images are not touched.  Returns the int64 per-item byte sums the
+    contrast step used (0 where it is off), or None when no item has contrast.  The library checks every item before it launches; a
+    refusal raises."""
+    from .augment import CONTRAST, descriptor
+    require_cuda(buf)
+    assert buf.dtype == torch.uint8 and buf.is_contiguous()
+    desc = [descriptor(off, h, w, params, bgr) for off, h, w, params, bgr in items]
+    arr = (JitterItem * max(len(desc), 1))(*[JitterItem(*d) for d in desc])
+    sums = torch.empty(len(desc), dtype=torch.int64, device=buf.device) if any(d[3] & CONTRAST for d in desc) else None
+    check(lib_color_jitter().cddmsl_color_jitter_batch_u8(ptr(buf), buf.numel(), ctypes.cast(arr, c_void_p), len(desc), ptr(sums), stream_ptr()),
+          "cddmsl_color_jitter_batch_u8")
+    return sums
 
 
 @_timed("avgpool2_fwd")

@@ -15,6 +15,11 @@ bench.py times the step on synthetic batches already resident in HBM; this tool 
 ``--crop [TYPE:A,B]`` / ``--min-size-range`` / ``--flip vertical`` pass INPUT.CROP, MIN_SIZE_TRAIN_SAMPLING "range" and RANDOM_FLIP on.
 ``--device-resize`` runs 2. and 3. with DATALOADER.DEVICE_RESIZE: the workers only decode, and the staging thread's one kernel launch
 per batch (cddmsl_resize_batch_u8) resizes, mirrors and transposes on the GPU -- the same bytes reach the model.
+``--color-jitter`` switches INPUT.COLOR_JITTER on with representative ranges (brightness, contrast and saturation in 0.6..1.4, lighting
+scale 25.5 = AlexNet's 0.1 on 0..255 pixels, the twin with the same draws): in the workers (numpy) without ``--device-resize``, one more
+launch per batch (cddmsl_color_jitter_batch_u8) with it.  ``--kernel-times`` (with ``--device-resize``) stages one batch by hand and
+prints the device time of the batch's resize and jitter launches, each timed between events behind a few milliseconds of queued
+fills so that no launch latency is inside the window, next to the bytes they move.
 
 usage (GPU box): python tools/loader_bench.py --iters 50 > profiles/r03_loader.txt
 """
@@ -64,6 +69,61 @@ def make_voc_tree(root, n, seed=0, year="VOC2007", twin="clipart"):
     return base
 
 
+def kernel_times(cfg, dicts, batch, reps=20):
+    """one landscape batch through DeviceBatches._stage, `reps` times; the resize and the jitter launch each between two events on the
+    staging stream, behind queued fills (the host has long enqueued both launches when the device reaches them)"""
+    from cddmsl_amd import data, hip
+    assert cfg.DATALOADER.DEVICE_RESIZE, "--kernel-times measures the device path: add --device-resize"
+    mapper = data.DatasetMapper(cfg, True, np.random.RandomState(0))
+    samples = []
+    for d in dicts:
+        s = mapper(d)
+        if s[data.DEVICE_RESIZE_KEY]["size"][1] > s[data.DEVICE_RESIZE_KEY]["size"][0]:
+            samples.append(s)
+        if len(samples) == batch:
+            break
+    db = data.DeviceBatches(iter(()), cfg.MODEL.DEVICE)
+    filler = torch.empty(1 << 30, dtype=torch.uint8, device=cfg.MODEL.DEVICE)
+    torch.cuda.synchronize()
+    events, moved = {"resize": [], "jitter": []}, {}
+    real = {"resize": hip.resize_batch_u8, "jitter": hip.color_jitter_batch_u8}
+
+    def timed(name):
+        def f(*a):
+            if name == "resize":
+                for _ in range(4):
+                    filler.fill_(1)                        # ~ms of device work in front: both launches below queue up behind it
+                moved[name] = sum(3 * it[2] * it[3] + 3 * it[4] * it[5] for it in a[3])
+            else:
+                moved[name] = sum(3 * h * w * (3 if "contrast" in p else 2) for _, h, w, p, _ in a[1])
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = real[name](*a)
+            e1.record()
+            events[name].append((e0, e1))
+            return out
+        return f
+
+    hip.resize_batch_u8, hip.color_jitter_batch_u8 = timed("resize"), timed("jitter")
+    try:
+        for _ in range(reps + 3):
+            db._stage(samples)
+            torch.cuda.synchronize()
+    finally:
+        hip.resize_batch_u8, hip.color_jitter_batch_u8 = real["resize"], real["jitter"]
+        db.close()
+    sizes = sorted({tuple(s[data.DEVICE_RESIZE_KEY]["size"]) for s in samples})
+    print(f"# kernel times, one batch of {len(samples)} pairs ({2 * len(samples)} images, output sizes {sizes[0]} .. {sizes[-1]}), median of {reps} after 3 warm-up batches, behind queued fills")
+    for name, evs in events.items():
+        if not evs:
+            print(f"{name:8s} not launched")
+            continue
+        ms = sorted(e0.elapsed_time(e1) for e0, e1 in evs[3:])
+        med = ms[len(ms) // 2]
+        what = "read of the originals + write of the results" if name == "resize" else "read + write of the results, one more read for contrast; sum + apply launches"
+        print(f"{name:8s} {med:7.4f} ms (min {ms[0]:.4f}, max {ms[-1]:.4f})   {moved[name] / 1e6:8.1f} MB ({what})   {moved[name] / med / 1e6:7.1f} GB/s")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=256)
@@ -72,6 +132,8 @@ def main():
     ap.add_argument("--workers", default="0,4,8,12")
     ap.add_argument("--loader-batches", type=int, default=12)
     ap.add_argument("--device-resize", action="store_true", help="DATALOADER.DEVICE_RESIZE: resize / flip on the GPU in the staging thread")
+    ap.add_argument("--color-jitter", action="store_true", help="INPUT.COLOR_JITTER: brightness / contrast / saturation / lighting on image and twin")
+    ap.add_argument("--kernel-times", action="store_true", help="device time of one batch's resize and jitter launches (needs --device-resize)")
     ap.add_argument("--skip-step", action="store_true", help="loader alone: skip the training-step measurements")
     ap.add_argument("--crop", nargs="?", const="relative_range:0.9,0.9", default=None, metavar="TYPE:A,B",
                     help="INPUT.CROP: RandomCrop in front of the resize, e.g. relative_range:0.9,0.9 (the default with no value) or absolute:300,400")
@@ -92,6 +154,9 @@ def main():
         cfg.merge_from_list(["INPUT.MIN_SIZE_TRAIN_SAMPLING", "range", "INPUT.MIN_SIZE_TRAIN", (min(cfg.INPUT.MIN_SIZE_TRAIN), max(cfg.INPUT.MIN_SIZE_TRAIN))])
     if args.flip is not None:
         cfg.merge_from_list(["INPUT.RANDOM_FLIP", args.flip])
+    if args.color_jitter:
+        cfg.merge_from_list(["INPUT.COLOR_JITTER.ENABLED", True, "INPUT.COLOR_JITTER.BRIGHTNESS", (0.6, 1.4), "INPUT.COLOR_JITTER.CONTRAST", (0.6, 1.4),
+                             "INPUT.COLOR_JITTER.SATURATION", (0.6, 1.4), "INPUT.COLOR_JITTER.LIGHTING", 25.5])
     engine.limit_host_threads()       # as build_trainer does: the box grants ~16 CPUs, torch's default intra-op pool has one thread per logical CPU
     root = tempfile.mkdtemp(prefix="cddmsl_voc_")
     t0 = time.perf_counter()
@@ -99,7 +164,9 @@ def main():
     print(f"# synthetic VOC tree: {args.images} JPEG pairs (500x375 / 375x500) under {root}, written in {time.perf_counter() - t0:.1f} s")
     dicts = data.load_voc_instances(base, "trainval", VOC_CLASS_NAMES, dt_data="clipart")
     print(f"# INPUT.MIN_SIZE_TRAIN {tuple(cfg.INPUT.MIN_SIZE_TRAIN)} ({cfg.INPUT.MIN_SIZE_TRAIN_SAMPLING}) max {cfg.INPUT.MAX_SIZE_TRAIN}, flip {cfg.INPUT.RANDOM_FLIP}, crop {(cfg.INPUT.CROP.TYPE, tuple(cfg.INPUT.CROP.SIZE)) if cfg.INPUT.CROP.ENABLED else None}; host: {os.cpu_count()} logical CPUs ({bench.cpu_model_name()})")
-    print(f"# DATALOADER.DEVICE_RESIZE {cfg.DATALOADER.DEVICE_RESIZE}")
+    print(f"# DATALOADER.DEVICE_RESIZE {cfg.DATALOADER.DEVICE_RESIZE}; INPUT.COLOR_JITTER {dict(cfg.INPUT.COLOR_JITTER) if cfg.INPUT.COLOR_JITTER.ENABLED else 'off'}")
+    if args.kernel_times:
+        kernel_times(cfg, dicts, args.batch)
     print("# 1. loader alone (decode 2 JPEGs + resize both + flip + batch + pin + H2D" + (" of the originals + one resize launch per batch" if args.device_resize else "")
           + "), samples/s after 2 warm-up batches")
     rates = {}
