@@ -1,5 +1,6 @@
 """Case table of tests/test_gpu_gemm_exact.py, plain data (the host test imports it to check that every launch recorded in
-tests/golden/bench_gemm_launches.json and every kernel instantiation has a Tier A and a Tier B case).
+tests/golden/bench_gemm_launches.json -- the CLIP benchmark step -- and in tests/golden/stock_gemm_launches.json -- the stock R50-C4
+configuration's step -- and every kernel instantiation has a Tier A and a Tier B case).
 
 A case: entry point, the kernel id dispatch must pick (cddmsl_last_kernel; hip.py _CONV_KERNEL), the per-call switches that force
 it, the geometry (the keys tools/record_gemm_launches.py writes), the epilogue flags, the tiers it runs in, the variants it covers
@@ -219,11 +220,75 @@ CASES.append(case("nt_mapper", "gemm_nt_batched", 3, nt(544, 1024, 1920, 16, 307
                   dict(bias=False, out_f32=True), {}, "the mapper's per-head product (A, B rows 30720 apart), k_conv_fwd256, plan_fwd (use_gemm256 with the batch count)",
                   ["batched_strided"]))
 
+# ---- the stock ResNet-50 path (cddmsl_amd/modeling/resnet.py): the stride lives in the first 1x1 of a block and in its shortcut, the stem
+# is a 7x7 stride-2 pad-3 convolution.  plan_fwd puts no condition on the stride, so a stride-2 1x1 lands on every forward GEMM kernel
+# by size; each of them addresses a tile from a per-block base plus lane offsets, and with stride 2 in H and W a tile's rows skip every
+# other pixel and every other image row.  Odd and even maps ((H - 1) // 2 + 1 floors or not), two images and more (an image boundary
+# inside a tile), more than one row tile.  tests/golden/stock_gemm_launches.json records which of these the stock step launches.
+_BN, _BN_RELU = _FWD_SETS_1X1["bn"], _FWD_SETS_1X1["bn_relu"]
+CASES += [
+    case("stem_7x7_s2_bf16", "conv_fwd", 1, conv(2, 37, 53, 8, 64, 7, 2, 3), _BN_RELU, {},
+         "k_conv_fwd on BasicStem's 7x7 stride 2 pad 3, one 16-byte chunk per pixel (all 8 channels non-zero here): 49 taps are above the "
+         "31 of gemm256_legal / fwd2_legal and 64 outputs no whole 128 columns, plan_fwd's default", ["stem_7x7_s2", "fwd"]),
+    case("stem_7x7_s2_bf16_even", "conv_fwd", 1, conv(2, 38, 54, 8, 64, 7, 2, 3), _BN_RELU, {},
+         "k_conv_fwd, the stem on an even map (the last tap row and column lie in the padding), plan_fwd's default", ["stem_7x7_s2", "fwd"]),
+    case("stem_7x7_s2_f32", "conv_fwd", 1, dict(conv(2, 37, 53, 4, 64, 7, 2, 3), dtype="f32"), _BN_RELU, {},
+         "k_conv_fwd<float> on the stem (4 f32 channels are one chunk), plan_fwd's default", ["stem_7x7_s2", "fwd_f32"]),
+    case("stem_7x7_s2_f32_even", "conv_fwd", 1, dict(conv(2, 38, 54, 4, 64, 7, 2, 3), dtype="f32"), _BN_RELU, {},
+         "k_conv_fwd<float> on the stem, even map, plan_fwd's default", ["stem_7x7_s2", "fwd_f32"]),
+    case("fwd_1x1_s2_bn_relu", "conv_fwd", 1, conv(2, 9, 37, 64, 136, 1, 2), _BN_RELU, F128,
+         "k_conv_fwd 1x1 stride 2 (conv1 of a stock block): 190 rows are two tiles, the image boundary inside the first; plan_fwd's default", ["fwd_1x1_s2"]),
+    case("fwd_1x1_s2_bn", "conv_fwd", 1, conv(2, 9, 37, 64, 136, 1, 2), _BN, F128,
+         "k_conv_fwd 1x1 stride 2 without ReLU (the shortcut of a stock block), plan_fwd's default", ["fwd_1x1_s2"]),
+    case("fwd_1x1_s2_bn_relu_even", "conv_fwd", 1, conv(2, 10, 38, 64, 136, 1, 2), _BN_RELU, F128,
+         "k_conv_fwd 1x1 stride 2 on an even map: the last row and column are never read; plan_fwd's default", ["fwd_1x1_s2"]),
+    case("fwd_1x1_s2_bn_even", "conv_fwd", 1, conv(2, 10, 38, 64, 136, 1, 2), _BN, F128,
+         "k_conv_fwd 1x1 stride 2, shortcut epilogue, even map; plan_fwd's default", ["fwd_1x1_s2"]),
+    case("fwd2_1x1_s2_bn_relu", "conv_fwd", 11, conv(3, 19, 23, 96, 384, 1, 2), _BN_RELU, FWD2,
+         "k_conv_fwd2<bf16, false, 0> 1x1 stride 2 (stride is legal there: fwd2_legal): 360 rows are two row tiles, two image boundaries "
+         "inside the first; launch_fwd2", ["fwd2_1x1_s2"]),
+    case("fwd2_1x1_s2_bn_even", "conv_fwd", 11, conv(3, 20, 24, 96, 384, 1, 2), _BN, FWD2,
+         "k_conv_fwd2 1x1 stride 2, shortcut epilogue, even map; launch_fwd2", ["fwd2_1x1_s2"]),
+    case("fwd256_1x1_s2_bn_relu", "conv_fwd", 3, conv(3, 19, 23, 128, 512, 1, 2), _BN_RELU, F256,
+         "k_conv_fwd256<bf16, false, false, 0> 1x1 stride 2, the plain tile form (4 tiles): two row panels, image boundaries inside the "
+         "first; launch256_main", ["fwd256_1x1_s2"]),
+    case("fwd256_1x1_s2_bn_even", "conv_fwd", 3, conv(3, 20, 24, 128, 512, 1, 2), _BN, F256,
+         "k_conv_fwd256 1x1 stride 2, shortcut epilogue, even map; launch256_main", ["fwd256_1x1_s2"]),
+    case("fwd256_roi_crops_s2", "conv_fwd", 3, conv(37, 14, 14, 256, 512, 1, 2), _BN_RELU, F256,
+         "k_conv_fwd256 on the RoI head's geometry, 14 x 14 crops to 7 x 7: 49 rows per crop, a 256-row tile spans more than five crops; "
+         "launch256_main", ["fwd256_1x1_s2"]),
+    case("fwd256_persistent_s2", "conv_fwd", 3, conv(2, 181, 181, 128, 1024, 1, 2), _BN_RELU, F256,
+         "persistent form under stride 2 (K = 128 <= 512; 2 x 91 x 91 = 16 562 rows are 65 panels, 260 tiles > 256 CUs, the ragged last panel "
+         "in the second round): launch256_main's persistent form", ["fwd256_persistent_s2", "fwd256_persistent"]),
+    case("fwd256_persistent_s2_bn", "conv_fwd", 3, conv(2, 181, 181, 128, 1024, 1, 2), _BN, F256,
+         "persistent form under stride 2, shortcut epilogue: launch256_main", ["fwd256_persistent_s2", "fwd256_persistent"]),
+    case("fwd256_tail_split_s2", "conv_fwd", 3, conv(169, 14, 14, 1024, 2048, 1, 2), _BN, dict(F256, CDDMSL_TAIL_SPLIT="1"),
+         "K-split tail under stride 2 at Res5ROIHeads' 1024 -> 2048 shortcut on 14 x 14 crops (8 281 rows are 33 panels, 264 tiles on 256 "
+         "CUs, 16 K-tiles in 8 slices) + k_conv_split_reduce: plan_tail_split in launch256", ["fwd256_tail_split_s2", "fwd256_tail_split"]),
+    case("wgrad_1x1_s2", "conv_wgrad", 4, conv(4, 41, 37, 128, 192, 1, 2), wg(True, True), {},
+         "k_conv_wgrad 1x1 stride 2 with the FrozenBN scale into a non-zero dW (conv1 / shortcut of a stock block; not 'same' in plan_wgrad), "
+         "odd map: 4 x 21 x 19 rows; run_wgrad", ["wgrad_1x1_s2"]),
+    case("wgrad_1x1_s2_even", "conv_wgrad", 4, conv(4, 40, 38, 128, 192, 1, 2), wg(True, True), {},
+         "k_conv_wgrad 1x1 stride 2, even map (the last row and column are never read), plan_wgrad (not 'same')", ["wgrad_1x1_s2"]),
+    case("wgrad_1x1_s2_one_row", "conv_wgrad", 4, conv(1, 1, 37, 128, 192, 1, 2), wg(True, True), {},
+         "k_conv_wgrad 1x1 stride 2, degenerate: one image of one row, 19 output pixels (Ho == Hi, Wo != Wi: still not 'same'), plan_wgrad",
+         ["wgrad_1x1_s2"]),
+]
+
+# ---- what the stock step's record (tests/golden/stock_gemm_launches.json) holds beyond the strided convolutions
+CASES += [
+    case("nt_rpn_sparse_dx", "gemm_nt_batched", 3, dict(nt(4096, 1024, 1024, 9, 1024, 9216, 1024, None, 1024, 4194304), sa=0),
+         dict(bias=False, out_f32=True), {},
+         "the RPN head's sparse input gradient (layers.py RpnHeadFn.backward): one product per filter tap, the 4 096 gathered rows shared by "
+         "all nine (sa = 0), B the tap's 1 024 columns of rows 9 216 apart, f32 out; k_conv_fwd256, plan_fwd (use_gemm256 with the batch "
+         "count) (the stock step's 16-image launch)", ["batched_strided", "nt_shared_a"]),
+]
 REQUIRED_VARIANTS = [
     "fwd", "fwd_reg_pool", "fwd2_1x1", "fwd2_taps", "fwd256_1x1", "fwd256_taps", "fwd256_res_pool", "fwd256_persistent",
     "fwd256_tail_split", "fwd256_batched", "fwd256_res_f32", "fwd256_out_f32", "small<1,1>", "small<1,2>", "small<8,2>", "small<4,1>",
     "small<4,2>", "small<8,2,1>", "small<32,2,1>", "wgrad256_ws", "wgrad256_atomics", "wgrad_dma", "wgrad_s56", "tn_small", "tn_stream",
     "relu_mask", "dgrad_wd", "full_m", "over_2gib", "batched_strided", "fwd_f32",
+    "stem_7x7_s2", "fwd_1x1_s2", "fwd2_1x1_s2", "fwd256_1x1_s2", "fwd256_persistent_s2", "fwd256_tail_split_s2", "wgrad_1x1_s2", "nt_shared_a",
 ]
 # (kernel id, M, N, K) bench launches the issue names: each has a full-M case
 BENCH_SHAPES = [(3, 1605632, 512, 4608), (3, 401408, 2048, 512), (3, 1065600, 256, 64), (3, 66400, 1024, 9216), (11, 1065600, 128, 1152),

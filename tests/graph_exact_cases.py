@@ -1,5 +1,6 @@
 """Case table of tests/test_gpu_graph_exact.py and tests/test_graph_ref_host.py, plain data: every autograd node of
-cddmsl_amd/layers.py, branch by branch, at the smallest shapes at which the branch is still taken.
+cddmsl_amd/layers.py and the stock ResNet's stage node (cddmsl_amd/modeling/resnet.py StockStageFn, kind ``stock_stage``), branch by
+branch, at the smallest shapes at which the branch is still taken.
 
 A case: ``kind`` (which node; tests/graph_ref.py ``reference`` and the GPU test's runner dispatch on it), ``branch`` (the name in
 REQUIRED_BRANCHES it covers), ``selects`` (the condition in layers.py that takes the branch), ``why`` (what the shape is for, and
@@ -23,6 +24,11 @@ def _stage(name, branch, selects, why, seed, x=(2, 10, 12, 32), planes=16, strid
            bits="1", pooled=None):
     return _case(name, "stage", branch, selects, why, seed, {"CDDMSL_POOL_MASK_BITS": bits}, x=x, planes=planes, strides=strides,
                  x_grad=x_grad, premasked=premasked, px=px, pooled=pooled)
+
+
+def _stock(name, branch, selects, why, seed, x=(2, 10, 12, 32), planes=16, strides=(2,), x_grad=True, pool=False):
+    # (32 channels in, 16 planes, 64 out: the first block has the shortcut convolution, the others the identity, as make_stage builds them)
+    return _case(name, "stock_stage", branch, selects, why, seed, x=x, planes=planes, strides=strides, x_grad=x_grad, pool=pool)
 
 
 def _roi(commute, extra, feat_grad, bits, seed):
@@ -116,6 +122,20 @@ CASES = [
     _case("stack_halves", "halves", "halves.out_spec", "hip.conv_fwd: `out_spec.full is None` / `out_spec.used == 1`; StackHalvesFn.backward: two views",
           "two res_stage calls on the same block write the halves of one buffer", 161, {"CDDMSL_POOL_MASK_BITS": "1"}, x=(2, 10, 12, 32), planes=16, strides=(2,)),
     _case("mean_pool", "meanpool", "meanpool", "MeanPoolFn", "3 regions of 7 x 7 x 64", 162, x=(3, 7, 7, 64)),
+    # ---------------------------------------------------------------------------------------------------- StockStageFn / _blk_backward (resnet.py)
+    _stock("stock_s1_shortcut", "stock.stride1_shortcut", "_blk_backward: `if s == 1`, `blk.shortcut is not None`: dsc a dense dgrad, the residual of conv1's",
+           "res2's first block: stride 1 with a shortcut convolution, 2 x 9 x 11", 171, x=(2, 9, 11, 32), strides=(1,)),
+    _stock("stock_s1_two_blocks", "stock.identity_mask_between", "_blk_backward: `else gs` (identity), `mask = x if mask_x` (StockStageFn.backward: mask_x = i > 0)",
+           "blocks (1, 1): the second has the identity and masks its input gradient by its input, the first block's output", 172, strides=(1, 1)),
+    _stock("stock_s2_odd", "stock.stride2_odd", "_blk_backward: stride 2: `low = conv_fwd(dpre1, ..., residual=dsc)`, hip.upsample_zero2 with mask=None",
+           "9 x 11 -> 5 x 6: (H - 1) // 2 + 1 does not floor; odd rows and columns of dx are exactly zero", 173, x=(2, 9, 11, 32)),
+    _stock("stock_s2_even", "stock.stride2_even", "_blk_backward: the same, on a map whose last row and column no output pixel reads",
+           "10 x 12 -> 5 x 6: the last row and column (every odd one) of dx are exactly zero, bit for bit", 174),
+    _stock("stock_no_dx", "stock.need_dx_false", "_blk_backward: `if not need_dx: return None` (StockStageFn.backward: needs_input_grad[0])",
+           "x wants no gradient: the four weight gradients alone, stride 2", 175, x_grad=False),
+    _stock("stock_res5_crops", "stock.res5_mean_pool", "Res5ROIHeads.forward: layers.mean_pool(self.res5.forward_nhwc(x)); blocks (2, 1): upsample_zero2 below a masked block",
+           "3 crops of 14 x 14 -> 7 x 7 through a stride-2 block and an identity block, then the mean over the map", 176, x=(3, 14, 14, 32),
+           strides=(2, 1), pool=True),
 ]
 
 REQUIRED_BRANCHES = [
@@ -125,10 +145,12 @@ REQUIRED_BRANCHES = [
     "stage.pool_mask_bits_off", "roi.on_map1.extra_grad", "roi.on_map0.extra_grad", "roi.on_map1.extra_nograd", "roi.on_map0.extra_nograd",
     "roi.on_map0.extra_none", "roi.on_map1.extra_none", "attn.fused_dx_premask", "attn.unfused_premask", "attn.fused_dx_plain", "attn.unfused_plain",
     "attn.frozen_fused", "attn.frozen_unfused", "attn.trainable_no_dx", "attn.res_stage_attnpool", "halves.out_spec", "meanpool",
+    "stock.stride1_shortcut", "stock.identity_mask_between", "stock.stride2_odd", "stock.stride2_even", "stock.need_dx_false", "stock.res5_mean_pool",
 ]
 
 # the node families of the accumulation contract (two backward passes into the same .grad, f32): one case each
-ACCUMULATE = ["conv_1x1_bias_relu", "heads_4d_out_f32", "stage_two_blocks", "roi_commute1_extra_grad_feat_bits1", "attn_fused_premask", "attn_after_stage"]
+ACCUMULATE = ["conv_1x1_bias_relu", "heads_4d_out_f32", "stage_two_blocks", "roi_commute1_extra_grad_feat_bits1", "attn_fused_premask", "attn_after_stage",
+              "stock_s1_two_blocks"]
 
 
 
@@ -141,6 +163,7 @@ def _natural(name):
 
 
 CASES += [_natural(n) for n in ("conv_1x1_bias_relu", "frozen_mlp", "stage_pooled_residual", "stage_pool_fallback_odd", "stage_two_blocks",
-                                "stage_premasked", "roi_commute1_extra_grad_feat_bits1", "roi_commute0_extra_grad_feat_bits0", "attn_after_stage")]
+                                "stage_premasked", "roi_commute1_extra_grad_feat_bits1", "roi_commute0_extra_grad_feat_bits0", "attn_after_stage",
+                                    "stock_s1_two_blocks", "stock_s2_odd")]
 
 BY_NAME = {c["name"]: c for c in CASES}

@@ -27,7 +27,8 @@ F64 = torch.float64
 DROPS = ("conv_residual_grad", "conv_relu_mask", "conv_bias_grad", "block_down_path_dx", "block_pool_quarter", "block_mask_between",
          "block_o2_mask", "block_scale_in_wgrad", "block_scale_in_dgrad", "roi_down_path_dfeat", "roi_extra_in_w1_grad",
          "roi_dextra_pooled_path", "roi_bias_before_pool", "attn_mean_token_share", "attn_query_path", "attn_pos_grad_masked",
-         "attn_softmax_scale_bwd")
+         "attn_softmax_scale_bwd", "stock_shortcut_path_dx", "stock_conv1_path_dx", "stock_mask_between", "stock_scale_in_wgrad",
+         "stock_scale_in_dgrad")
 
 F32_FACTOR, F32_FLOOR, F32_CAP = 8.0, 1e-6, 1e-4
 BF16_FACTOR, BF16_FLOOR, BF16_CAP = 4.0, 2.0 ** -8, 3e-2
@@ -138,6 +139,38 @@ def stage(x, blocks, round_bf16=False, drop=None, parts=None):
     return x, pre
 
 
+def stock_block(x, w, bn, stride, round_bf16=False, drop=None, last=True):
+    """One block of the stock ResNet (cddmsl_amd/modeling/resnet.py BottleneckBlock) in the literal order: 1x1 with stride ``stride``,
+    affine, ReLU; 3x3 pad 1, affine, ReLU; 1x1, affine; plus the identity, or a 1x1 with stride ``stride`` followed by an affine; ReLU.
+    w = (w1, w2, w3, ws or None), bn = four (scale, bias).  -> (out, the pre-ReLU sum).  The drops: the shortcut path's input gradient;
+    conv1's (with the shortcut's it makes the sum a stride-2 block forms at low resolution); the ReLU mask between blocks; the
+    FrozenBN scale in conv1's weight gradient; in conv1's input gradient."""
+    rb = round_bf16
+    (s1, b1), (s2, b2), (s3, b3), bnd = bn
+    w1, w2, w3, ws = (_r(v, rb) for v in w)
+    x = _r(x, rb)
+    x1 = x.detach() if drop == "stock_conv1_path_dx" else x
+    c1 = _c(x1, w1, stride)
+    if drop == "stock_scale_in_wgrad":          # (the value of c1, the gradient of an expression whose weight term lacks the scale)
+        c1 = _grad_of(c1, _c(x1, w1.detach(), stride) + _c(x1.detach(), w1, stride) / s1)
+    elif drop == "stock_scale_in_dgrad":
+        c1 = _grad_of(c1, _c(x1.detach(), w1, stride) + _c(x1, w1.detach(), stride) / s1)
+    o1 = _r(torch.relu(_r(c1, rb) * s1 + b1), rb)
+    o2 = _r(torch.relu(_r(_c(o1, w2, pad=1), rb) * s2 + b2), rb)
+    z3 = _r(_c(o2, w3), rb) * s3 + b3
+    xs = x.detach() if drop == "stock_shortcut_path_dx" else x
+    idn = _r(_c(xs, ws, stride), rb) * bnd[0] + bnd[1] if ws is not None else xs
+    pre = z3 + idn
+    return _r(_relu(pre, drop == "stock_mask_between" and not last), rb), pre
+
+
+def stock_stage(x, blocks, pool=False, round_bf16=False, drop=None):
+    """blocks: [dict(w, bn, stride)] -> the output, mean-pooled over the map with ``pool`` (Res5ROIHeads: stage, then layers.mean_pool)"""
+    for i, b in enumerate(blocks):
+        x, _ = stock_block(x, b["w"], b["bn"], b["stride"], round_bf16, drop, i + 1 == len(blocks))
+    return mean_pool(x, round_bf16) if pool else x
+
+
 def roi_crops(feat, rois, out_size, scale, sr):
     """aligned RoIAlign of feat [N, H, W, C] from the separable float64 weight tables of tests/exact_roi.py: linear in feat, so
     autograd differentiates it.  rois [K, 5] f32, grouped by image."""
@@ -242,7 +275,7 @@ def _side_bias(z, g, masks, first_sign=1.0):
     return b, float(((flat + b).abs() / (flat.abs() + b.abs())).min())
 
 
-def _make_blocks(g, cin, planes, strides, x, masks="gated"):
+def _make_blocks(g, cin, planes, strides, x, masks="gated", stock=False):
     """Bottleneck parameters as tests/test_gpu_three_passes.py ``_blocks`` draws them (weights N(0, 1 / fan-in), scales in [0.5, 1.5)),
     the first block with a downsample convolution -> (blocks, the stage's output, the smallest margin of its ReLUs).
 
@@ -255,7 +288,8 @@ def _make_blocks(g, cin, planes, strides, x, masks="gated"):
     size of its terms), the side alternating by channel, conv2's the other way round than conv1's: half of all activations are exact
     zeros, the masks of o1, o2 and the output differ, and a mask taken from the wrong tensor or dropped moves the gradients.
     What a gated case cannot see is a mask read at the wrong PIXEL.  The "natural" cases (f32 only, where the noise is 2^-24 and
-    MARGIN["natural"] = 2^-18 is met by redrawing) keep N(0, 0.3^2) biases and masks that vary from pixel to pixel."""
+    MARGIN["natural"] = 2^-18 is met by redrawing) keep N(0, 0.3^2) biases and masks that vary from pixel to pixel.
+    ``stock``: the blocks of ``stock_block`` -- the stride in conv1 and in the shortcut convolution instead of the two AvgPool2d; same draws."""
     x = x.to(F64)
     rn = lambda *s: torch.randn(*s, generator=g)
     cw = lambda co, ci, k: _bf(rn(co, ci, k, k) * (ci * k * k) ** -0.5)
@@ -265,14 +299,14 @@ def _make_blocks(g, cin, planes, strides, x, masks="gated"):
         w = [cw(planes, cin, 1), cw(planes, planes, 3), cw(4 * planes, planes, 1), cw(4 * planes, cin, 1) if bi == 0 else None]
         s = [sc(planes), sc(planes), sc(4 * planes), sc(4 * planes) if bi == 0 else None]
         d = [None if v is None else v.to(F64) for v in w]
-        z1 = _c(x, d[0]) * s[0]
+        z1 = _c(x, d[0], stride if stock else 1) * s[0]
         b1, m1 = _side_bias(z1, g, masks)
         o1 = torch.relu(z1 + b1)
         z2 = _c(o1, d[1], pad=1) * s[1]
         b2, m2 = _side_bias(z2, g, masks, -1.0)
-        p2 = _avg(torch.relu(z2 + b2), stride)
+        p2 = _avg(torch.relu(z2 + b2), 1 if stock else stride)
         z3 = _c(p2, d[2]) * s[2]
-        idn = _c(_avg(x, stride), d[3]) * s[3] if bi == 0 else x
+        idn = (_c(x, d[3], stride) if stock else _c(_avg(x, stride), d[3])) * s[3] if bi == 0 else x
         # (the downsample path's bias: of the size of the values it is added to -- b3 below takes up its mean -- so that a bias that
         # got lost with the weight of a RoI's samples outside the map, drop "roi_bias_before_pool", shows in the output)
         bd = _bf(rn(4 * planes) * 2.0 * float((z3 + idn).std())) if bi == 0 else None
@@ -368,6 +402,10 @@ def _draw(case, g):
         both = torch.cat([inp["x"], inp["xb"]]) if k == "halves" else inp["x"]
         inp["blocks"], y, margin = _make_blocks(g, case["x"][-1], case["planes"], case["strides"], both, masks)
         inp["gy"] = _bf(rn(*y.shape))
+    elif k == "stock_stage":
+        inp["x"] = _bf(rn(*case["x"]).clamp_min(0))
+        inp["blocks"], y, margin = _make_blocks(g, case["x"][-1], case["planes"], case["strides"], inp["x"], masks, stock=True)
+        inp["gy"] = _bf(rn(y.shape[0], y.shape[-1])) if case["pool"] else _bf(rn(*y.shape))
     elif k == "roi":
         inp["feat"] = _bf(rn(*case["feat"]).clamp_min(0))
         inp["rois"] = torch.tensor(ROIS, dtype=torch.float32)
@@ -415,7 +453,7 @@ def compared(case):
         return ["y", "dx"] + [f"{n}{i}" for i in range(len(case["widths"])) for n in "wb"]
     if k == "mlp":
         return ["y", "dx", "dres"]
-    if k == "stage":
+    if k in ("stage", "stock_stage"):
         return ["y"] + ["dx"] * case["x_grad"] + blk(case["strides"])
     if k == "halves":
         return ["y", "dx", "dxb"] + blk(case["strides"])
@@ -445,6 +483,10 @@ def drops_for(case):
             d += ["roi_bias_before_pool"] + ["roi_down_path_dfeat"] * x_grad + ["roi_extra_in_w1_grad"] * (case["extra"] != "none") \
                 + ["roi_dextra_pooled_path"] * (case["extra"] == "grad")
         return d + (["attn_softmax_scale_bwd"] if k == "attn" else [])
+    if k == "stock_stage":
+        strides, x_grad = case["strides"], case["x_grad"]
+        return ["stock_scale_in_wgrad"] + ["stock_scale_in_dgrad"] * (x_grad or len(strides) > 1) + ["stock_mask_between"] * (len(strides) > 1) \
+            + ["stock_shortcut_path_dx"] * x_grad + ["stock_conv1_path_dx"] * x_grad
     if k == "attn":
         # (the query path reaches the map only through the mean token's share; where no parameter gradient is compared it is that term)
         return ["attn_softmax_scale_bwd"] + ["attn_mean_token_share"] * case["x_grad"] + ["attn_query_path"] * (case["x_grad"] and not case["frozen"]) \
@@ -502,6 +544,8 @@ def reference(case, inp, dtype=F64, round_bf16=False, drop=None):
     elif k == "stage":
         y, pre = stage(leaf("dx", inp["x"], case["x_grad"]), blocks_of(inp["blocks"]), **kw)
         target = pre if case["premasked"] else y
+    elif k == "stock_stage":
+        y = stock_stage(leaf("dx", inp["x"], case["x_grad"]), blocks_of(inp["blocks"]), case["pool"], **kw)
     elif k == "halves":
         bl = blocks_of(inp["blocks"])
         y = torch.cat([stage(leaf("dx", inp["x"]), bl, **kw)[0], stage(leaf("dxb", inp["xb"]), bl, **kw)[0]])

@@ -1,6 +1,6 @@
 """The exact-product checker itself (tests/exact_gemm.py), on the CPU: the float64 reference against ATen, the bound against an f32
 convolution in another summation order, negative controls the bound must reject -- with the verdict of the old 2e-2 * max criterion
-printed next to it -- and the coverage of the bench's recorded launches by the GPU case table."""
+printed next to it -- and the coverage of the recorded launches (the bench step's and the stock R50-C4 step's) by the GPU case table."""
 import json
 import os
 
@@ -171,9 +171,17 @@ def test_rounding_bias_separates_rne_from_truncation():
 
 
 # ------------------------------------------------------------------------------------------------ coverage of the recorded launches
+RECORDS = ("bench_gemm_launches.json", "stock_gemm_launches.json")      # the CLIP benchmark step; the stock R50-C4 configuration's step
+
+
+def _recorded(name):
+    with open(os.path.join(GOLDEN, name)) as fh:
+        return json.load(fh)["entries"]
+
+
 def test_case_table_covers_every_recorded_launch_class_in_both_tiers():
-    with open(os.path.join(GOLDEN, "bench_gemm_launches.json")) as fh:
-        rec = json.load(fh)["entries"]
+    rec = [e for record in RECORDS for e in _recorded(record)]
+    assert all(_recorded(record) for record in RECORDS)
     have = {}
     for c in CASES.CASES:
         for tier in c["tiers"]:
@@ -191,9 +199,13 @@ def test_case_table_covers_every_instantiation_and_bench_shape():
     assert not set(CASES.REQUIRED_VARIANTS) - variants, sorted(set(CASES.REQUIRED_VARIANTS) - variants)
     full = {(c["kid"]) for c in CASES.CASES if "full_m" in c.get("variants", ())}
     assert CASES.BENCH_KERNELS <= full, CASES.BENCH_KERNELS - full
-    with open(os.path.join(GOLDEN, "bench_gemm_launches.json")) as fh:
-        launched = {e["kernel_id"] for e in json.load(fh)["entries"]}
-    assert launched <= CASES.BENCH_KERNELS, launched - CASES.BENCH_KERNELS
+    for record in RECORDS:
+        launched = {e["kernel_id"] for e in _recorded(record)}
+        assert launched <= CASES.BENCH_KERNELS, (record, launched - CASES.BENCH_KERNELS)
+    # the stock step's strided launches (7x7 stem, stride-2 1x1 forward and weight gradient): each kernel that takes one has a strided case
+    strided = {(e["entry"], e["kernel_id"]) for e in _recorded("stock_gemm_launches.json") if e["geometry"].get("stride", 1) > 1}
+    assert strided == {("conv_fwd", 1), ("conv_fwd", 3), ("conv_fwd", 11), ("conv_wgrad", 4)}, strided
+    assert strided <= {(c["entry"], c["kid"]) for c in CASES.CASES if c["geom"].get("stride", 1) == 2}
     for shape in CASES.BENCH_SHAPES:
         assert any(CASES.mnk(c) == shape[1:] and c["kid"] == shape[0] and "full_m" in c["variants"] for c in CASES.CASES), shape
     big = [c for c in CASES.CASES if "over_2gib" in c.get("variants", ())]
@@ -246,11 +258,12 @@ def test_dispatch_replayed_through_the_raw_abi_in_plan_only_mode(monkeypatch):
     ge.build()
     from cddmsl_amd import hip
     L = hip._L()
-    with open(os.path.join(GOLDEN, "bench_gemm_launches.json")) as fh:
-        rec = json.load(fh)["entries"]
+    rec = _recorded("bench_gemm_launches.json")
+    stock = _recorded("stock_gemm_launches.json")
     todo = [(f"recorded launch {i}", e["entry"], e["geometry"], e["epilogue"], {}, e["kernel_id"]) for i, e in enumerate(rec)]
+    todo += [(f"recorded stock launch {i}", e["entry"], e["geometry"], e["epilogue"], {}, e["kernel_id"]) for i, e in enumerate(stock)]
     todo += [(c["id"], c["entry"], c["geom"], dict({"emit8": False}, **c["epi"]), c["env"], c["kid"]) for c in CASES.CASES]
-    assert len(rec) >= 367 and len(CASES.CASES) >= 100
+    assert len(rec) >= 367 and len(stock) >= 58 and len(CASES.CASES) >= 120
     bad = []
     was = L.cddmsl_plan_only(1)
     try:

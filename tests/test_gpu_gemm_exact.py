@@ -6,7 +6,21 @@ the 32-image geometry past 2 GiB -- in two tiers:
      (split-K, atomics, workspace reductions), so the output must equal the exact value rounded once -- torch.equal.
   B  Gaussian operands: every element inside exact_gemm.check_bound, and a bf16 store without rounding bias.
 
-Plus the launch record (tests/golden/bench_gemm_launches.json) replayed in plan-only mode: dispatch still picks the recorded kernel."""
+Plus the launch records (tests/golden/bench_gemm_launches.json, and stock_gemm_launches.json of the stock R50-C4 step) replayed in
+plan-only mode: dispatch still picks the recorded kernel.  And the stock stem as the model calls it (BasicStem.forward_nhwc).
+
+Measured on one MI355X, the strided cases of the stock ResNet path and what else its record added; tier A bit-equal in all of them,
+tier B worst |err| / bound (0.99 is a correctly rounded bf16 store of a value just above a power of two; none below 0.05, the mark of
+a loose bound -- the two lowest, the accumulating weight gradients, are dominated by the 2^-24 |dW before| term of the bound), then
+the bf16 store's rounding bias in ulp or, for f32 outputs, the accumulation ratio C_ACC = 8 must cover:
+  stem_7x7_s2_bf16 0.993 -0.0004         stem_7x7_s2_bf16_even 0.992 -0.0027     stem_7x7_s2_f32 0.467 acc 3.18
+  stem_7x7_s2_f32_even 0.445 acc 3.06    fwd_1x1_s2_bn_relu 0.986 -0.0064        fwd_1x1_s2_bn 0.990 -0.0002
+  fwd_1x1_s2_bn_relu_even 0.993 -0.0016  fwd_1x1_s2_bn_even 0.995 -0.0000        fwd2_1x1_s2_bn_relu 0.994 +0.0017
+  fwd2_1x1_s2_bn_even 0.995 -0.0001      fwd256_1x1_s2_bn_relu 0.992 +0.0006     fwd256_1x1_s2_bn_even 0.995 -0.0001
+  fwd256_roi_crops_s2 0.995 -0.0001      fwd256_persistent_s2 0.996 -0.0003      fwd256_persistent_s2_bn 0.996 -0.0002
+  fwd256_tail_split_s2 0.995 -0.0003     wgrad_1x1_s2 0.055 acc 0.43             wgrad_1x1_s2_even 0.068 acc 0.43
+  wgrad_1x1_s2_one_row 0.244 acc 0.43    nt_rpn_sparse_dx 0.283 acc 2.03
+  test_stock_stem_against_float64, worst |err| / limit: f32 0.470 (37 x 53), 0.589 (38 x 54); bf16 0.992, 0.986"""
 import json
 import os
 
@@ -308,13 +322,11 @@ def _plan(entry, g, epi):
     return _kid()
 
 
-def test_recorded_bench_launches_keep_their_kernels(monkeypatch, golden_dir, capsys):
-    """every distinct GEMM launch of the bench step (16 and 32 images) still dispatches to the kernel recorded for it; a change of
-    dispatch must re-record tests/golden/bench_gemm_launches.json (tools/record_gemm_launches.py) -- and the case table follows"""
+def _replay(monkeypatch, golden_dir, capsys, record):
     from cddmsl_amd import hip
     hip.ensure_workspace(DEV)
     _set_env(monkeypatch, {})
-    with open(os.path.join(golden_dir, "bench_gemm_launches.json")) as fh:
+    with open(os.path.join(golden_dir, record)) as fh:
         rec = json.load(fh)["entries"]
     bad = []
     for e in rec:
@@ -323,5 +335,69 @@ def test_recorded_bench_launches_keep_their_kernels(monkeypatch, golden_dir, cap
             bad.append((e["images"], e["entry"], e["geometry"], e["epilogue"], e["kernel_id"], kid))
         torch.cuda.empty_cache()
     with capsys.disabled():
-        print(f"\n{len(rec)} recorded launches replayed in plan-only mode, {len(bad)} changed kernel")
-    assert not bad, bad
+        print(f"\n{record}: {len(rec)} recorded launches replayed in plan-only mode, {len(bad)} changed kernel")
+    assert rec and not bad, bad
+
+
+def test_recorded_bench_launches_keep_their_kernels(monkeypatch, golden_dir, capsys):
+    """every distinct GEMM launch of the bench step (16 and 32 images) still dispatches to the kernel recorded for it; a change of
+    dispatch must re-record tests/golden/bench_gemm_launches.json (tools/record_gemm_launches.py) -- and the case table follows"""
+    _replay(monkeypatch, golden_dir, capsys, "bench_gemm_launches.json")
+
+
+def test_recorded_stock_launches_keep_their_kernels(monkeypatch, golden_dir, capsys):
+    """the same for the stock R50-C4 configuration's step (16 images; tests/golden/stock_gemm_launches.json, recorded with
+    tools/record_gemm_launches.py --stock): the 7x7 stem, the stride-2 1x1 convolutions and their weight gradients among them"""
+    _replay(monkeypatch, golden_dir, capsys, "stock_gemm_launches.json")
+
+
+# ------------------------------------------------------------------------------------------------ the stock stem, as the model calls it
+@pytest.mark.parametrize("H,W", [(37, 53), (38, 54)])
+@pytest.mark.parametrize("tname", ["f32", "bf16"])
+def test_stock_stem_against_float64(tname, H, W, capsys):
+    """BasicStem.forward_nhwc (7x7 stride 2 pad 3 on k_conv_fwd, FrozenBN, ReLU, then hip.maxpool3s2_fwd) on 2 x H x W pixels padded
+    to one 16-byte chunk, the padding channels holding garbage (the stem's padded weights are zero there), non-trivial FrozenBN
+    buffers -- against F.conv2d on the 3 real channels in float64, the folded affine, ReLU and F.max_pool2d(3, 2, 1).
+
+    Limit, per pooled element: the largest exact_gemm.bound of the convolution outputs in its 3 x 3 window.  Reasoning, as in
+    tests/test_gpu_fused_bottleneck.py test_against_float64_chain: the chain has ONE rounded layer.  A stored convolution output
+    differs from the exact relu(scale * sum + bias) by at most the bound of the exact-product cases above (accumulation: C_ACC * 2^-24
+    * |scale| * sum|a*b|, plus 2^-24 |bias|, plus one rounding of the output, u_out * |exact|; ReLU does not increase a difference);
+    the pooling kernel selects one of the stored values and rounds nothing, and |max a_i - max b_i| <= max |a_i - b_i|."""
+    import torch.nn.functional as F
+    from cddmsl_amd.modeling import resnet
+    T = {"f32": torch.float32, "bf16": torch.bfloat16}[tname]
+    cp = 16 // torch.empty((), dtype=T).element_size()
+    gen = _gen(4100 + H + (T == torch.bfloat16))
+    stem = resnet.BasicStem(3, 64).to(DEV)
+    w = torch.randn(64, 3, 7, 7, device=DEV, generator=gen) * 147 ** -0.5
+    stem.conv1.weight.data.copy_(w.to(T).float())                  # (values the compute dtype holds: weight_prep rounds nothing)
+    n = stem.conv1.norm
+    for buf, v in (("weight", torch.rand(64, device=DEV, generator=gen) + 0.5), ("bias", torch.randn(64, device=DEV, generator=gen) * 0.3),
+                   ("running_mean", torch.randn(64, device=DEV, generator=gen) * 0.3), ("running_var", torch.rand(64, device=DEV, generator=gen) + 0.5)):
+        getattr(n, buf).copy_(v)
+    x = _gauss((2, H, W, cp), gen, T)
+    x[..., 3:] = _gauss((2, H, W, cp - 3), gen, T, 100.0)           # garbage where the model writes zeros
+    assert float(x[..., 3:].abs().min()) > 0
+    with torch.no_grad():
+        got = stem.forward_nhwc(x)
+    assert _kid() == 1, _kid()
+    torch.cuda.synchronize()
+    scale, bias = (X._f64(v) for v in n.affine())
+    xr, wr = X._f64(x[..., :3]).permute(0, 3, 1, 2), X._f64(stem.conv1.weight.detach())
+    acc = F.conv2d(xr, wr, stride=2, padding=3)
+    absp = F.conv2d(xr.abs(), wr.abs(), stride=2, padding=3)
+    sc, bi = scale.view(1, -1, 1, 1), bias.view(1, -1, 1, 1)
+    exact = (acc * sc + bi).clamp_min(0)
+    b = X.bound(exact, absp, T, sc, bi.expand_as(exact))
+    ref = F.max_pool2d(exact, 3, 2, 1).permute(0, 2, 3, 1)
+    lim = F.max_pool2d(b, 3, 2, 1).permute(0, 2, 3, 1)
+    Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    assert got.dtype == T and tuple(got.shape) == tuple(ref.shape) == (2, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1, 64)
+    err = (X._f64(got) - ref).abs()
+    ratio = float((err / lim).max())
+    with capsys.disabled():
+        print(f"\n[stock stem {tname} 2 x {H} x {W}] kernel 1 + maxpool3s2: worst |err| / limit {ratio:.3g}, elements {got.numel()}, "
+              f"non-zero {int((ref > 0).sum())}")
+    assert int((ref > 0).sum()) > got.numel() // 2
+    assert bool((err <= lim).all()), ratio

@@ -1,5 +1,6 @@
-"""GPU: every hand-written autograd node of cddmsl_amd/layers.py, branch by branch (tests/graph_exact_cases.py), against float64
-autograd of the plainly written module (tests/graph_ref.py) on the same bf16-valued inputs, in f32 and in bf16.
+"""GPU: every hand-written autograd node of cddmsl_amd/layers.py and the stock ResNet's stage node (cddmsl_amd/modeling/resnet.py
+StockStageFn), branch by branch (tests/graph_exact_cases.py), against float64 autograd of the plainly written module
+(tests/graph_ref.py) on the same bf16-valued inputs, in f32 and in bf16.
 
 Metric per tensor: max |got - ref| / max |ref|.  Limits come from the plain module alone (graph_ref.prepared): f32 -- 8 times the
 error of the plain module run in float32 on the CPU, floor 1e-6; bf16 -- 4 times the error of the plain module with every
@@ -8,7 +9,19 @@ each single dropped term of a backward pass moves some compared tensor by ten ti
 
 Routes are confirmed where a case names one: profiler rows (hip.PROFILE) for the sliced input gradient, the fused pooled residual
 against its avgpool2_bwd fallback and the given pooled map; ``ctx`` fields for the attention pool's fused input gradient, the RoI
-stage's ``on_map`` and the mask bits a pooled block keeps."""
+stage's ``on_map`` and the mask bits a pooled block keeps; the type and the saved tensors of the stock stage's node.
+
+Measured on one MI355X, the ``stock_stage`` cases: worst error / limit over the compared tensors (the tensor), f32 then bf16.
+  stock_s1_shortcut     0.179 (b0.w1)  0.366 (y)        stock_s1_two_blocks   0.302 (b0.w3)  0.265 (dx)
+  stock_s2_odd          0.222 (b0.w1)  0.275 (y)        stock_s2_even         0.216 (b0.w2)  0.467 (dx)
+  stock_no_dx           0.221 (b0.w0)  0.317 (y)        stock_res5_crops      0.308 (b0.w2)  0.321 (dx)
+  stock_s1_two_blocks_natural 0.338 (b1.w2)             stock_s2_odd_natural  0.184 (b0.w2)
+Below 0.05, the mark of a loose limit: the shortcut's weight gradient of a ONE-block case in bf16 (b0.w3: 1e-7 against a limit of
+1e-2, as in f32).  Its operands are the stage's input and the incoming gradient masked by the output's sign -- bf16 values given, no
+rounded intermediate, and the node hands the FrozenBN scale to the weight-gradient kernel, which applies it in f32 -- so the node's
+result is as good as f32, while the rounded model rounds the scaled gradient to bf16 in front of the convolution's backward pass.
+The same tensor is held at 0.15 to 0.23 where a second block follows (two_blocks, res5_crops).  stock_res5_crops y in bf16 sits
+at 0.050: the mean over 49 pixels averages the roundings out, and the node rounds at fewer places than the model."""
 import pytest
 import torch
 
@@ -44,6 +57,44 @@ def _blocks(spec, params, prefix=""):
             if v is not None:
                 params[f"{prefix}b{bi}.w{wi}"] = v
     return out
+
+
+def _stock_stage(spec, case, params):
+    """graph_ref's block dicts -> resnet.Stage of BottleneckBlocks built directly.  The FrozenBN buffers are not the trivial ones: running
+    statistics drawn from the case's seed, weight and bias chosen so that the fold gives the case's (scale, bias) -- exactly, since the
+    reference keeps the case's own numbers: running_var + eps is 1/4, 1 or 4 in f32 (its rsqrt is exact), running_mean a multiple of 1/8,
+    so every step of ``affine()`` is exact in f32.  Checked here, bit for bit."""
+    from cddmsl_amd.modeling import resnet
+    g = torch.Generator().manual_seed(case["seed"] + 7)
+    cin, planes = case["x"][-1], case["planes"]
+    blocks = []
+    for bi, b in enumerate(spec):
+        blk = resnet.BottleneckBlock(cin, 4 * planes, planes, b["stride"]).to(DEV)
+        assert (blk.shortcut is not None) == (b["w"][3] is not None)
+        for wi, m in enumerate((blk.conv1, blk.conv2, blk.conv3, blk.shortcut)):
+            if m is None:
+                continue
+            m.weight.data.copy_(b["w"][wi].to(DEV))
+            assert m.weight.requires_grad and m.weight.permute(0, 2, 3, 1).is_contiguous()
+            params[f"b{bi}.w{wi}"] = m.weight
+            sc, bias = (v.float() for v in b["bn"][wi])
+            n, eps = sc.numel(), m.norm.eps
+            p4 = torch.pow(4.0, torch.randint(-1, 2, (n,), generator=g).float())
+            var = p4 - eps
+            for _ in range(4):          # (the f32 number next to p4 - eps whose f32 sum with eps is p4 itself)
+                d = (var + eps) - p4
+                var = torch.where(d > 0, torch.nextafter(var, -p4), torch.where(d < 0, torch.nextafter(var, 2 * p4), var))
+            assert torch.equal(var + eps, p4)
+            mean = torch.randint(-8, 9, (n,), generator=g).float() / 8
+            beta = bias + mean * sc
+            assert torch.equal((beta.double() - mean.double() * sc.double()).float(), bias) and torch.equal(beta.double(), bias.double() + mean.double() * sc.double())
+            for name, v in (("weight", sc * p4.sqrt()), ("bias", beta), ("running_mean", mean), ("running_var", var)):
+                getattr(m.norm, name).copy_(v.to(DEV))
+            fs, fb = (v.cpu() for v in m.norm.affine())
+            assert torch.equal(fs, sc) and torch.equal(fb, bias), "the FrozenBN fold does not return the case's scale and bias"
+        blocks.append(blk)
+        cin = 4 * planes
+    return resnet.Stage(*blocks).train()
 
 
 def _attn_params(inp, case, params):
@@ -115,6 +166,15 @@ def _run_node(case, inp, T, passes, k, data, params, leaves, notes):
                     x._pooled2 = torch.full((N, H // 2 + 1, W // 2, C), float("nan"), device=DEV, dtype=T)
             y = layers.res_stage(leaves["dx"], blocks, False, out_grad_premasked=case["premasked"])
             notes["saved_o2"] = y.grad_fn.saved_tensors[2].dtype
+        elif k == "stock_stage":
+            if not leaves:
+                leaves["dx"] = data("x", case["x_grad"])
+                stock = _stock_stage(inp["blocks"], case, params)
+            y = stock.forward_nhwc(leaves["dx"])
+            notes["stock_node"] = (type(y.grad_fn).__name__, len(y.grad_fn.saved_tensors))
+            assert y.dtype == T
+            if case["pool"]:
+                y = layers.mean_pool(y)
         elif k == "halves":
             if not leaves:
                 leaves["dx"], leaves["dxb"] = data("x", True), data("xb", True)
@@ -166,6 +226,12 @@ def _run_node(case, inp, T, passes, k, data, params, leaves, notes):
         out[n] = t.grad
     for t in notes.get("unused", []):
         assert t.grad is None, "a frozen parameter received a gradient"
+    if k == "stock_stage" and case["x_grad"] and case["strides"][0] == 2:
+        # a stride-2 1x1 reads the even pixels alone: every odd row and column of dx (on an even map the last ones) is exactly zero
+        dx = out["dx"]
+        assert float(dx[:, 1::2].abs().max()) == 0.0 and float(dx[:, :, 1::2].abs().max()) == 0.0, "dx of an unread pixel is not exactly zero"
+        if case["x"][1] % 2 == 0:
+            assert not bool(dx[:, -1].any()) and not bool(dx[:, :, -1].any()), "the last row / column of dx is not exactly zero"
     return out, params, notes
 
 
@@ -190,6 +256,8 @@ def _check_route(case, tname, notes):
         assert notes["saved_o2"] == (torch.int32 if bits else DT[tname]), notes["saved_o2"]
     if k == "attn":
         assert notes["fused_dx"] == (case["fused"] and bf), notes["fused_dx"]
+    if k == "stock_stage":      # the hand-written node (not a frozen stage's plain forward): it saved x and (o1, o2, out) of every block
+        assert notes["stock_node"] == ("StockStageFnBackward", 1 + 3 * len(case["strides"])), notes["stock_node"]
 
 
 _results = {}

@@ -4,10 +4,14 @@ tools/shape_profile.py): a recording shim around ``hip.conv_fwd``, ``hip.conv_wg
 ``hip.gemm_tn_batched`` notes each call's entry point, full geometry, epilogue flags and the kernel the library picked
 (``cddmsl_last_kernel``).  Writes tests/golden/bench_gemm_launches.json, which tests/test_gpu_gemm_exact.py replays in plan-only mode
 (dispatch still picks the recorded kernel) and tests/test_exact_bound_host.py checks against the exact-product case table.
-A change of dispatch or of the step's shapes must re-record it.  usage: python tools/record_gemm_launches.py [--batches 16 32] [--out F]
+A change of dispatch or of the step's shapes must re-record it.  usage: python tools/record_gemm_launches.py [--stock] [--batches 16 32] [--out F]
 With ``--dtype fp8`` the shim also notes ``hip.conv_fwd_fp8``, ``hip.conv_wgrad_fp8`` and ``hip.fp8_dot_nt``, keeps only those and the
 ``hip.conv_fwd`` calls that write an e4m3 second output (``emit8``), and writes tests/golden/bench_fp8_launches.json (the case table of
-tests/fp8_exact_cases.py is checked against it by tests/test_fp8_bound_host.py); the bf16 file is not touched."""
+tests/fp8_exact_cases.py is checked against it by tests/test_fp8_bound_host.py); the bf16 file is not touched.
+With ``--stock`` the step is the stock configuration's instead (configs/PascalVOC-Detection/faster_rcnn_R_50_C4.yaml: Detectron2's
+R50-C4 of cddmsl_amd/modeling/resnet.py -- the 7x7 stem, the stride in a block's first 1x1 -- with Res5ROIHeads; one supervised forward
+and backward pass of the model in bf16 on the same 800x1333 images, 16 of them unless --batches says otherwise) and the file
+tests/golden/stock_gemm_launches.json, same format, read by the same tests."""
 import argparse
 import json
 import os
@@ -19,6 +23,8 @@ import torch  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "bench_gemm_launches.json")
 OUT_FP8 = os.path.join(ROOT, "tests", "golden", "bench_fp8_launches.json")
+OUT_STOCK = os.path.join(ROOT, "tests", "golden", "stock_gemm_launches.json")
+STOCK_YAML = os.path.join(ROOT, "configs", "PascalVOC-Detection", "faster_rcnn_R_50_C4.yaml")
 
 
 def _dt(t):
@@ -123,19 +129,12 @@ class Recorder:
         return locals()[name]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, nargs="+", default=[16, 32])
-    ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    fp8 = args.dtype == "fp8"
-    args.out = args.out or (OUT_FP8 if fp8 else OUT)
+def record_bench(rec, batches, dtype):
+    """one bench-shaped training step per batch size, the second one recorded"""
     import bench
-    from cddmsl_amd import engine, hip, synthetic
-    rec = Recorder(hip)
-    for batch in args.batches:
-        cfg = bench.make_cfg(args.dtype)
+    from cddmsl_amd import engine, synthetic
+    for batch in batches:
+        cfg = bench.make_cfg(dtype)
         cfg.MODEL.DEVICE = "cuda:0"
         tr = engine.build_trainer(cfg, batch, 800, 1333)
         tr.model.load_state_dict(synthetic.make_state_dict(0), strict=False)
@@ -149,12 +148,55 @@ def main():
         rec.on = False
         del tr
         torch.cuda.empty_cache()
+
+
+def record_stock(rec, batches):
+    """one supervised step (forward + backward of the model) of the stock configuration per batch size, the second one recorded"""
+    from cddmsl_amd import synthetic
+    from cddmsl_amd.config import get_cfg
+    from cddmsl_amd.modeling import build_model
+    for batch in batches:
+        cfg = get_cfg()
+        cfg.merge_from_file(STOCK_YAML)
+        cfg.merge_from_list(["MODEL.COMPUTE_DTYPE", "bf16", "MODEL.DEVICE", "cuda:0"])
+        model = build_model(cfg)
+        model.load_state_dict(synthetic.make_state_dict_r50(0), strict=False)
+        model.train()
+        for it in range(2):
+            rec.batch, rec.on = batch, it == 1           # (first step: lazy weight copies and buffers)
+            model.zero_grad(set_to_none=True)
+            sum(model(synthetic.make_batch(batch, 800, 1333, iteration=it)).values()).backward()
+            torch.cuda.synchronize()
+        rec.on = False
+        del model
+        torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=None)
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--stock", action="store_true", help="record the stock R50-C4 configuration's step (bf16) instead of the bench's")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    fp8 = args.dtype == "fp8"
+    assert not (args.stock and fp8), "--stock records the bf16 step"
+    args.batches = args.batches or ([16] if args.stock else [16, 32])
+    args.out = args.out or (OUT_STOCK if args.stock else OUT_FP8 if fp8 else OUT)
+    from cddmsl_amd import hip
+    rec = Recorder(hip)
+    if args.stock:
+        record_stock(rec, args.batches)
+    else:
+        record_bench(rec, args.batches, args.dtype)
     rec.restore()
     calls = [d for d in rec.calls.values() if not fp8 or d["geometry"]["dtype"] == "e4m3" or d["epilogue"].get("emit8")]
     entries = sorted(calls, key=lambda d: (d["images"], d["entry"], d["kernel_id"], json.dumps(d["geometry"], sort_keys=True),
                                                         json.dumps(d["epilogue"], sort_keys=True)))
-    doc = {"about": "distinct GEMM / convolution launches of one bench-shaped training step (tools/record_gemm_launches.py)",
-           "dtype": args.dtype, "images": args.batches, "entries": entries}
+    about = "distinct GEMM / convolution launches of one bench-shaped training step (tools/record_gemm_launches.py)"
+    if args.stock:
+        about = "distinct GEMM / convolution launches of one supervised step of the stock R50-C4 configuration (tools/record_gemm_launches.py --stock)"
+    doc = {"about": about, "dtype": args.dtype, "images": args.batches, "entries": entries}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         json.dump(doc, fh, indent=1, sort_keys=True)
