@@ -6,6 +6,10 @@ held to the float64 product of the operands it was given -- not to another libra
   |got - exact| <= u_out * |exact| + C_ACC * 2^-24 * |scale| * sum|a*b| + 2^-24 * (|bias| + |residual| + |dW before|)
 
 u_out is the unit roundoff of the stored output (2^-8 bf16, 2^-24 f32).  Everything here runs on the CPU or on the GPU, in float64.
+
+The f32 instantiations of the same kernels (Mma<float>: 32x32x2f32 steps) are held to the same bound: their products are rounded to
+f32 as well, one more 2^-24 |a*b| each, which C_ACC covers (figures below).  Small-integer operands stay exact in f32, so tier A of
+tests/test_gpu_gemm_exact.py asks of them what it asks of bf16: the exact value, rounded once.
 """
 import math
 
@@ -20,7 +24,13 @@ U_BF16 = 2.0 ** -8
 # (k_conv_fwd, the attention pool's per-region product at 16384 regions) and 1.30 (k_conv_wgrad, stride 56, M = 8192); the
 # weight-gradient reductions through the workspace stay below 0.9.  The bf16 MFMA chains thus accumulate like plain f32 sums --
 # nowhere near the 64 that would call for probing the instruction's internal accumulation.  ATen's CPU f32 convolution
-# (tests/test_exact_bound_host.py, K = 576) measures 2.4.  8 keeps a margin of 2.3x over the worst case measured.
+# (tests/test_exact_bound_host.py, K = 576) measures 2.4.  8 keeps a margin of 2.3x over the worst of these.
+# The f32-operand cases (f32_*: every f32 instantiation, products rounded to f32 as well), worst per kernel: k_conv_fwd<float> 5.52
+# (the RPN head's shared-A batched product, K = 1024, the maximum over 2.4 M outputs), k_conv_fwd256<float> 5.01 (K = 64 on 2.2 M
+# outputs), k_conv3x3_small<float> 4.91, k_conv_fwd2<float> 4.25, k_conv_wgrad_dma<float> 4.27, k_conv_fwd_reg<float> 3.58,
+# k_gemm_tn_stream<float> 3.55, k_conv_wgrad<float> 2.46.  ATen's CPU f32 convolution of f32 operands measures 4.07 at K = 288
+# on 0.2 M outputs (the same file), so this is what a plain f32 sum of rounded products gives; none exceeds 8 (margin 1.45x), and the
+# bf16 constant stays as it is.  Should an f32 case pass 8 with its tier A twin bit-equal, it gets a constant of its own.
 C_ACC = 8.0
 
 

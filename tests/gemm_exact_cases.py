@@ -1,6 +1,7 @@
 """Case table of tests/test_gpu_gemm_exact.py, plain data (the host test imports it to check that every launch recorded in
 tests/golden/bench_gemm_launches.json -- the CLIP benchmark step -- and in tests/golden/stock_gemm_launches.json -- the stock R50-C4
-configuration's step -- and every kernel instantiation has a Tier A and a Tier B case).
+configuration's step --, in their f32 twins bench_gemm_launches_f32.json and stock_gemm_launches_f32.json -- the same steps in f32 on one
+image -- and every kernel instantiation, bf16 and f32, has a Tier A and a Tier B case).
 
 A case: entry point, the kernel id dispatch must pick (cddmsl_last_kernel; hip.py _CONV_KERNEL), the per-call switches that force
 it, the geometry (the keys tools/record_gemm_launches.py writes), the epilogue flags, the tiers it runs in, the variants it covers
@@ -283,12 +284,212 @@ CASES += [
          "all nine (sa = 0), B the tap's 1 024 columns of rows 9 216 apart, f32 out; k_conv_fwd256, plan_fwd (use_gemm256 with the batch "
          "count) (the stock step's 16-image launch)", ["batched_strided", "nt_shared_a"]),
 ]
+N_BF16_TABLE = len(CASES)          # the cases above keep their place: a case's seed is its index (tests/test_gpu_gemm_exact.py)
+
+# ================================================================================================ f32 operands
+# The f32 instantiations are their own index math -- 4 elements per 16-byte chunk, a 32-element K-tile, Mma<float>'s k-to-lane layout
+# (four 32x32x2f32 steps per chunk), TrFrag<float> / TrFragS<float> in the weight gradient, 64x64 weight-gradient tiles that only ever
+# finish with atomics, b32 mask loads and stores in the epilogues -- and every oracle-parity step runs on them.  One case per
+# instantiation and epilogue set, each at the smallest shape that still has a ragged last tile in M and N, a reduction that ends
+# inside a K-tile where the kernel allows one (Cin 36 = 9 chunks, a K-tile holds 8) and, for the strided cases, an image boundary
+# inside a tile.  Residuals and masks of an f32 launch are f32; its output is f32 without the out_f32 flag.
+# tests/golden/bench_gemm_launches_f32.json and stock_gemm_launches_f32.json record which classes the f32 steps launch.
+
+
+def conv32(*a, **k):
+    return dict(conv(*a, **k), dtype="f32")
+
+
+_F32_SETS = {k: dict(_FWD_SETS_1X1[k], residual="f32" if _FWD_SETS_1X1[k]["residual"] else None)
+             for k in ("plain", "bn", "bn_relu", "bias_relu", "bn_res_relu", "res", "mask", "mask_res")}
+_BN32, _BN_RELU32, _MASK32 = _F32_SETS["bn"], _F32_SETS["bn_relu"], _F32_SETS["mask"]
+
+
+def _tags(k, *base):
+    return list(base) + (["relu_mask_f32"] if "mask" in k else [])
+
+
+# ---- k_conv_fwd<float> (id 1), plan_fwd's default
+for k, e in _F32_SETS.items():
+    CASES.append(case(f"f32_fwd_1x1_{k}", "conv_fwd", 1, conv32(2, 9, 37, 36, 136), e, F128,
+                      "k_conv_fwd<float> 1x1, 666 x 136 outputs, K = 36 is 9 chunks: the second K-tile holds one; plan_fwd's default",
+                      _tags(k, "fwd_f32", "fwd_f32_ragged_k")))
+CASES += [
+    case("f32_fwd_3x3_bn_relu", "conv_fwd", 1, conv32(2, 9, 13, 32, 96, 3, 1, 1), _BN_RELU32, F128,
+         "k_conv_fwd<float> taps: 32 channels are one K-tile per tap, plan_fwd's default", ["fwd_f32_taps"]),
+    case("f32_fwd_3x3_mask", "conv_fwd", 1, conv32(2, 9, 13, 32, 96, 3, 1, 1), _MASK32, F128,
+         "k_conv_fwd<float> taps, ReLU-mask input gradient (b32 mask loads), plan_fwd's default", ["fwd_f32_taps", "relu_mask_f32"]),
+    case("f32_fwd_1x1_s2_bn_relu", "conv_fwd", 1, conv32(2, 9, 37, 32, 136, 1, 2), _BN_RELU32, F128,
+         "k_conv_fwd<float> 1x1 stride 2 (conv1 of a stock block): 190 rows are two tiles, the image boundary inside the first; plan_fwd's default",
+         ["fwd_1x1_s2_f32"]),
+    case("f32_fwd_1x1_s2_bn", "conv_fwd", 1, conv32(2, 9, 37, 32, 136, 1, 2), _BN32, F128,
+         "k_conv_fwd<float> 1x1 stride 2, the shortcut's epilogue, plan_fwd's default", ["fwd_1x1_s2_f32"]),
+    case("f32_fwd_1x1_s2_bn_relu_even", "conv_fwd", 1, conv32(2, 10, 38, 32, 136, 1, 2), _BN_RELU32, F128,
+         "k_conv_fwd<float> 1x1 stride 2 on an even map: the last row and column are never read; plan_fwd's default", ["fwd_1x1_s2_f32"]),
+    case("f32_fwd_1x1_s2_bn_even", "conv_fwd", 1, conv32(2, 10, 38, 32, 136, 1, 2), _BN32, F128,
+         "k_conv_fwd<float> 1x1 stride 2, shortcut epilogue, even map; plan_fwd's default", ["fwd_1x1_s2_f32"]),
+    case("f32_fwd_s56_bias", "conv_fwd", 1, conv32(37, 1, 56, 64, 136, 1, 56), fwd(bias=True), F128,
+         "k_conv_fwd<float>, the attention pool's strided query projection (one row of every 56), plan_fwd's default", ["fwd_f32_s56"]),
+    case("f32_fwd_1x1_64_not_small", "conv_fwd", 1, conv32(2, 37, 53, 32, 64), _BN_RELU32, {},
+         "k_conv_fwd<float>: plan_fwd's one-tap branch to k_conv3x3_small is bf16 only (op == OP_BF16), so the f32 1x1 with 64 outputs "
+         "stays on plan_fwd's default -- a change of that rule shows here", ["fwd_f32_one_tap_rule"]),
+    # ---- k_conv_fwd_reg<float> (id 2)
+    case("f32_fwd_reg_pool", "conv_fwd", 2, conv32(2, 15, 21, 32, 160, pool=True), _F32_SETS["plain"], F128,
+         "k_conv_fwd_reg<float>: AvgPool2d(2) fused into the loader, odd sizes floor, plan_fwd (pool)", ["fwd_reg_pool_f32"]),
+    case("f32_fwd_reg_pool_bn_relu", "conv_fwd", 2, conv32(3, 14, 14, 64, 256, pool=True), _BN_RELU32, {},
+         "k_conv_fwd_reg<float> (pool is never legal on the 256 kernels: gemm256_legal), plan_fwd (pool)", ["fwd_reg_pool_f32"]),
+]
+# ---- k_conv_fwd256<float, TAPS, false, -1> (id 3): use_gemm256 in plan_fwd; launch256 gives f32 operands EPI -1
+for k, e in _F32_SETS.items():
+    CASES.append(case(f"f32_fwd256_1x1_{k}", "conv_fwd", 3, conv32(2, 19, 23, 64, 512), e, F256,
+                      "k_conv_fwd256<float, false, false, -1>: 874 rows are four row panels, the last ragged; two K-tiles; launch256_main",
+                      _tags(k, "fwd256_1x1_f32")))
+CASES += [
+    case("f32_fwd256_3x3_bn_relu", "conv_fwd", 3, conv32(2, 19, 23, 32, 256, 3, 1, 1), _BN_RELU32, F256,
+         "k_conv_fwd256<float, true, false, -1>, launch256_main", ["fwd256_taps_f32"]),
+    case("f32_fwd256_3x3_mask", "conv_fwd", 3, conv32(2, 19, 23, 32, 256, 3, 1, 1), _MASK32, F256,
+         "k_conv_fwd256<float, true, false, -1>, ReLU-mask input gradient, launch256_main", ["fwd256_taps_f32", "relu_mask_f32"]),
+    case("f32_fwd256_1x1_s2_bn_relu", "conv_fwd", 3, conv32(3, 19, 23, 64, 512, 1, 2), _BN_RELU32, F256,
+         "k_conv_fwd256<float, false, false, -1> 1x1 stride 2: 360 rows are two row panels, image boundaries inside the first; launch256_main",
+         ["fwd256_1x1_s2_f32"]),
+    case("f32_fwd256_1x1_s2_bn_even", "conv_fwd", 3, conv32(3, 20, 24, 64, 512, 1, 2), _BN32, F256,
+         "k_conv_fwd256<float> 1x1 stride 2, shortcut epilogue, even map; launch256_main", ["fwd256_1x1_s2_f32"]),
+    case("f32_fwd256_res_pool", "conv_fwd", 3, conv32(3, 15, 21, 64, 256), fwd(residual="pooled"), F256,
+         "k_conv_fwd256<float, false, true>: AvgPool2d(2)-backward residual (f32), odd sizes, launch_fwd (res_pool)", ["fwd256_res_pool_f32"]),
+    case("f32_fwd256_res_pool_mask", "conv_fwd", 3, conv32(3, 15, 21, 64, 256), fwd(residual="pooled", relu_mask=True), F256,
+         "k_conv_fwd256<float, false, true> with the ReLU mask, launch_fwd (res_pool)", ["fwd256_res_pool_f32", "relu_mask_f32"]),
+]
+# ---- k_conv_fwd2<float, TAPS, -1> (id 11): use_fwd2 in plan_fwd; launch_fwd2
+for k in ("plain", "bn_relu", "mask"):
+    CASES.append(case(f"f32_fwd2_1x1_{k}", "conv_fwd", 11, conv32(2, 19, 23, 48, 384), _F32_SETS[k], FWD2,
+                      "k_conv_fwd2<float, false, -1>: K = 48 is 12 chunks, three K-tiles of 4; launch_fwd2", _tags(k, "fwd2_1x1_f32")))
+for k in ("bn_relu", "mask"):
+    CASES.append(case(f"f32_fwd2_3x3_{k}", "conv_fwd", 11, conv32(2, 19, 23, 16, 128, 3, 1, 1), _F32_SETS[k], FWD2,
+                      "k_conv_fwd2<float, true, -1>: one K-tile per tap, launch_fwd2", _tags(k, "fwd2_taps_f32")))
+CASES.append(case("f32_fwd2_1x1_s2_bn", "conv_fwd", 11, conv32(3, 19, 23, 48, 384, 1, 2), _BN32, FWD2,
+                  "k_conv_fwd2<float, false, -1> 1x1 stride 2: 360 rows are two row tiles, two image boundaries inside the first; launch_fwd2",
+                  ["fwd2_1x1_s2_f32"]))
+# ---- k_conv3x3_small<float, CPP, NB> (id 8): plan_fwd's 3x3 branch (its one-tap branch is bf16 only: f32_fwd_1x1_64_not_small above);
+# launch_small picks the instantiation by chunks per pixel / Cout.  A chunk is 4 f32 channels: <4,.> is 16 channels, <8,2> is 32.
+CASES += [
+    case("f32_small_1_1", "conv_fwd", 8, conv32(2, 37, 53, 4, 32, 3, 2, 1), _BN_RELU32, {},
+         "k_conv3x3_small<float, 1, 1>: one chunk per pixel, 32 outputs, stride 2, launch_small", ["small_f32<1,1>"]),
+    case("f32_small_1_2", "conv_fwd", 8, conv32(1, 40, 61, 4, 64, 3, 1, 1), _BN_RELU32, {},
+         "k_conv3x3_small<float, 1, 2>, launch_small", ["small_f32<1,2>"]),
+    case("f32_small_4_1", "conv_fwd", 8, conv32(3, 21, 30, 16, 32, 3, 1, 1), _BN_RELU32, {},
+         "k_conv3x3_small<float, 4, 1>, launch_small", ["small_f32<4,1>"]),
+    case("f32_small_4_2", "conv_fwd", 8, conv32(3, 21, 30, 16, 64, 3, 1, 1), _BN_RELU32, {},
+         "k_conv3x3_small<float, 4, 2>, launch_small", ["small_f32<4,2>"]),
+    case("f32_small_8_2", "conv_fwd", 8, conv32(2, 37, 53, 32, 64, 3, 1, 1), _BN_RELU32, {},
+         "k_conv3x3_small<float, 8, 2>: 32 -> 64 3x3, launch_small", ["small_f32<8,2>"]),
+    case("f32_small_8_2_mask", "conv_fwd", 8, conv32(1, 50, 83, 32, 64, 3, 1, 1), _MASK32, {},
+         "k_conv3x3_small<float, 8, 2> input-gradient form, launch_small", ["small_f32<8,2>_mask", "relu_mask_f32"]),
+]
+# ---- weight gradients: f32 operands take 64x64 tiles and always finish with f32 atomics (launch_wgrad); k_wgrad256 is bf16 only
+CASES += [
+    case("f32_wgrad_dma_1x1_acc", "conv_wgrad", 5, conv32(4, 40, 37, 64, 96), wg(True, True), F128,
+         "k_conv_wgrad_dma<float>: 64x64 tiles (Cout 96: a ragged second), atomics, scale, into a non-zero dW; plan_wgrad, launch_wgrad",
+         ["wgrad_dma_f32"]),
+    case("f32_wgrad_dma_1x1_new", "conv_wgrad", 5, conv32(4, 40, 37, 64, 96), wg(), F128,
+         "k_conv_wgrad_dma<float> into a fresh dW, plan_wgrad, launch_wgrad", ["wgrad_dma_f32_new"]),
+    case("f32_wgrad_dma_3x3", "conv_wgrad", 5, conv32(3, 14, 14, 32, 64, 3, 1, 1), wg(True, True), F128,
+         "k_conv_wgrad_dma<float> taps, plan_wgrad, launch_wgrad", ["wgrad_dma_f32_taps"]),
+    case("f32_wgrad_dma_under_f256", "conv_wgrad", 5, conv32(4, 40, 37, 256, 512), wg(True, True), F256,
+         "k_conv_wgrad_dma<float> where bf16 takes k_wgrad256 (wgrad256_ok: bf16 only, so CDDMSL_GEMM256=2 must not move it); plan_wgrad",
+         ["wgrad_f32_not_256"]),
+    case("f32_wgrad_1x1_s2", "conv_wgrad", 4, conv32(4, 41, 37, 64, 96, 1, 2), wg(True, True), {},
+         "k_conv_wgrad<float> 1x1 stride 2 with the FrozenBN scale into a non-zero dW (not 'same' in plan_wgrad), odd map: 4 x 21 x 19 rows; "
+         "run_wgrad", ["wgrad_1x1_s2_f32"]),
+    case("f32_wgrad_1x1_s2_even", "conv_wgrad", 4, conv32(4, 40, 38, 64, 96, 1, 2), wg(True, True), {},
+         "k_conv_wgrad<float> 1x1 stride 2, even map (the last row and column are never read), plan_wgrad (not 'same')", ["wgrad_1x1_s2_f32_even"]),
+    case("f32_wgrad_1x1_s2_one_row", "conv_wgrad", 4, conv32(1, 1, 37, 64, 96, 1, 2), wg(True, True), {},
+         "k_conv_wgrad<float> 1x1 stride 2, degenerate: one image of one row, 19 output pixels, plan_wgrad", ["wgrad_1x1_s2_f32_one_row"]),
+    case("f32_wgrad_s56", "conv_wgrad", 4, conv32(37, 1, 56, 64, 136, 1, 56), wg(False, True), {},
+         "k_conv_wgrad<float>: the stride-56 1x1 query projection (not 'same' in plan_wgrad), run_wgrad", ["wgrad_s56_f32"]),
+]
+# ---- batched products on f32 operands (f32 stores: the out_f32 flag is for bf16 operands)
+_NT32 = dict(bias=False, out_f32=False)
+CASES += [
+    case("f32_nt_128", "gemm_nt_batched", 1, dict(nt(70, 40, 32, 3), dtype="f32"), _NT32, F128,
+         "k_conv_fwd<float> over gridDim.y batches, packed operands, plan_fwd's default", ["nt_f32"]),
+    case("f32_nt_256", "gemm_nt_batched", 3, dict(nt(300, 256, 32, 2), dtype="f32"), _NT32, F256,
+         "k_conv_fwd256<float> batched, packed operands, plan_fwd (use_gemm256 with the batch count)", ["fwd256_batched_f32"]),
+    case("f32_nt_regions", "gemm_nt_batched", 1, dict(nt(32, 56, 64, 5, sa=4096, sw=3584, sc=1792, a_off=2048), dtype="f32"), _NT32, {},
+         "k_conv_fwd<float> on the attention pool's per-region layout: A the second half of a two-part buffer (batches 2 * M * K apart, "
+         "operand offset M * K), plan_fwd's default", ["nt_f32_strided"]),
+    case("f32_nt_shared_a", "gemm_nt_batched", 1, dict(nt(70, 40, 32, 9, ldb=288, sw=32), sa=0, dtype="f32"), _NT32, {},
+         "k_conv_fwd<float> on the RPN head's sparse input-gradient layout: one A for all nine batches (sa = 0), B the tap's 32 columns of "
+         "rows 288 apart, plan_fwd's default", ["nt_f32_shared_a"]),
+    case("f32_tn_stream", "gemm_tn_batched", 7, dict(tn(56, 32, 256, 70), dtype="f32"), dict(accumulate=False, out="f32"), {},
+         "k_gemm_tn_stream<float> where bf16 takes k_gemm_tn_small (bf16 only): one reduction tile, 70 batches, plan_gemm_tn", ["tn_stream_f32"]),
+    case("f32_tn_stream_2", "gemm_tn_batched", 7, dict(tn(100, 32, 128, 77), dtype="f32"), dict(accumulate=False, out="f32"), {},
+         "k_gemm_tn_stream<float>, two reduction tiles, runs of batches per block, plan_gemm_tn", ["tn_stream_f32_two_tiles"]),
+    case("f32_tn_dma_acc", "gemm_tn_batched", 5, dict(tn(700, 64, 96, 3), dtype="f32"), dict(accumulate=True, out="f32"), {},
+         "k_conv_wgrad_dma<float> batched, f32 atomics into a non-zero out, plan_gemm_tn's last branch", ["wgrad_dma_f32_batched"]),
+]
+# ---- what the f32 records hold beyond the instantiations above (bench_gemm_launches_f32.json, stock_gemm_launches_f32.json: the records
+# decide): epilogue sets -- the out_f32 flag on f32 operands (layers.linear(..., out_f32=True) passes it in either dtype; the store is
+# f32 anyway), a pooled residual on the 128x128 kernel (too few tiles for use_gemm256 on one image), the bottleneck's residual sets on
+# k_conv_fwd2, a weight gradient accumulated without a scale -- a store-mode k_conv_wgrad_dma<float> product (fewer than 64 batches),
+# and the attention pool's, the mapper's and the RPN head's strided layouts, which only a case with the same strides covers
+# (batched_layout), at the one-image sizes recorded: 34 regions, 32 heads, 256 gathered rows.
+_SETS32_MORE = {"f32": fwd(out_f32=True), "bias_f32": fwd(bias=True, out_f32=True), "bias_relu_f32": fwd(bias=True, relu=True, out_f32=True)}
+for k, e in _SETS32_MORE.items():
+    CASES.append(case(f"f32_fwd_1x1_{k}", "conv_fwd", 1, conv32(2, 9, 37, 36, 136), e, F128,
+                      "k_conv_fwd<float> 1x1 with the out_f32 flag set on f32 operands (heads and linear layers), plan_fwd's default",
+                      ["f32_recorded", "fwd_f32_out_flag"]))
+CASES += [
+    case("f32_fwd_3x3_bias_relu", "conv_fwd", 1, conv32(2, 9, 13, 32, 96, 3, 1, 1), _F32_SETS["bias_relu"], F128,
+         "k_conv_fwd<float> taps, the RPN head's 3x3 epilogue (bias, ReLU, no scale), plan_fwd's default", ["f32_recorded", "fwd_f32_taps"]),
+    case("f32_fwd_res_pool", "conv_fwd", 1, conv32(3, 15, 21, 36, 136), fwd(residual="pooled"), F128,
+         "k_conv_fwd<float> with the AvgPool2d(2)-backward residual (res_pool is legal on the 128x128 kernel; not on k_conv_fwd2: fwd2_legal), "
+         "odd sizes, plan_fwd's default", ["f32_recorded", "fwd_res_pool_f32"]),
+]
+for k in ("bn", "bn_res_relu", "mask_res"):
+    CASES.append(case(f"f32_fwd2_1x1_{k}", "conv_fwd", 11, conv32(2, 19, 23, 48, 384), _F32_SETS[k], FWD2,
+                      "k_conv_fwd2<float, false, -1> under a bottleneck's residual / shortcut epilogues, launch_fwd2",
+                      _tags(k, "f32_recorded", "fwd2_1x1_f32")))
+CASES += [
+    case("f32_wgrad_dma_1x1_acc_noscale", "conv_wgrad", 5, conv32(4, 40, 37, 64, 96), wg(False, True), F128,
+         "k_conv_wgrad_dma<float> into a non-zero dW without a scale (linear layers), plan_wgrad, launch_wgrad", ["f32_recorded", "wgrad_dma_f32_noscale"]),
+    case("f32_tn_dma_store", "gemm_tn_batched", 5, dict(tn(56, 32, 96, 34), dtype="f32"), dict(accumulate=False, out="f32"), {},
+         "k_conv_wgrad_dma<float> batched in store mode (fewer than 64 batches: neither k_gemm_tn_small nor k_gemm_tn_stream), one block "
+         "per 64x64 tile, ragged in N and K, plan_gemm_tn's last branch", ["f32_recorded", "tn_dma_store_f32"]),
+]
+_ATTN32 = [  # (id, entry, kid, geometry, epilogue, why): the layouts of _ATTN, nt_mapper and nt_rpn_sparse_dx at the f32 records' one-image sizes
+    ("f32_nt_heads", "gemm_nt_batched", 1, nt(34, 64, 2048, 32, 65536, 2048, 2048, 2048, 131072, 64), _NT32,
+     "o = Z @ Wv^T per head: A rows H*C apart, k_conv_fwd<float> (64 columns), plan_fwd's default"),
+    ("f32_nt_regions_full", "gemm_nt_batched", 1, nt(32, 56, 2048, 34, 2048, 2048, 56, 131072, 114688, 1792, a_off=65536), _NT32,
+     "S = U . tok^T per region, U = the second half of zu, k_conv_fwd<float>, plan_fwd's default"),
+    ("f32_nt_qk", "gemm_nt_batched", 3, nt(34, 2048, 64, 32, 2048, 2048, 131072, 64, 64, 2048, c_off=65536), _NT32,
+     "U = q0 @ Wk per head into the second half of zu (rows 2*H*C apart): 34 rows of a 256-row tile, k_conv_fwd256<float>, plan_fwd "
+     "(use_gemm256 with the batch count)"),
+    ("f32_tn_dwv", "gemm_tn_batched", 5, tn(34, 64, 2048, 32, 2048, 65536, 2048, 64, 2048, 131072), dict(accumulate=True, out="f32"),
+     "dWv += dO^T Z per head: f32 atomics, B rows H*C apart, k_conv_wgrad_dma<float>, plan_gemm_tn's last branch"),
+    ("f32_nt_mapper", "gemm_nt_batched", 1, nt(34, 1024, 1920, 16, 30720, 30720, 1024, 1920, 1920, 34816), _NT32,
+     "the mapper's per-head product (A, B rows 30720 apart): too few 256x256 tiles on one image, k_conv_fwd<float>, plan_fwd's default"),
+    ("f32_nt_rpn_sparse_dx", "gemm_nt_batched", 1, dict(nt(256, 1024, 1024, 9, 1024, 9216, 1024, None, 1024, 262144), sa=0), _NT32,
+     "the RPN head's sparse input gradient: 256 gathered rows shared by the nine taps (sa = 0), B the tap's 1 024 columns of rows 9 216 "
+     "apart; k_conv_fwd<float>, plan_fwd's default"),
+]
+for id_, entry, kid, geom, epi, why in _ATTN32:
+    CASES.append(case(id_, entry, kid, dict(geom, dtype="f32"), epi, {}, why + " (the f32 step's one-image launch)", ["f32_recorded", "batched_strided_f32"]))
+
 REQUIRED_VARIANTS = [
     "fwd", "fwd_reg_pool", "fwd2_1x1", "fwd2_taps", "fwd256_1x1", "fwd256_taps", "fwd256_res_pool", "fwd256_persistent",
     "fwd256_tail_split", "fwd256_batched", "fwd256_res_f32", "fwd256_out_f32", "small<1,1>", "small<1,2>", "small<8,2>", "small<4,1>",
     "small<4,2>", "small<8,2,1>", "small<32,2,1>", "wgrad256_ws", "wgrad256_atomics", "wgrad_dma", "wgrad_s56", "tn_small", "tn_stream",
     "relu_mask", "dgrad_wd", "full_m", "over_2gib", "batched_strided", "fwd_f32",
     "stem_7x7_s2", "fwd_1x1_s2", "fwd2_1x1_s2", "fwd256_1x1_s2", "fwd256_persistent_s2", "fwd256_tail_split_s2", "wgrad_1x1_s2", "nt_shared_a",
+    # the f32 instantiations (and what only f32 dispatch does: the one-tap rule, no k_wgrad256, no k_gemm_tn_small)
+    "fwd_f32_ragged_k", "fwd_f32_taps", "fwd_1x1_s2_f32", "fwd_f32_s56", "fwd_f32_one_tap_rule", "fwd_reg_pool_f32", "fwd256_1x1_f32",
+    "fwd256_taps_f32", "fwd256_1x1_s2_f32", "fwd256_res_pool_f32", "fwd2_1x1_f32", "fwd2_taps_f32", "fwd2_1x1_s2_f32", "small_f32<1,1>",
+    "small_f32<1,2>", "small_f32<4,1>", "small_f32<4,2>", "small_f32<8,2>", "small_f32<8,2>_mask", "relu_mask_f32", "wgrad_dma_f32",
+    "wgrad_dma_f32_new", "wgrad_dma_f32_taps", "wgrad_f32_not_256", "wgrad_1x1_s2_f32", "wgrad_1x1_s2_f32_even", "wgrad_1x1_s2_f32_one_row",
+    "wgrad_s56_f32", "nt_f32", "fwd256_batched_f32", "nt_f32_strided", "nt_f32_shared_a", "tn_stream_f32", "tn_stream_f32_two_tiles",
+    "wgrad_dma_f32_batched",
+    # what the f32 records added
+    "f32_recorded", "fwd_f32_out_flag", "fwd_res_pool_f32", "wgrad_dma_f32_noscale", "tn_dma_store_f32", "batched_strided_f32",
 ]
 # (kernel id, M, N, K) bench launches the issue names: each has a full-M case
 BENCH_SHAPES = [(3, 1605632, 512, 4608), (3, 401408, 2048, 512), (3, 1065600, 256, 64), (3, 66400, 1024, 9216), (11, 1065600, 128, 1152),

@@ -1,6 +1,7 @@
 """The exact-product checker itself (tests/exact_gemm.py), on the CPU: the float64 reference against ATen, the bound against an f32
 convolution in another summation order, negative controls the bound must reject -- with the verdict of the old 2e-2 * max criterion
-printed next to it -- and the coverage of the recorded launches (the bench step's and the stock R50-C4 step's) by the GPU case table."""
+printed next to it --, the same for f32 operands, and the coverage of the recorded launches (the bench step's and the stock R50-C4 step's,
+in bf16 and in f32) by the GPU case table."""
 import json
 import os
 
@@ -170,8 +171,118 @@ def test_rounding_bias_separates_rne_from_truncation():
     assert n >= 100000 and abs(rne) <= 0.02 and -0.55 < tr < -0.45, (rne, tr, n)
 
 
+# ------------------------------------------------------------------------------------------------ f32 operands
+def test_bound_accepts_atens_f32_convolution_of_f32_operands(capsys):
+    """f32 operands: the products are rounded too (one more 2^-24 |a*b| each).  ATen's CPU f32 convolution of f32 Gaussian operands
+    at the shape of the table's f32_fwd256_3x3 cases (K = 288) stays inside the bound with u_out = 2^-24 and the same C_ACC"""
+    g = CASES.conv32(2, 19, 23, 32, 256, 3, 1, 1)
+    assert any(c["geom"] == g for c in CASES.CASES)
+    x = torch.randn(g["N"], g["H"], g["W"], g["Cin"], generator=_g(71))
+    w = torch.randn(g["Cout"], 3, 3, g["Cin"], generator=_g(72)) * (9 * g["Cin"]) ** -0.5
+    f32 = F.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), padding=1).permute(0, 2, 3, 1).reshape(-1, g["Cout"])
+    assert f32.dtype == torch.float32
+    acc, absp = X.conv_exact(x, w, 1, 1)
+    ok, ratio, _ = X.check_bound(f32, acc, absp, torch.float32)
+    ar = X.acc_ratio(f32, acc, absp)
+    with capsys.disabled():
+        print(f"\nATen f32 conv of f32 operands (K = 288): worst |err|/bound {ratio:.3f}, acc_ratio {ar:.3g} (C_ACC = {X.C_ACC:g})")
+    assert ok, ratio
+    assert ar < X.C_ACC
+
+
+def _f32_data(tier, shape, seed, lim=3, scale=1.0):
+    if tier == "A":
+        return torch.randint(-lim, lim + 1, shape, generator=_g(seed)).float()
+    return torch.randn(shape, generator=_g(seed)) * scale
+
+
+def _mutants_f32(tier):
+    """(name, mutant, exact, absprod, operands of the bound) on f32 operands at shapes of the table's f32 cases; tier A data
+    (small integers, power-of-two scales, dyadic bias / residual / dW) or tier B (Gaussian); mutant and exact in float64"""
+    out = []
+    N, H, W, Cin, Cout = 2, 9, 37, 36, 136                      # f32_fwd_1x1_*: 9 chunks of 4 elements
+    x = _f32_data(tier, (N, H, W, Cin), 81)
+    w = _f32_data(tier, (Cout, 1, 1, Cin), 82, scale=Cin ** -0.5)
+    M = N * H * W
+    if tier == "A":
+        scale = torch.pow(2.0, torch.randint(-2, 2, (Cout,), generator=_g(83)).float())
+        bias = torch.randint(-64, 65, (Cout,), generator=_g(84)).float() / 8
+        res = torch.randint(-16, 17, (M, Cout), generator=_g(85)).float() / 4
+        msk = torch.randint(-1, 2, (M, Cout), generator=_g(86)).float()
+    else:
+        scale = torch.rand(Cout, generator=_g(83)) + 0.5
+        bias = torch.randn(Cout, generator=_g(84)) * 0.1
+        res = torch.randn(M, Cout, generator=_g(85)) * 3.0
+        msk = torch.randn(M, Cout, generator=_g(86))
+    acc, absp = X.conv_exact(x, w)
+    # 1. the last 4-element chunk of the reduction dropped (the one chunk of the second K-tile)
+    short, _ = X.conv_exact(x[..., :Cin - 4].contiguous(), w[..., :Cin - 4].contiguous())
+    out.append(("last 4-element chunk of the reduction dropped", short, acc, absp, {}))
+    # 2. stride 2: the tap of the second row tile (rows 128..189 of 190) read one pixel to the right (f32_fwd_1x1_s2_*)
+    x2, w2 = x[..., :32].contiguous(), w[..., :32].contiguous()
+    ex2, ab2 = X.conv_exact(x2, w2, 2, 0)
+    off, _ = X.conv_exact(torch.roll(x2, -1, dims=2), w2, 2, 0)
+    mut = ex2.clone()
+    mut[128:] = off[128:]
+    out.append(("one tap read one pixel off under stride 2", mut, ex2, ab2, {}))
+    # 3. the ReLU mask taken from the neighbouring channel
+    ex = X.epilogue_exact(acc, relu_mask=msk)
+    out.append(("mask taken from the neighbouring channel", X.epilogue_exact(acc, relu_mask=torch.roll(msk, -1, dims=1)), ex, absp, {}))
+    # 4. the scale of channel n + 1 applied to channel n
+    ex = X.epilogue_exact(acc, scale, bias, relu=True)
+    out.append(("scale of channel n+1 applied to channel n", X.epilogue_exact(acc, torch.roll(scale, -1), bias, relu=True), ex, absp,
+                {"scale": scale, "bias": bias}))
+    # 5. the residual added twice
+    ex = X.epilogue_exact(acc, None, None, res)
+    out.append(("residual added twice", ex + res.double(), ex, absp, {"residual": res}))
+    # weight gradient at f32_wgrad_dma_1x1_acc: M = 5920 rows, scale and a non-zero dW
+    N, H, W, Cin, Cout = 4, 40, 37, 64, 96
+    M = N * H * W
+    xg, dy = _f32_data(tier, (N, H, W, Cin), 91), _f32_data(tier, (N, H, W, Cout), 92)
+    base = (torch.randint(-100, 101, (Cout, Cin), generator=_g(93)).float() if tier == "A" else torch.randn(Cout, Cin, generator=_g(93))).double()
+    sc = (torch.pow(2.0, torch.randint(-2, 2, (Cout,), generator=_g(94)).float()) if tier == "A" else torch.rand(Cout, generator=_g(94)) + 0.5).view(-1, 1)
+    dw, dabs = X.wgrad_exact(xg, dy, 1, 1)
+    dw, dabs = dw[:, 0], dabs[:, 0]
+    ex = dw * sc.double() + base
+    # 6. one of eight splits of the reduction lost (its atomics never land)
+    rows = slice(2 * (M // 8), 3 * (M // 8))
+    part = dy.view(M, Cout)[rows].double().t() @ xg.view(M, Cin)[rows].double()
+    out.append(("one split's contribution to dW lost", (dw - part) * sc.double() + base, ex, dabs, {"scale": sc, "base": base.abs()}))
+    # 7. dW overwritten instead of accumulated
+    out.append(("dW overwritten instead of accumulated", dw * sc.double(), ex, dabs, {"scale": sc, "base": base.abs()}))
+    return out
+
+
+def test_f32_negative_controls_break_tier_a_and_the_tier_b_bound(capsys):
+    """each mutant of an f32 launch, stored as a correctly rounded f32: tier A data -- not bit-equal to the exact value rounded once;
+    tier B data -- outside check_bound with u_out = 2^-24 (the unmutated value, rounded once, passes both).  Next to it the verdict of
+    the criterion tests/test_gpu_conv.py applies to f32 results, max|got - ref| < 2e-5 * max|ref|."""
+    lines = ["", "f32 negative controls (tier A: must not be bit-equal; tier B: must be rejected by the bound):"]
+    a, b = _mutants_f32("A"), _mutants_f32("B")
+    assert [m[0] for m in a] == [m[0] for m in b] and len(a) == 7
+    missed = []
+    for (name, mut_a, ex_a, absp_a, _), (_, mut_b, ex_b, absp_b, epi) in zip(a, b):
+        assert float(absp_a.max()) < 2 ** 24 and torch.equal(ex_a, ex_a.float().double()), name       # tier A's premise
+        same = torch.equal(mut_a.float(), ex_a.float())
+        ok0, r0, _ = X.check_bound(ex_b.float(), ex_b, absp_b, torch.float32, **epi)
+        ok, ratio, _ = X.check_bound(mut_b.float(), ex_b, absp_b, torch.float32, **epi)
+        old_ok = X.old_criterion(mut_b.float(), ex_b, tol=2e-5)
+        missed += [name] if old_ok else []
+        lines.append(f"  {name:48s} tier A bit-equal: {'YES' if same else 'no'}   old 2e-5*max: {'ACCEPTS' if old_ok else 'rejects'}   "
+                     f"bound: {'ACCEPTS' if ok else 'rejects'} (worst |err|/bound {ratio:.3g}; unmutated {r0:.3g})")
+        assert ok0 and r0 <= 1.0, (name, r0)
+        assert not same, name
+        assert not ok, name
+    lines.append(f"  the 2e-5 * max criterion would have missed: {', '.join(missed) if missed else 'none of these, had it run them'}")
+    with capsys.disabled():
+        print("\n".join(lines))
+
+
 # ------------------------------------------------------------------------------------------------ coverage of the recorded launches
-RECORDS = ("bench_gemm_launches.json", "stock_gemm_launches.json")      # the CLIP benchmark step; the stock R50-C4 configuration's step
+BF16_RECORDS = ("bench_gemm_launches.json", "stock_gemm_launches.json")     # the CLIP benchmark step; the stock R50-C4 configuration's step
+# ... and the same two configurations' f32 steps on one 800x1333 image (the oracle-parity path: tests/test_gpu_e2e.py test_full_size_step_matches_oracle)
+F32_RECORDS = ("bench_gemm_launches_f32.json", "stock_gemm_launches_f32.json")
+RECORDS = BF16_RECORDS + F32_RECORDS
 
 
 def _recorded(name):
@@ -199,9 +310,15 @@ def test_case_table_covers_every_instantiation_and_bench_shape():
     assert not set(CASES.REQUIRED_VARIANTS) - variants, sorted(set(CASES.REQUIRED_VARIANTS) - variants)
     full = {(c["kid"]) for c in CASES.CASES if "full_m" in c.get("variants", ())}
     assert CASES.BENCH_KERNELS <= full, CASES.BENCH_KERNELS - full
-    for record in RECORDS:
+    for record in BF16_RECORDS:
         launched = {e["kernel_id"] for e in _recorded(record)}
         assert launched <= CASES.BENCH_KERNELS, (record, launched - CASES.BENCH_KERNELS)
+    f32_kernels = {(c["entry"], c["kid"]) for c in CASES.CASES if c["geom"]["dtype"] == "f32"}
+    for record in F32_RECORDS:         # (one image: no full-M cases; every kernel an f32 step launches has f32 cases)
+        rec = _recorded(record)
+        assert all(e["geometry"]["dtype"] == "f32" for e in rec), record
+        launched = {(e["entry"], e["kernel_id"]) for e in rec}
+        assert launched <= f32_kernels, (record, launched - f32_kernels)
     # the stock step's strided launches (7x7 stem, stride-2 1x1 forward and weight gradient): each kernel that takes one has a strided case
     strided = {(e["entry"], e["kernel_id"]) for e in _recorded("stock_gemm_launches.json") if e["geometry"].get("stride", 1) > 1}
     assert strided == {("conv_fwd", 1), ("conv_fwd", 3), ("conv_fwd", 11), ("conv_wgrad", 4)}, strided
@@ -212,6 +329,40 @@ def test_case_table_covers_every_instantiation_and_bench_shape():
     assert {c["kid"] for c in big} >= {1, 3, 5, 6, 9}
     for c in CASES.CASES:          # every case says what it targets and where dispatch selects it
         assert c.get("why"), c["id"]
+
+
+N_F32_CASES = 75       # the f32-operand block of the table: 59 cases, one per instantiation and epilogue set, and 16 more that the f32 records
+                       # demanded; none may go without this changing
+
+
+def test_f32_block_is_complete_and_leaves_the_bf16_table_in_place():
+    """The cases before the f32 block keep their index (their seeds are 1000 + 2 * index + tier); the f32 block is all f32, runs in both
+    tiers, adds no full-M and no over-2-GiB case, holds no two cases alike -- so that with the count above and REQUIRED_VARIANTS
+    (one entry per f32 instantiation) a dropped case shows -- and covers each forward kernel under each epilogue set an f32 launch has."""
+    n0 = CASES.N_BF16_TABLE
+    assert n0 == 120 and CASES.CASES[0]["id"] == "fwd_1x1_plain" and CASES.CASES[n0 - 1]["id"] == "nt_rpn_sparse_dx"
+    assert [c["id"] for c in CASES.CASES[:n0] if c["geom"]["dtype"] == "f32"] == ["fwd_f32_1x1", "fwd_f32_1x1_narrow", "stem_7x7_s2_f32",
+                                                                                 "stem_7x7_s2_f32_even"]
+    new = CASES.CASES[n0:]
+    assert len(new) == N_F32_CASES
+    seen = set()
+    for c in new:
+        assert c["geom"]["dtype"] == "f32" and c["tiers"] == CASES.AB and c["id"].startswith("f32_"), c["id"]
+        assert not {"full_m", "over_2gib"} & set(c["variants"]), c["id"]
+        assert c["variants"] and set(c["variants"]) <= set(CASES.REQUIRED_VARIANTS), c["id"]
+        key = json.dumps([c["entry"], c["kid"], c["geom"], c["epi"], c["env"]], sort_keys=True)
+        assert key not in seen, c["id"]
+        seen.add(key)
+        M, N, K = CASES.mnk(c)
+        assert M * N * K * c["geom"].get("batch", 1) <= 1 << 32, (c["id"], "a new GPU test takes seconds: its float64 reference too")
+        if c["entry"] == "conv_fwd":         # residuals and masks of an f32 launch are f32
+            assert c["epi"]["residual"] in (None, "f32", "pooled"), c["id"]
+    sets = {}
+    for c in new:
+        if c["entry"] == "conv_fwd" and c["geom"]["KH"] == 1 and c["geom"]["stride"] == 1 and not c["geom"]["pool"]:
+            sets.setdefault(c["kid"], set()).add(CASES.launch_class(c["entry"], c["kid"], c["geom"], c["epi"])[-1])
+    eight = {CASES.launch_class("conv_fwd", 1, CASES.conv32(1, 1, 1, 4, 4), e)[-1] for e in CASES._F32_SETS.values()}
+    assert len(eight) == 8 and eight <= sets[1] and eight <= sets[3], (eight - sets[1], eight - sets[3])
 
 
 # ------------------------------------------------------------------------------------------------ the dispatch, replayed on the CPU
@@ -251,7 +402,7 @@ def _plan_raw(L, entry, g, epi):
 
 
 def test_dispatch_replayed_through_the_raw_abi_in_plan_only_mode(monkeypatch):
-    """every launch recorded from the bench step and every case of the GPU table -- under the case's switches, the others cleared --
+    """every launch recorded from the bench step, the stock step and their f32 twins, and every case of the GPU table -- under the case's switches, the others cleared --
     goes through the raw C ABI in plan-only mode (no GPU: validate, plan, return): status CDDMSL_OK and the recorded / expected
     kernel id.  Every entry point of the two tables has a raw call in _plan_raw (an unknown one fails there, it is not skipped)."""
     import __graft_entry__ as ge
@@ -262,8 +413,11 @@ def test_dispatch_replayed_through_the_raw_abi_in_plan_only_mode(monkeypatch):
     stock = _recorded("stock_gemm_launches.json")
     todo = [(f"recorded launch {i}", e["entry"], e["geometry"], e["epilogue"], {}, e["kernel_id"]) for i, e in enumerate(rec)]
     todo += [(f"recorded stock launch {i}", e["entry"], e["geometry"], e["epilogue"], {}, e["kernel_id"]) for i, e in enumerate(stock)]
+    for record in F32_RECORDS:
+        assert len(_recorded(record)) >= 40, record
+        todo += [(f"{record} launch {i}", e["entry"], e["geometry"], e["epilogue"], {}, e["kernel_id"]) for i, e in enumerate(_recorded(record))]
     todo += [(c["id"], c["entry"], c["geom"], dict({"emit8": False}, **c["epi"]), c["env"], c["kid"]) for c in CASES.CASES]
-    assert len(rec) >= 367 and len(stock) >= 58 and len(CASES.CASES) >= 120
+    assert len(rec) >= 367 and len(stock) >= 58 and len(CASES.CASES) >= 120 + N_F32_CASES
     bad = []
     was = L.cddmsl_plan_only(1)
     try:

@@ -1,13 +1,14 @@
-"""bf16 convolution / GEMM kernels against the exact float64 product of the operands they were given (tests/exact_gemm.py), for
-every case of tests/gemm_exact_cases.py -- every kernel family and instantiation, the bench's own launch shapes at full M and
-the 32-image geometry past 2 GiB -- in two tiers:
+"""bf16 and f32 convolution / GEMM kernels against the exact float64 product of the operands they were given (tests/exact_gemm.py),
+for every case of tests/gemm_exact_cases.py -- every kernel family and instantiation in either operand type, the bench's own launch
+shapes at full M and the 32-image geometry past 2 GiB -- in two tiers:
 
   A  small-integer operands, power-of-two scales, dyadic bias / residual / dW: every partial sum is exact in f32 in any order
      (split-K, atomics, workspace reductions), so the output must equal the exact value rounded once -- torch.equal.
   B  Gaussian operands: every element inside exact_gemm.check_bound, and a bf16 store without rounding bias.
 
-Plus the launch records (tests/golden/bench_gemm_launches.json, and stock_gemm_launches.json of the stock R50-C4 step) replayed in
-plan-only mode: dispatch still picks the recorded kernel.  And the stock stem as the model calls it (BasicStem.forward_nhwc).
+Plus the launch records (tests/golden/bench_gemm_launches.json, stock_gemm_launches.json of the stock R50-C4 step, and the f32 steps
+of both in bench_gemm_launches_f32.json and stock_gemm_launches_f32.json) replayed in plan-only mode: dispatch still picks the
+recorded kernel.  And the stock stem as the model calls it (BasicStem.forward_nhwc).
 
 Measured on one MI355X, the strided cases of the stock ResNet path and what else its record added; tier A bit-equal in all of them,
 tier B worst |err| / bound (0.99 is a correctly rounded bf16 store of a value just above a power of two; none below 0.05, the mark of
@@ -20,7 +21,39 @@ the bf16 store's rounding bias in ulp or, for f32 outputs, the accumulation rati
   fwd256_roi_crops_s2 0.995 -0.0001      fwd256_persistent_s2 0.996 -0.0003      fwd256_persistent_s2_bn 0.996 -0.0002
   fwd256_tail_split_s2 0.995 -0.0003     wgrad_1x1_s2 0.055 acc 0.43             wgrad_1x1_s2_even 0.068 acc 0.43
   wgrad_1x1_s2_one_row 0.244 acc 0.43    nt_rpn_sparse_dx 0.283 acc 2.03
-  test_stock_stem_against_float64, worst |err| / limit: f32 0.470 (37 x 53), 0.589 (38 x 54); bf16 0.992, 0.986"""
+  test_stock_stem_against_float64, worst |err| / limit: f32 0.470 (37 x 53), 0.589 (38 x 54); bf16 0.992, 0.986
+
+The f32-operand block (the f32_* cases: operands, residuals, masks and output f32; u_out = 2^-24, the same C_ACC = 8), measured on one
+MI355X: tier A bit-equal in all 75, no kernel fix needed; tier B worst |err| / bound, then acc_ratio.  Worst acc_ratio per kernel:
+k_conv_fwd<float> 5.52 (f32_nt_rpn_sparse_dx, K = 1024, 2.4 M outputs), k_conv_fwd_reg<float> 3.58, k_conv_fwd256<float> 5.01
+(f32_nt_qk), k_conv_fwd2<float> 4.25, k_conv3x3_small<float> 4.91, k_conv_wgrad<float> 2.46, k_conv_wgrad_dma<float> 4.27
+(f32_tn_dwv), k_gemm_tn_stream<float> 3.55 -- above the bf16-operand figures because the products are rounded too, and in line with
+ATen's CPU f32 convolution of f32 operands (4.07 at K = 288, tests/test_exact_bound_host.py); none reaches 8.
+  f32_fwd_1x1_plain 0.526 acc 3.43              f32_fwd_1x1_bn 0.500 acc 2.88                 f32_fwd_1x1_bn_relu 0.458 acc 2.56
+  f32_fwd_1x1_bias_relu 0.497 acc 2.93          f32_fwd_1x1_bn_res_relu 0.538 acc 3.11        f32_fwd_1x1_res 0.428 acc 2.31
+  f32_fwd_1x1_mask 0.458 acc 2.68               f32_fwd_1x1_mask_res 0.434 acc 2.63           f32_fwd_3x3_bn_relu 0.538 acc 3.85
+  f32_fwd_3x3_mask 0.550 acc 4.05               f32_fwd_1x1_s2_bn_relu 0.505 acc 3.29         f32_fwd_1x1_s2_bn 0.424 acc 2.61
+  f32_fwd_1x1_s2_bn_relu_even 0.542 acc 3.35    f32_fwd_1x1_s2_bn_even 0.481 acc 2.68         f32_fwd_s56_bias 0.408 acc 2.50
+  f32_fwd_1x1_64_not_small 0.478 acc 2.73       f32_fwd_reg_pool 0.414 acc 2.21               f32_fwd_reg_pool_bn_relu 0.566 acc 3.58
+  f32_fwd256_1x1_plain 0.669 acc 4.85           f32_fwd256_1x1_bn 0.572 acc 3.85              f32_fwd256_1x1_bn_relu 0.535 acc 3.66
+  f32_fwd256_1x1_bias_relu 0.550 acc 3.86       f32_fwd256_1x1_bn_res_relu 0.504 acc 3.29     f32_fwd256_1x1_res 0.536 acc 3.26
+  f32_fwd256_1x1_mask 0.654 acc 4.33            f32_fwd256_1x1_mask_res 0.510 acc 3.37        f32_fwd256_3x3_bn_relu 0.615 acc 4.55
+  f32_fwd256_3x3_mask 0.496 acc 3.60            f32_fwd256_1x1_s2_bn_relu 0.573 acc 3.99      f32_fwd256_1x1_s2_bn_even 0.507 acc 3.53
+  f32_fwd256_res_pool 0.516 acc 3.55            f32_fwd256_res_pool_mask 0.628 acc 4.26       f32_fwd2_1x1_plain 0.555 acc 3.35
+  f32_fwd2_1x1_bn_relu 0.571 acc 3.92           f32_fwd2_1x1_mask 0.547 acc 3.50              f32_fwd2_3x3_bn_relu 0.532 acc 3.88
+  f32_fwd2_3x3_mask 0.501 acc 3.64              f32_fwd2_1x1_s2_bn 0.487 acc 2.98             f32_small_1_1 0.547 acc 3.22
+  f32_small_1_2 0.482 acc 3.32                  f32_small_4_1 0.417 acc 2.93                  f32_small_4_2 0.542 acc 3.88
+  f32_small_8_2 0.650 acc 4.91                  f32_small_8_2_mask 0.568 acc 4.26             f32_wgrad_dma_1x1_acc 0.067 acc 0.53
+  f32_wgrad_dma_1x1_new 0.082 acc 0.58          f32_wgrad_dma_3x3 0.405 acc 2.94              f32_wgrad_dma_under_f256 0.105 acc 0.80
+  f32_wgrad_1x1_s2 0.180 acc 1.23               f32_wgrad_1x1_s2_even 0.172 acc 1.25          f32_wgrad_1x1_s2_one_row 0.393 acc 1.86
+  f32_wgrad_s56 0.455 acc 2.46                  f32_nt_128 0.405 acc 2.45                     f32_nt_256 0.485 acc 2.71
+  f32_nt_regions 0.565 acc 3.89                 f32_nt_shared_a 0.416 acc 2.52                f32_tn_stream 0.418 acc 2.58
+  f32_tn_stream_2 0.479 acc 3.55                f32_tn_dma_acc 0.277 acc 2.21                 f32_fwd_1x1_f32 0.502 acc 3.06
+  f32_fwd_1x1_bias_f32 0.526 acc 3.28           f32_fwd_1x1_bias_relu_f32 0.564 acc 3.41      f32_fwd_3x3_bias_relu 0.461 acc 3.32
+  f32_fwd_res_pool 0.517 acc 2.91               f32_fwd2_1x1_bn 0.628 acc 4.25                f32_fwd2_1x1_bn_res_relu 0.492 acc 2.90
+  f32_fwd2_1x1_mask_res 0.499 acc 2.59          f32_wgrad_dma_1x1_acc_noscale 0.075 acc 0.59  f32_tn_dma_store 0.589 acc 3.90
+  f32_nt_heads 0.546 acc 4.21                   f32_nt_regions_full 0.579 acc 4.48            f32_nt_qk 0.684 acc 5.01
+  f32_tn_dwv 0.646 acc 4.27                     f32_nt_mapper 0.618 acc 4.83                  f32_nt_rpn_sparse_dx 0.707 acc 5.52"""
 import json
 import os
 
@@ -134,12 +167,12 @@ def _run_conv_fwd(c, tier, seed):
         w = wm.to(dt)
     res = rp = msk = None
     if e["residual"] == "pooled":
-        rp = (_ints((N, Ho // 2, Wo // 2, Cout), -16, 16, gen) / 4 if tier == "A" else _gauss((N, Ho // 2, Wo // 2, Cout), gen)).to(torch.bfloat16)
+        rp = (_ints((N, Ho // 2, Wo // 2, Cout), -16, 16, gen) / 4 if tier == "A" else _gauss((N, Ho // 2, Wo // 2, Cout), gen, dt)).to(dt)
     elif e["residual"] in ("bf16", "f32"):
         rdt = torch.bfloat16 if e["residual"] == "bf16" else torch.float32
         res = (_ints((N, Ho, Wo, Cout), -16, 16, gen, torch.float32) / 4).to(rdt) if tier == "A" else _gauss((N, Ho, Wo, Cout), gen, rdt, 3.0)
     if e["relu_mask"]:
-        msk = _ints((N, Ho, Wo, Cout), -1, 1, gen) if tier == "A" else _gauss((N, Ho, Wo, Cout), gen)
+        msk = _ints((N, Ho, Wo, Cout), -1, 1, gen, dt) if tier == "A" else _gauss((N, Ho, Wo, Cout), gen, dt)     # (the operand dtype: b32 mask loads in f32)
     y = hip.conv_fwd(xa, w, scale, bias, rp if rp is not None else res, e["relu"], msk, s, p, pool, e["out_f32"], rp is not None)
     assert _kid() == c["kid"], (_kid(), c["kid"])
     odt = y.dtype
@@ -167,15 +200,16 @@ def _run_conv_wgrad(c, tier, seed):
     Ho, Wo = X.out_geometry(H, W, KH, KW, s, p, pool)
     M = N * Ho * Wo
     gen = _gen(seed)
+    dt = {"bf16": torch.bfloat16, "f32": torch.float32}[g["dtype"]]      # (x and dy; dW and its master are f32 in either)
     if tier == "A":
         lim = 1 if M * 9 >= 2 ** 20 else 3              # bench M: {-1, 0, 1} keeps sums over millions of rows exact
-        x = _ints((N, H, W, Cin), -lim, lim, gen)
-        dy = _ints((N, Ho, Wo, Cout), -lim, lim, gen)
+        x = _ints((N, H, W, Cin), -lim, lim, gen, dt)
+        dy = _ints((N, Ho, Wo, Cout), -lim, lim, gen, dt)
         scale = _pow2(Cout, gen) if e["scale"] else None
         base = _ints((Cout, KH, KW, Cin), -100, 100, gen, torch.float32) if e["accumulate"] else None
     else:
-        x = _gauss((N, H, W, Cin), gen)
-        dy = _gauss((N, Ho, Wo, Cout), gen)
+        x = _gauss((N, H, W, Cin), gen, dt)
+        dy = _gauss((N, Ho, Wo, Cout), gen, dt)
         scale = (torch.rand(Cout, device=DEV, generator=gen) + 0.5) if e["scale"] else None
         base = torch.randn(Cout, KH, KW, Cin, device=DEV, generator=gen) if e["accumulate"] else None
     out = hip.conv_wgrad(x, dy, (Cout, KH, KW, Cin), scale, s, p, pool, out=None if base is None else base.clone())
@@ -207,18 +241,20 @@ def _run_gemm(c, tier, seed):
     g, e = c["geom"], c["epi"]
     M, N, K, B = g["M"], g["N"], g["K"], g["batch"]
     gen = _gen(seed)
+    dt = {"bf16": torch.bfloat16, "f32": torch.float32}[g["dtype"]]      # (both operands; an f32 product stores f32)
     is_nt = c["entry"] == "gemm_nt_batched"
     if is_nt:
         va = ((B, M, K), (g["sa"], g["lda"], 1), g["a_off"])
         vb = ((B, N, K), (g["sw"], g["ldb"], 1), g["b_off"])
         vo = ((B, M, N), (g["sc"], g["ldc"], 1), g["c_off"])
-        odt, acc_out = (torch.float32 if e["out_f32"] else torch.bfloat16), False
+        odt, acc_out = (torch.float32 if e["out_f32"] else dt), False
     else:
         va = ((B, M, N), (g["sa"], g["lda"], 1), g["a_off"])
         vb = ((B, M, K), (g["sb"], g["ldb"], 1), g["b_off"])
         vo = ((B, N, K), (g["so"], g["ldo"], 1), g["c_off"])
         odt, acc_out = (torch.float32 if e["out"] == "f32" else torch.bfloat16), e["accumulate"]
-    mk = (lambda n: _ints((n,), -3, 3, gen)) if tier == "A" else (lambda n: _gauss((n,), gen))
+        assert odt == torch.float32 or dt == torch.bfloat16, "an f32 product has no bf16 store"
+    mk = (lambda n: _ints((n,), -3, 3, gen, dt)) if tier == "A" else (lambda n: _gauss((n,), gen, dt))
     abuf, bbuf = mk(_extent(*va)), mk(_extent(*vb))
     no = _extent(*vo)
     if acc_out:
@@ -244,7 +280,8 @@ def _run_gemm(c, tier, seed):
     if B <= 64:
         bsel = torch.arange(B, device=DEV)
     else:
-        bsel = X.sample_rows(B, [va[1][0] * 2, vb[1][0] * 2, vo[1][0] * obuf.element_size()], tile=64, seed=seed, device=DEV)
+        es = abuf.element_size()
+        bsel = X.sample_rows(B, [va[1][0] * es, vb[1][0] * es, vo[1][0] * obuf.element_size()], tile=64, seed=seed, device=DEV)
     parts = []
     for i in range(0, len(bsel), 4):           # (float64 copies of a few batches at a time)
         bi = bsel[i:i + 4]
@@ -349,6 +386,13 @@ def test_recorded_stock_launches_keep_their_kernels(monkeypatch, golden_dir, cap
     """the same for the stock R50-C4 configuration's step (16 images; tests/golden/stock_gemm_launches.json, recorded with
     tools/record_gemm_launches.py --stock): the 7x7 stem, the stride-2 1x1 convolutions and their weight gradients among them"""
     _replay(monkeypatch, golden_dir, capsys, "stock_gemm_launches.json")
+
+
+@pytest.mark.parametrize("record", ["bench_gemm_launches_f32.json", "stock_gemm_launches_f32.json"])
+def test_recorded_f32_launches_keep_their_kernels(record, monkeypatch, golden_dir, capsys):
+    """the same for the f32 steps of the two configurations on one 800x1333 image -- the instantiations every oracle-parity test runs
+    on (tools/record_gemm_launches.py --dtype f32, with and without --stock)"""
+    _replay(monkeypatch, golden_dir, capsys, record)
 
 
 # ------------------------------------------------------------------------------------------------ the stock stem, as the model calls it

@@ -4,14 +4,17 @@ tools/shape_profile.py): a recording shim around ``hip.conv_fwd``, ``hip.conv_wg
 ``hip.gemm_tn_batched`` notes each call's entry point, full geometry, epilogue flags and the kernel the library picked
 (``cddmsl_last_kernel``).  Writes tests/golden/bench_gemm_launches.json, which tests/test_gpu_gemm_exact.py replays in plan-only mode
 (dispatch still picks the recorded kernel) and tests/test_exact_bound_host.py checks against the exact-product case table.
-A change of dispatch or of the step's shapes must re-record it.  usage: python tools/record_gemm_launches.py [--stock] [--batches 16 32] [--out F]
+A change of dispatch or of the step's shapes must re-record it.  usage: python tools/record_gemm_launches.py [--stock] [--dtype bf16|f32|fp8] [--batches 16 32] [--out F]
 With ``--dtype fp8`` the shim also notes ``hip.conv_fwd_fp8``, ``hip.conv_wgrad_fp8`` and ``hip.fp8_dot_nt``, keeps only those and the
 ``hip.conv_fwd`` calls that write an e4m3 second output (``emit8``), and writes tests/golden/bench_fp8_launches.json (the case table of
 tests/fp8_exact_cases.py is checked against it by tests/test_fp8_bound_host.py); the bf16 file is not touched.
 With ``--stock`` the step is the stock configuration's instead (configs/PascalVOC-Detection/faster_rcnn_R_50_C4.yaml: Detectron2's
 R50-C4 of cddmsl_amd/modeling/resnet.py -- the 7x7 stem, the stride in a block's first 1x1 -- with Res5ROIHeads; one supervised forward
 and backward pass of the model in bf16 on the same 800x1333 images, 16 of them unless --batches says otherwise) and the file
-tests/golden/stock_gemm_launches.json, same format, read by the same tests."""
+tests/golden/stock_gemm_launches.json, same format, read by the same tests.
+With ``--dtype f32`` (alone or with ``--stock``) the step runs the f32 instantiations -- the parity path the oracle tests of
+tests/test_gpu_e2e.py and tests/test_gpu_golden.py hold to the reference -- on ONE 800x1333 image unless --batches says otherwise (the size
+of test_full_size_step_matches_oracle), and the files are tests/golden/bench_gemm_launches_f32.json and stock_gemm_launches_f32.json."""
 import argparse
 import json
 import os
@@ -24,6 +27,8 @@ import torch  # noqa: E402
 OUT = os.path.join(ROOT, "tests", "golden", "bench_gemm_launches.json")
 OUT_FP8 = os.path.join(ROOT, "tests", "golden", "bench_fp8_launches.json")
 OUT_STOCK = os.path.join(ROOT, "tests", "golden", "stock_gemm_launches.json")
+OUT_F32 = os.path.join(ROOT, "tests", "golden", "bench_gemm_launches_f32.json")
+OUT_STOCK_F32 = os.path.join(ROOT, "tests", "golden", "stock_gemm_launches_f32.json")
 STOCK_YAML = os.path.join(ROOT, "configs", "PascalVOC-Detection", "faster_rcnn_R_50_C4.yaml")
 
 
@@ -150,7 +155,7 @@ def record_bench(rec, batches, dtype):
         torch.cuda.empty_cache()
 
 
-def record_stock(rec, batches):
+def record_stock(rec, batches, dtype):
     """one supervised step (forward + backward of the model) of the stock configuration per batch size, the second one recorded"""
     from cddmsl_amd import synthetic
     from cddmsl_amd.config import get_cfg
@@ -158,7 +163,7 @@ def record_stock(rec, batches):
     for batch in batches:
         cfg = get_cfg()
         cfg.merge_from_file(STOCK_YAML)
-        cfg.merge_from_list(["MODEL.COMPUTE_DTYPE", "bf16", "MODEL.DEVICE", "cuda:0"])
+        cfg.merge_from_list(["MODEL.COMPUTE_DTYPE", dtype, "MODEL.DEVICE", "cuda:0"])
         model = build_model(cfg)
         model.load_state_dict(synthetic.make_state_dict_r50(0), strict=False)
         model.train()
@@ -176,17 +181,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=None)
     ap.add_argument("--dtype", default="bf16")
-    ap.add_argument("--stock", action="store_true", help="record the stock R50-C4 configuration's step (bf16) instead of the bench's")
+    ap.add_argument("--stock", action="store_true", help="record the stock R50-C4 configuration's step (bf16 or f32) instead of the bench's")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     fp8 = args.dtype == "fp8"
-    assert not (args.stock and fp8), "--stock records the bf16 step"
-    args.batches = args.batches or ([16] if args.stock else [16, 32])
-    args.out = args.out or (OUT_STOCK if args.stock else OUT_FP8 if fp8 else OUT)
+    f32 = args.dtype == "f32"
+    assert not (args.stock and fp8), "--stock records the bf16 or the f32 step"
+    args.batches = args.batches or ([1] if f32 else [16] if args.stock else [16, 32])
+    args.out = args.out or ((OUT_STOCK_F32 if f32 else OUT_STOCK) if args.stock else OUT_FP8 if fp8 else OUT_F32 if f32 else OUT)
     from cddmsl_amd import hip
     rec = Recorder(hip)
     if args.stock:
-        record_stock(rec, args.batches)
+        record_stock(rec, args.batches, args.dtype)
     else:
         record_bench(rec, args.batches, args.dtype)
     rec.restore()
